@@ -12,12 +12,15 @@ secondary ray traced AND shaded.  N>1 shards the pixels of the SAME view over th
 Host synchronisation: the primary pass of a view (`bake_shading.primary_hits`) compacts the valid pixels with a boolean mask, which synchronises the
 host ONCE per view (the pixel count is needed to size the launch); everything else of a step is stream-ordered.  It is inside the timed region.
 
-After the timed region rank 0 CHECKS the numbers it timed: a pixel subsample of the LAST timed view's maps (all lobes) against the CPU oracle in
-device-arithmetic mode, bit for bit (`parity_check`; a mismatch makes the run fail with exit code 3).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps and prints it; --dump-outputs DIR first writes what the
+last timed step computed (a fixed, seeded pixel sample of its maps) as DIR/<name>.npy.  Everything else runs only with --full:
 
-Rank 0 prints ONE JSON line.  `roofline` prices the timed kernel (bake_view_kernel: all lobes of a view behind one launch) against three
-calibrated roofs -- VALU issue, the vector-memory (L1 / TA) path, HBM-side bytes -- and names the binding one.
-`cpu_baseline` is the CPU oracle (a port of the same algorithm, oracle/) timed on a bounded pixel sample of the same workload.
+  parity_check  a pixel subsample of the LAST timed view's maps (all lobes) against the CPU oracle in device-arithmetic mode, bit for bit
+                (a mismatch makes the run fail with exit code 3); at N > 1 also the gathered image against what the ranks sent.
+  roofline      prices the timed kernel (bake_view_kernel: all lobes of a view behind one launch) against three calibrated roofs -- VALU
+                issue, the vector-memory (L1 / TA) path, HBM-side bytes -- and names the binding one.
+  extras        other lobe / spp mixes, cfg 5 (path_tracing_single) and refine's diffuse pass, timed with their own events.
+  cpu_baseline  the CPU oracle (a port of the same algorithm, oracle/) timed on a bounded pixel sample of the same workload.
 """
 import argparse
 import json
@@ -120,6 +123,23 @@ def load_pmc(rays_per_launch, node_bytes):
     return None, "; ".join(why)
 
 
+DUMP_BYTES = 48 << 20      # --dump-outputs: the files together stay well under 64 MB
+
+
+def dump_outputs(out_dir, maps, pix, lobes):
+    """maps (n_maps, n, 3) float32 of one view in pixel order `pix` (n,): the same seeded sample of the n pixels every run, one float32 file per map
+    (lobe0_Ld; lobe<l>_Ls0 / lobe<l>_Ls1 for specular level l) and pixel_index.npy (float64, exact) with the image pixel ids of the rows."""
+    n_maps, n = maps.shape[0], maps.shape[1]
+    k = min(n, DUMP_BYTES // (n_maps * 3 * 4 + 8))
+    rows = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, k, replace=False))).to(maps.device)
+    os.makedirs(out_dir, exist_ok=True)
+    names = [nm for l in lobes for nm in ([f"lobe{l}_Ld"] if l == 0 else [f"lobe{l}_Ls0", f"lobe{l}_Ls1"])]
+    assert len(names) == n_maps
+    for m, name in enumerate(names):
+        np.save(os.path.join(out_dir, name + ".npy"), maps[m, rows].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "pixel_index.npy"), pix[rows].cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -156,6 +176,10 @@ def main():
     ap.add_argument("--cpu-repeats", type=int, default=3, help="repeats of the cpu_baseline sample (the median is reported; each takes --cpu-seconds / repeats)")
     ap.add_argument("--scene-scaling", type=str, default="", help="comma-separated triangle counts: also measure the 7-lobe bake on rooms of these sizes (extras.scene_scaling), e.g. 200000,1000000,3000000,6000000")
     ap.add_argument("--scene-scaling-views", type=int, default=8)
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the checks and side measurements: parity_check (and, N > 1, the "
+                    "gathered-image check), roofline, extras, cpu_baseline.  A plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write a fixed, seeded pixel sample of the maps the last timed step computed "
+                    "(rank 0: the gathered image at N > 1) as DIR/<name>.npy, float32, with their image pixel ids (pixel_index.npy, float64)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -328,7 +352,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dist.all_reduce(rays_t, op=dist.ReduceOp.SUM)
         dist.all_reduce(ranks_seen, op=dist.ReduceOp.SUM)
-        if gatherer is not None:
+        if gatherer is not None and args.full:
             # the gathered image of the last view holds exactly the ranks' local maps: an order-independent integer checksum (the float bits summed
             # as int64, wrapping) of what every rank sent, reduced over the ranks, against the same checksum of what a receiving rank holds
             sent = last_maps.view(torch.int32).to(torch.int64).sum().reshape(1)
@@ -361,7 +385,12 @@ def main():
                       "gathered_image_matches_what_the_ranks_sent": gather_ok},
     }
 
-    if rank == 0 and not args.no_roofline and one_launch and ev_view:
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path receives from the last timed step: the maps, rank 0's pixels (the whole image once gathered)
+        out, pix = (full, torch.arange(H * W, device=dev)) if gatherer is not None else (last_maps, pix_local)
+        dump_outputs(args.dump_outputs, out, pix, lobes)
+
+    if args.full and rank == 0 and not args.no_roofline and one_launch and ev_view:
         # ---- roofline of the timed kernel (bake_view_kernel: all lobes of a view behind one launch) ----
         ms = [e0.elapsed_time(e1) for e0, e1, _ in ev_view]
         rays_per_launch = float(np.mean([n for _, _, n in ev_view]))
@@ -475,7 +504,7 @@ def main():
 
     # ---- the timed output checked: a pixel subsample of the LAST timed view, every lobe, against the CPU oracle in device-arithmetic mode, bit for bit
     parity_failed = False
-    if rank == 0 and args.parity_pixels > 0 and one_launch and last_g[0] is not None:
+    if args.full and rank == 0 and args.parity_pixels > 0 and one_launch and last_g[0] is not None:
         import oracle
         oracle.build()
         g, view_checked = last_g[0]
@@ -505,7 +534,7 @@ def main():
                                   "what": "the maps written by the LAST TIMED step (not a re-bake), evenly spaced valid pixels", "mismatches": mism[:8], "oracle_seconds": round(time.perf_counter() - t0c, 2)}
         del osc, oem, oslf
 
-    if rank == 0 and world == 1 and not args.no_extras and one_launch:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and one_launch:
         # ---- extras with their own events: SURVEY 8(d)'s n_lobes = 1 figure (the diffuse lobe alone: fully incoherent secondary rays) and the reference's own
         # spp mix (bake_shading.py:90,143: diffuse 256, specular 64 / 128 x 5), on views of the same sequence
         def timed_views(lobe_ids, spps, n_views=4):
@@ -557,7 +586,7 @@ def main():
             torch.cuda.empty_cache()
         result.setdefault("extras", {})["scene_scaling"] = rows
 
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # (before the CPU baseline: its OpenMP team keeps spinning for a while after the last parallel region, and this loop of small launches is
         #  bound by the host thread that issues them -- on a box whose cgroup grants exactly as many CPUs as that team has threads)
         # ---- extras: BASELINE configs[4] (train_brdf_crf / train_emitter inner loop: differentiable one-bounce path tracer, SPP 32) on the same scene
@@ -582,7 +611,7 @@ def main():
         result["extras"]["refine_diffuse_pass_reference_batch"] = bench_refine.run_f1(scene, emitter, slf_np, dev, batch_pixels=10240, batches=4)
         result["extras"]["refine_diffuse_pass_default_batch"] = bench_refine.run_f1(scene, emitter, slf_np, dev, batch_pixels=163840, batches=2)
 
-    if rank == 0 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and args.cpu_seconds > 0:
         # (at N > 1 too: the timed region is over -- `value` is final --, the other ranks wait in the closing barrier, whose timeout is --collective-timeout)
         # ---- CPU baseline: the oracle (port of the same algorithm) on a bounded pixel sample of the same workload ----
         import oracle

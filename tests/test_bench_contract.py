@@ -12,9 +12,9 @@ from conftest import REPO
 pytestmark = pytest.mark.gpu
 
 
-def _run(*extra, env_extra=None, extras=True):
+def _run(*extra, env_extra=None, extras=True, full=True):
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--height", "120", "--width", "160", "--spp", "32", "--tris", "20000",
-           "--slf-res", "64", "--views", "4", "--cpu-seconds", "0.5"] + ([] if extras else ["--no-extras"]) + list(extra)
+           "--slf-res", "64", "--views", "4", "--cpu-seconds", "0.5"] + (["--full"] if full else []) + ([] if extras else ["--no-extras"]) + list(extra)
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=600, env=dict(os.environ, **(env_extra or {})))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -47,6 +47,29 @@ def test_single_gpu_line():
 
 
 @pytest.mark.timeout(900)
+def test_plain_line_times_the_steps_and_dumps_their_outputs(tmp_path):
+    """Without --full the line holds the headline and nothing that needs runs of its own (no roofline, parity check, extras or CPU baseline); --steps sets
+    the timed steps; --dump-outputs writes the last timed step's maps, the same bits in a second run -- one with --full, whose parity check passes them."""
+    import numpy as np
+    d = _run("--steps", "2", "--dump-outputs", str(tmp_path / "plain"), full=False)
+    assert d["steps"] == 2 and len(d["config"]["ms_by_view"]) == 2 and d["ms_per_step"] > 0 and d["unit"] == "Mrays/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["metric"].startswith("bake_shading throughput")
+    assert abs(d["value"] - d["config"]["rays_per_step"] / d["ms_per_step"] / 1e3) <= 0.02 * d["value"]
+    assert not {"roofline", "parity_check", "extras", "cpu_baseline", "gpu_over_cpu"} & set(d)
+    f = _run("--steps", "2", "--dump-outputs", str(tmp_path / "full"), extras=False)
+    assert f["parity_check"]["bit_exact"] is True and "cpu_baseline" in f and "roofline" in f
+    names = ["lobe0_Ld"] + [f"lobe{l}_Ls{k}" for l in range(1, 7) for k in (0, 1)] + ["pixel_index"]
+    assert sorted(os.listdir(tmp_path / "plain")) == sorted(n + ".npy" for n in names)
+    assert sum(os.path.getsize(tmp_path / "plain" / (n + ".npy")) for n in names) <= 64 << 20
+    pix = np.load(tmp_path / "plain" / "pixel_index.npy")
+    assert pix.dtype == np.float64 and np.array_equal(pix, np.arange(120 * 160))          # the whole image fits the budget at this size
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / (n + ".npy")), np.load(tmp_path / "full" / (n + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    assert np.abs(np.load(tmp_path / "plain" / "lobe0_Ld.npy")).sum() > 0
+
+
+@pytest.mark.timeout(900)
 def test_forced_process_group_of_one_runs_rccl():
     """IRIS_BENCH_FORCE_PG=1: RCCL's communicator, the gather of a view and the permutation of the received buffer execute on this one GPU"""
     for collective in ("gather", "all_gather"):
@@ -63,7 +86,7 @@ def _two_ranks(*extra, env_extra=None, expect_ok=True, n=2):
     import time
     env = dict(os.environ, IRIS_BENCH_BACKEND="gloo", **(env_extra or {}))
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--height", "120", "--width", "160", "--spp", "32",
-           "--tris", "20000", "--slf-res", "64", "--views", "4", "--cpu-seconds", "0", "--no-extras", "--no-roofline"] + list(extra)
+           "--tris", "20000", "--slf-res", "64", "--views", "4", "--cpu-seconds", "0", "--no-extras", "--no-roofline", "--full"] + list(extra)
     t0 = time.time()
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=600, env=env)
     dt = time.time() - t0
@@ -94,7 +117,7 @@ def test_the_drivers_launch_form():
     env = dict(os.environ, IRIS_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--height", "120", "--width", "160", "--spp", "32", "--tris", "20000", "--slf-res", "64",
-           "--views", "4", "--cpu-seconds", "0", "--no-extras", "--no-roofline"]
+           "--views", "4", "--cpu-seconds", "0", "--no-extras", "--no-roofline", "--full"]
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -126,7 +149,7 @@ def test_eight_ranks_full_size_line_is_complete():
     `cpu_baseline` (run by rank 0 after the timed region), the parity check of the timed maps, the gathered image equal to what the ranks sent."""
     import time
     env = dict(os.environ, IRIS_BENCH_BACKEND="gloo")
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--cpu-seconds", "3", "--cpu-repeats", "1", "--no-extras"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--cpu-seconds", "3", "--cpu-repeats", "1", "--no-extras", "--full"]
     t0 = time.time()
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=1400, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

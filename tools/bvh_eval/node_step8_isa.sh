@@ -6,11 +6,13 @@ import sys; sys.path.insert(0, 'tools')
 import isa_flags
 h, a, f = isa_flags.makefile_flags()
 print(h, a, ' '.join(x for x in f if x != '-fPIC'))")"
-$HIPCC --offload-arch=$ARCH $FLAGS -Iinclude -S --cuda-device-only -o /tmp/node_step8.s tools/bvh_eval/node_step8_isa.hip 2>/dev/null || exit 1
-python3 - <<'PY'
-import re, json
+S=$(mktemp --suffix=.s) || exit 1
+trap 'rm -f "$S"' EXIT
+$HIPCC --offload-arch=$ARCH $FLAGS -Iinclude -S --cuda-device-only -o "$S" tools/bvh_eval/node_step8_isa.hip 2>/dev/null || exit 1
+python3 - "$S" <<'PY'
+import re, json, sys
 from collections import Counter
-txt = open("/tmp/node_step8.s").read()
+txt = open(sys.argv[1]).read()
 out = {}
 for w in (4, 8):
     body = re.search(r"^_Z12visit_kernelILi%d.*?s_endpgm" % w, txt, re.S | re.M).group(0).splitlines()
