@@ -5,6 +5,7 @@ The reference wraps Mitsuba's OptiX closest hit; here the scene is a BVH built o
 """
 import ctypes as C
 import math
+import threading
 
 import numpy as np
 import torch
@@ -167,17 +168,22 @@ def ray_intersect(scene, xs, ds):
 # cfg 5: the one-bounce MIS path tracer the reference trains through (utils/path_tracing.py:320-407)
 # ----------------------------------------------------------------------------------------------------------------------
 _SIDE = {}
+_SIDE_LOCK = threading.Lock()
 
 
 def _side_stream(dev):
     """one extra HIP stream per (device, calling stream) for stages that are independent of each other: calls issued on different streams (a training loop that runs
-    its independent path_tracing_single calls side by side) do not queue their emitter-sampling stages behind one another"""
+    its independent path_tracing_single calls side by side) do not queue their emitter-sampling stages behind one another.
+    Thread-safe: the table is read and trimmed under a lock and the caller keeps its own reference, so a stream dropped from the table for another thread's entry
+    stays valid for the call that holds it (the fork / join events order the work, not the table)."""
     key = (torch.device(dev).index if torch.device(dev).index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
-    if key not in _SIDE:
-        if len(_SIDE) >= 16:
-            _SIDE.pop(next(iter(_SIDE)))
-        _SIDE[key] = torch.cuda.Stream(device=dev)
-    return _SIDE[key]
+    with _SIDE_LOCK:
+        s = _SIDE.get(key)
+        if s is None:
+            if len(_SIDE) >= 16:
+                _SIDE.pop(next(iter(_SIDE)))
+            s = _SIDE[key] = torch.cuda.Stream(device=dev)
+        return s
 
 
 class _PtAccumulate(torch.autograd.Function):
@@ -397,17 +403,22 @@ def _lobe_trace(scene, position, normal, wo, mat, s1, s2, lobe, roughness=0.0):
 
 
 class _Counts:
-    """Pinned host words the device-side path counts are copied into (one per device): the ONE thing a bounce hands back to the host -- the number of paths that
-    continue, which sizes the next bounce's launches and the material network's evaluation (a caller-supplied callable) -- as a 4-byte copy and an event wait
-    instead of torch.nonzero (a scan, a host synchronisation and an index tensor) plus one ATen gather per state array."""
-    _host = {}
+    """Pinned host words the device-side path counts are copied into (one per device AND per host thread): the ONE thing a bounce hands back to the host -- the number
+    of paths that continue, which sizes the next bounce's launches and the material network's evaluation (a caller-supplied callable) -- as a 4-byte copy and an event
+    wait instead of torch.nonzero (a scan, a host synchronisation and an index tensor) plus one ATen gather per state array.
+    The word belongs to the calling thread: a thread finishes its read before it issues its next copy, so calls from several threads (each on its own stream or on
+    the same one) never see each other's count."""
+    _local = threading.local()
 
     @classmethod
     def read(cls, count, dev):
         key = torch.device(dev).index if torch.device(dev).index is not None else torch.cuda.current_device()
-        h = cls._host.get(key)
+        host = getattr(cls._local, "host", None)
+        if host is None:
+            host = cls._local.host = {}
+        h = host.get(key)
         if h is None:
-            h = cls._host[key] = torch.empty(1, dtype=torch.int32).pin_memory()
+            h = host[key] = torch.empty(1, dtype=torch.int32).pin_memory()
         h.copy_(count, non_blocking=True)
         ev = torch.cuda.Event(); ev.record(torch.cuda.current_stream(dev)); ev.synchronize()
         return int(h[0])

@@ -313,6 +313,30 @@ def sample_brdf(s1, s2, wo, normal, mat):
     return wi, pdf, w
 
 
+class DrawSource:
+    """Seeded uniforms drawn while an integrator runs, in place of a recorded `uniforms` list: the integrators below ask it for each draw at the
+    moment its size (the survivor count of a bounce) is known.  Every array handed out is appended to `recorded`, in the order the HIP integrators
+    consume `uniforms=`, so `recorded` can be passed to them unchanged.
+    edge_frac > 0 plants the extremes torch.rand can return, 0.0 and 1 - 2**-24, each into a fraction edge_frac / 2 of every draw (fixed flat positions
+    with an odd stride, so both columns of an (N, 2) draw receive them)."""
+    TOP = np.float32(1.0 - 2.0 ** -24)
+
+    def __init__(self, seed, edge_frac=0.0):
+        self.rng = np.random.default_rng(seed)
+        self.edge_frac = float(edge_frac)
+        self.recorded = []
+
+    def __call__(self, *shape):
+        u = self.rng.random(shape, dtype=np.float32)           # [0, 1) on the float32 grid
+        if self.edge_frac > 0.0:
+            step = max(3, int(round(2.0 / self.edge_frac))) | 1
+            flat = u.reshape(-1)
+            flat[0::step] = 0.0
+            flat[1::step] = self.TOP
+        self.recorded.append(u)
+        return u
+
+
 def path_tracing_single(scene, emitter, material_fn, rays_o, rays_d, dx_du, dy_dv, spp, uniforms, radiance=None, trace_roughness=0.0, indir_depth=0):
     """utils/path_tracing.py:320-407.  material_fn(position ndarray) -> dict of ndarrays.  uniforms: the five draws.
     Returns (L (B,3), terms) where terms lets grad_radiance() form dL/d radiance analytically.
@@ -320,8 +344,9 @@ def path_tracing_single(scene, emitter, material_fn, rays_o, rays_d, dx_du, dy_d
     paths whose sampled hit is valid continued by trace_indirect (no gradient) and added with the BRDF weight."""
     rays_o = _f32(rays_o); rays_d = _f32(rays_d); dx_du = _f32(dx_du); dy_dv = _f32(dy_dv); B = rays_o.shape[0]
     rad = emitter.radiance if radiance is None else _f32(radiance).reshape(-1, 3)
-    u = [np.ascontiguousarray(np.asarray(x, np.float32)) for x in uniforms]
-    dudv = u[0].reshape(2, B, spp)
+    src = uniforms if isinstance(uniforms, DrawSource) else None
+    u = None if src is not None else [np.ascontiguousarray(np.asarray(x, np.float32)) for x in uniforms]
+    dudv = src(2, B, spp) if src is not None else u[0].reshape(2, B, spp)
     wi = np.empty((B * spp, 3), np.float32)
     lib().orc_pt_jitter(_p(rays_d), _p(dx_du), _p(dy_dv), _p(dudv), C.c_int64(B), C.c_int(spp), _p(wi))
     pos, nrm, _, tri, vis = scene.ray_intersect(np.repeat(rays_o, spp, 0), wi)
@@ -333,7 +358,10 @@ def path_tracing_single(scene, emitter, material_fn, rays_o, rays_d, dx_du, dy_d
     path_of = np.full(B * spp, -1, np.int32); path_of[sel] = np.arange(N, dtype=np.int32)
     pos, nrm, wo = _f32(pos[sel]), _f32(nrm[sel]), _f32(-wi[sel])
     a, r, m = _mat(material_fn(pos))
-    s1, s2, s1b, s2b = u[1].reshape(-1), u[2].reshape(-1, 2), u[3].reshape(-1), u[4].reshape(-1, 2)
+    if src is not None:
+        s1, s2, s1b, s2b = src(N), src(N, 2), src(N), src(N, 2)
+    else:
+        s1, s2, s1b, s2b = u[1].reshape(-1), u[2].reshape(-1, 2), u[3].reshape(-1), u[4].reshape(-1, 2)
     coef1 = np.empty((N, 3), np.float32); e1 = np.empty(N, np.int32)
     lib().orc_pt_nee(scene.h, emitter.h, _p(pos), _p(nrm), _p(wo), _p(a), _p(r), _p(m), _p(s1), _p(s2), C.c_int64(N), _p(coef1), _p(e1),
                      C.c_float(1e-6), C.c_float(1e-6), C.c_float(0.0 if indir_depth > 0 else 1e-6))     # path_tracing (:260) does not clamp the MIS denominator, path_tracing_single (:366) does
@@ -347,7 +375,7 @@ def path_tracing_single(scene, emitter, material_fn, rays_o, rays_d, dx_du, dy_d
                              _p(coef2), _p(const2), _p(e2), _p(vn), C.c_float(trace_roughness), C.c_float(1e-6))
     if indir_depth > 0:                                     # :300-316
         keep = vn.astype(bool)
-        Li = trace_indirect(scene, emitter, material_fn, pos_n[keep], -wi_b[keep], nrm_n[keep], indir_depth, u[5:])
+        Li = trace_indirect(scene, emitter, material_fn, pos_n[keep], -wi_b[keep], nrm_n[keep], indir_depth, src if src is not None else u[5:])
         const2[keep] = const2[keep] + w_b[keep] * Li         # (f32: one product, one sum per component)
     Lout = np.empty((B, 3), np.float32)
     lib().orc_pt_accumulate(_p(rad), _p(e0), _p(path_of), _p(e1), _p(coef1), _p(e2), _p(coef2), _p(const2), C.c_int64(B), C.c_int(spp), _p(Lout))
@@ -395,14 +423,20 @@ def _apply(Lacc, rows, throughput, radiance, e, coef, cst, weight):
 
 
 def path_tracing(scene, emitter, material_fn, rays_o, rays_d, dx_du, dy_dv, spp, indir_depth, uniforms, radiance=None):
-    """utils/path_tracing.py:214-318 (render.py's integrator).  uniforms: the 5 draws of the first bounce, then trace_indirect's 4 per bounce."""
+    """utils/path_tracing.py:214-318 (render.py's integrator).  uniforms: the 5 draws of the first bounce, then trace_indirect's 4 per bounce (or a DrawSource)."""
     return path_tracing_single(scene, emitter, material_fn, rays_o, rays_d, dx_du, dy_dv, spp, uniforms, radiance, trace_roughness=0.6, indir_depth=indir_depth)
 
 
-def trace_indirect(scene, emitter, material_fn, position, wo, normal, indir_depth, uniforms):
-    """utils/path_tracing.py:409-502"""
+def trace_indirect(scene, emitter, material_fn, position, wo, normal, indir_depth, uniforms, stats=None):
+    """utils/path_tracing.py:409-502.  uniforms: the recorded draws (a list, per bounce rand(N), rand(N,2), rand(N), rand(N,2)) or a DrawSource.
+    stats: optional dict; receives per depth the lists "N" (paths traced), "brdf_miss" (BRDF rays that left the scene, tri_n < 0) and "continue"
+    (paths that go on to the next depth)."""
     position = _f32(position); wo = _f32(wo); normal = _f32(normal); B = position.shape[0]
-    u = [np.ascontiguousarray(np.asarray(x, np.float32)) for x in uniforms]
+    src = uniforms if isinstance(uniforms, DrawSource) else None
+    u = None if src is not None else [np.ascontiguousarray(np.asarray(x, np.float32)) for x in uniforms]
+    if stats is not None:
+        for k in ("N", "brdf_miss", "continue"):
+            stats.setdefault(k, [])
     Lacc = np.zeros((B, 3), np.float32); rows = np.arange(B); thr = np.ones((B, 3), np.float32)
     rad = emitter.radiance
     mat = None
@@ -413,13 +447,13 @@ def trace_indirect(scene, emitter, material_fn, position, wo, normal, indir_dept
         if depth == 0:
             mat = _mat(material_fn(position))
         a, r, m = mat
-        s1, s2 = u.pop(0).reshape(-1), u.pop(0).reshape(-1, 2)
+        s1, s2 = (src(N), src(N, 2)) if src is not None else (u.pop(0).reshape(-1), u.pop(0).reshape(-1, 2))
         assert s1.shape[0] == N and s2.shape[0] == N, f"trace_indirect depth {depth}: {N} paths but draws for {s1.shape[0]} (the recorded uniforms belong to another path set)"
         coef1 = np.empty((N, 3), np.float32); e1 = np.empty(N, np.int32)
         lib().orc_pt_nee(scene.h, emitter.h, _p(position), _p(normal), _p(wo), _p(a), _p(r), _p(m), _p(s1), _p(s2), C.c_int64(N), _p(coef1), _p(e1),
                          C.c_float(1e-12), C.c_float(1e-12), C.c_float(0.0))
         _apply(Lacc, rows, thr, rad, e1, coef1, None, None)
-        s1b, s2b = u.pop(0).reshape(-1), u.pop(0).reshape(-1, 2)
+        s1b, s2b = (src(N), src(N, 2)) if src is not None else (u.pop(0).reshape(-1), u.pop(0).reshape(-1, 2))
         wi, pdf, w, pos_n, nrm_n, tri_n = _lobe_trace(scene, position, normal, wo, mat, s1b, s2b, 0)
         mat_next = _mat(material_fn(pos_n))
         coef2 = np.empty((N, 3), np.float32); const2 = np.empty((N, 3), np.float32); e2 = np.empty(N, np.int32); vn = np.empty(N, np.uint8)
@@ -427,29 +461,39 @@ def trace_indirect(scene, emitter, material_fn, position, wo, normal, indir_dept
                                  _p(coef2), _p(const2), _p(e2), _p(vn), C.c_float(0.6), C.c_float(1e-12))
         _apply(Lacc, rows, thr, rad, e2, coef2, const2, w)
         keep = vn.astype(bool)
+        if stats is not None:
+            stats["N"].append(int(N)); stats["brdf_miss"].append(int((tri_n < 0).sum())); stats["continue"].append(int(keep.sum()))
         rows, thr = rows[keep], np.ascontiguousarray(thr[keep])
         position, wo, normal = _f32(pos_n[keep]), _f32(-wi[keep]), _f32(nrm_n[keep])
         mat = tuple(np.ascontiguousarray(t[keep]) for t in mat_next)
     return Lacc
 
 
-def path_tracing_det(scene, emitter, material_fn, positions, wis, normals, triangle_idxs, spp, indir_depth, uniforms, roughness=None):
-    """utils/path_tracing.py:50-124 (roughness None -> diffuse) and :126-212 (specular).  Returns Lout or (L0out, L1out)."""
+def path_tracing_det(scene, emitter, material_fn, positions, wis, normals, triangle_idxs, spp, indir_depth, uniforms, roughness=None, stats=None,
+                     return_total=False):
+    """utils/path_tracing.py:50-124 (roughness None -> diffuse) and :126-212 (specular).  Returns Lout or (L0out, L1out).
+    uniforms: the recorded draws or a DrawSource; stats: handed to trace_indirect.
+    return_total: returns (that, total, w) -- the per-path totals Le + L_indirect (P, spp, 3) and the lobe weights (P, spp, 3) before the mean
+    (None, None when no row has a hit)."""
     positions = _f32(positions); wis = _f32(wis); normals = _f32(normals)
-    u = [np.ascontiguousarray(np.asarray(x, np.float32)) for x in uniforms]
+    src = uniforms if isinstance(uniforms, DrawSource) else None
+    u = src if src is not None else [np.ascontiguousarray(np.asarray(x, np.float32)) for x in uniforms]
+    total_ = w_ = None
     sel = np.nonzero(np.asarray(triangle_idxs) != -1)[0]; P = len(sel)
     outs = [np.zeros_like(positions) for _ in range(1 if roughness is None else 2)]
     if P:
         position = _f32(np.repeat(positions[sel], spp, 0)); normal = _f32(np.repeat(normals[sel], spp, 0)); wo = _f32(np.repeat(-wis[sel], spp, 0))
-        s2 = u.pop(0).reshape(-1, 2)
+        s2 = src(P * spp, 2) if src is not None else u.pop(0).reshape(-1, 2)
         wi, _, w, pos_n, nrm_n, tri_n = _lobe_trace(scene, position, normal, wo, None, None, s2, 1 if roughness is None else 2, 0.0 if roughness is None else roughness)
         mat_next = material_fn(pos_n)
         Le, _, vn = emitter.eval_emitter(pos_n, tri_n, mat_next["roughness"], 0.6)
         total = Le.copy()
-        total[vn] += trace_indirect(scene, emitter, material_fn, pos_n[vn], -wi[vn], nrm_n[vn], indir_depth, u)
+        total[vn] += trace_indirect(scene, emitter, material_fn, pos_n[vn], -wi[vn], nrm_n[vn], indir_depth, u, stats=stats)
+        total_, w_ = total.reshape(P, spp, 3), w.reshape(P, spp, 3)
         if roughness is None:
             outs[0][sel] = total.reshape(P, spp, 3).mean(1, dtype=np.float64).astype(np.float32)
         else:
             for k in range(2):
                 outs[k][sel] = (w[:, k:k + 1] * total).reshape(P, spp, 3).mean(1, dtype=np.float64).astype(np.float32)
-    return outs[0] if roughness is None else tuple(outs)
+    res = outs[0] if roughness is None else tuple(outs)
+    return (res, total_, w_) if return_total else res
