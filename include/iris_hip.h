@@ -294,6 +294,17 @@ IRIS_API int iris_ngp_create(const float *params, int64_t n_params, double voxel
 IRIS_API int iris_ngp_forward(const iris_ngp *, const float *position, int64_t N, float *albedo, float *roughness, float *metallic, iris_stream_t);
 IRIS_API void iris_ngp_destroy(iris_ngp *);
 
+/* ---- OpenEXR ZIP / ZIPS writer, device half ------------------------------------------------------------- */
+/* Deflate of the scanline blocks of n_maps maps (utils/exr.py scanline_blocks_torch): full (n_maps, n_full, block_bytes) and tail (n_maps, tail_bytes)
+ * hold the PREDICTED bytes (reordered, delta-coded) of every block, device uint8, contiguous.  records receives, map by map, every chunk record as the
+ * file stores it (int32 y = chunk * lines_per_block, int32 size, data): data is a zlib stream of the predicted bytes when that is shorter than the block,
+ * else the raw (un-predicted) block -- OpenEXR's ZIP rule.  records must hold n_maps * (n_full * (block_bytes + 8) + (tail_bytes ? tail_bytes + 8 : 0))
+ * bytes; map_offsets (device int64, n_maps + 1) receives where each map's records start and, last, their total size.  workspace: device scratch of
+ * iris_exr_zip_workspace_bytes() bytes (0: the sizes are not supported).  Four launches on the stream, no host round trip. */
+IRIS_API uint64_t iris_exr_zip_workspace_bytes(int n_maps, int64_t n_full, int64_t block_bytes, int64_t tail_bytes);
+IRIS_API int iris_exr_zip_encode(const uint8_t *full, const uint8_t *tail, int n_maps, int64_t n_full, int64_t block_bytes, int64_t tail_bytes,
+                        int lines_per_block, uint8_t *records, int64_t *map_offsets, void *workspace, uint64_t workspace_bytes, iris_stream_t);
+
 /* ---- misc --------------------------------------------------------------------------------------------- */
 /* Philox uniforms exactly as the bake kernels draw them (for tests): u2[i] = U(seed, idx0+i, stream_id). */
 IRIS_API int iris_philox_u2(uint64_t seed, uint64_t idx0, uint32_t stream_id, int64_t n, float *u2, iris_stream_t);

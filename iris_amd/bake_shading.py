@@ -273,12 +273,17 @@ class MapWriter:
     predictor: utils/exr.scanline_blocks_torch), enqueues one device-to-host copy into pinned buffers on a side stream and returns; writer
     threads wait for the copy's event, deflate and write, so the next view's kernels start while this view is still on its way to disk and
     the host threads do nothing under the GIL but file I/O.  Two buffer sets: a third view waits for the first one's files.  Files appear
-    under their final name only when complete (the CLI's resume rule never sees a truncated file)."""
+    under their final name only when complete (the CLI's resume rule never sees a truncated file).
+    encoder="device" (ZIP / ZIPS only): deflate runs on the GPU too (utils/exr.zip_encode_torch), the copy brings the finished chunk records and
+    per-map offsets (the worst-case size, known in advance: no host synchronisation) and the writer threads only write files."""
 
-    def __init__(self, device, img_hw, compression, n_maps=13, n_buffers=2):
+    def __init__(self, device, img_hw, compression, n_maps=13, n_buffers=2, encoder="host"):
         from concurrent.futures import ThreadPoolExecutor
         from .utils import exr
+        if encoder not in ("host", "device"):
+            raise L.IrisError(f"MapWriter: encoder {encoder!r} is not 'host' or 'device'")
         self.exr, self.compression, self.img_hw, self.n_buffers = exr, compression, tuple(img_hw), n_buffers
+        self.device_zip = encoder == "device" and compression != "none"
         self.stream = torch.cuda.Stream(device=device)
         self.bufs = None                                    # pinned (full, tail) pairs, sized at the first submit
         self.busy = [[] for _ in range(n_buffers)]
@@ -290,8 +295,10 @@ class MapWriter:
         on_written: called (on a writer thread) once ALL of this view's files are complete on disk -- refine_shading's per-view resume marker."""
         exr, (H, W) = self.exr, self.img_hw
         full, tail = exr.scanline_blocks_torch(maps_dev, self.compression)
+        if self.device_zip:
+            full, tail = exr.zip_encode_torch(full, tail, self.compression)     # -> (records, map_offsets): what the files hold, on the device
         if self.bufs is None:
-            self.bufs = [(torch.empty(full.shape, dtype=torch.uint8).pin_memory(), torch.empty(tail.shape, dtype=torch.uint8).pin_memory())
+            self.bufs = [(torch.empty(full.shape, dtype=full.dtype).pin_memory(), torch.empty(tail.shape, dtype=tail.dtype).pin_memory())
                          for _ in range(self.n_buffers)]
         i = self.k % self.n_buffers; self.k += 1
         for f in self.busy[i]:
@@ -310,7 +317,10 @@ class MapWriter:
         def write(path, j):
             done.synchronize()
             tmp = path + ".part"
-            exr.write_exr_blocks(tmp, H, W, self.compression, hfull[j], htail[j], pool=chunks)
+            if self.device_zip:
+                exr.write_exr_records(tmp, H, W, self.compression, hfull[htail[j]:htail[j + 1]])
+            else:
+                exr.write_exr_blocks(tmp, H, W, self.compression, hfull[j], htail[j], pool=chunks)
             os.replace(tmp, path)
         writes = [self.pool.submit(write, f, j) for j, f in enumerate(files)]
         self.busy[i] = list(writes)
@@ -350,6 +360,8 @@ def main(argv=None):
     parser.add_argument("--spps_specular", type=int, nargs=N_ROUGHNESS, default=SPPS_SPECULAR)
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--compression", type=str, default="zip", choices=["none", "zips", "zip"])
+    parser.add_argument("--exr_encoder", type=str, default="host", choices=["host", "device"],
+                        help="where ZIP / ZIPS deflate runs: host (zlib on the writer threads) or device (GPU kernels); the pixels are the same")
     parser.add_argument("--overwrite", action="store_true", help="re-bake views whose 13 files already exist")
     parser.add_argument("--denoise", type=str, default="atrous", choices=["atrous", "none"],
                         help="atrous: guided a-trous filter in place of the reference's OptiX denoiser (:129, :198-200); none: raw Monte-Carlo maps")
@@ -393,7 +405,7 @@ def main(argv=None):
     if args.denoise == "atrous":
         from .utils.denoise import Denoiser
         denoiser = Denoiser(img_hw[::-1], device)          # denoiser = mitsuba.OptixDenoiser(img_hw[::-1])   (:81)
-    writer = MapWriter(device, img_hw, args.compression)
+    writer = MapWriter(device, img_hw, args.compression, encoder=args.exr_encoder)
     start_time = time.time()
     rays = 0
     for im_id in range(rank, len(views), world):           # views shard over ranks with no collective: one file set per view

@@ -21,6 +21,7 @@
 #include "iris_cache.h"
 #include "iris_denoise.h"
 #include "iris_ngp.h"
+#include "iris_deflate.h"
 
 using namespace iris;
 
@@ -1470,6 +1471,55 @@ extern "C" IRIS_API int iris_pt_compact(const uint8_t* keep, int64_t N, int n3, 
     const int blocks = (int)((N + kCompactItems - 1) / kCompactItems);
     hipLaunchKernelGGL(pt_compact_count_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
     hipLaunchKernelGGL(pt_compact_move_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
+// ======================================================================================================
+// OpenEXR ZIP / ZIPS scanline blocks deflated on the device (iris_deflate.h)
+// ======================================================================================================
+struct ZipLayout { int64_t n_segs, n_chunks, seg_data, seg_len, seg_adler, chunk_len, chunk_adler, chunk_off, total; int sf, st; };
+static bool zip_layout(int n_maps, int64_t n_full, int64_t block_bytes, int64_t tail_bytes, ZipLayout& z) {
+    if (n_maps <= 0 || n_full < 0 || tail_bytes < 0 || (n_full > 0 && block_bytes <= 0) || (n_full == 0 && tail_bytes == 0)) return false;
+    if (block_bytes >= ((int64_t)1 << 31) - 64 || tail_bytes >= ((int64_t)1 << 31) - 64) return false;
+    auto up = [](int64_t x) { return (x + 255) / 256 * 256; };
+    z.sf = n_full > 0 ? (int)((block_bytes + kZipSeg - 1) / kZipSeg) : 0;
+    z.st = tail_bytes > 0 ? (int)((tail_bytes + kZipSeg - 1) / kZipSeg) : 0;
+    z.n_segs = (int64_t)n_maps * (n_full * z.sf + z.st);
+    z.n_chunks = (int64_t)n_maps * (n_full + (tail_bytes > 0 ? 1 : 0));
+    if (z.n_segs >= ((int64_t)1 << 31)) return false;
+    z.seg_data = 0;
+    z.seg_len = up(z.seg_data + z.n_segs * kZipSegCap);
+    z.seg_adler = up(z.seg_len + z.n_segs * 4);
+    z.chunk_len = up(z.seg_adler + z.n_segs * 8);
+    z.chunk_adler = up(z.chunk_len + z.n_chunks * 4);
+    z.chunk_off = up(z.chunk_adler + z.n_chunks * 4);
+    z.total = up(z.chunk_off + z.n_chunks * 8);
+    return true;
+}
+extern "C" IRIS_API uint64_t iris_exr_zip_workspace_bytes(int n_maps, int64_t n_full, int64_t block_bytes, int64_t tail_bytes) {
+    ZipLayout z;
+    return zip_layout(n_maps, n_full, block_bytes, tail_bytes, z) ? (uint64_t)z.total : 0;
+}
+extern "C" IRIS_API int iris_exr_zip_encode(const uint8_t* full, const uint8_t* tail, int n_maps, int64_t n_full, int64_t block_bytes, int64_t tail_bytes,
+                                          int lines_per_block, uint8_t* records, int64_t* map_offsets, void* workspace, uint64_t workspace_bytes,
+                                          iris_stream_t stream) {
+    ZipLayout z;
+    if (!zip_layout(n_maps, n_full, block_bytes, tail_bytes, z) || lines_per_block <= 0 || !records || !map_offsets || !workspace ||
+        (n_full > 0 && !full) || (tail_bytes > 0 && !tail))
+        return fail(IRIS_ERR_ARG, "iris_exr_zip_encode: bad arguments");
+    if ((n_full + 1) * (int64_t)lines_per_block >= ((int64_t)1 << 31)) return fail(IRIS_ERR_ARG, "iris_exr_zip_encode: scanline index beyond int32");
+    if (workspace_bytes < (uint64_t)z.total) return fail(IRIS_ERR_ARG, "iris_exr_zip_encode: workspace smaller than iris_exr_zip_workspace_bytes()");
+    uint8_t* ws = (uint8_t*)workspace;
+    ZipArgs a{};
+    a.full = full; a.tail = tail; a.M = n_maps; a.lines = lines_per_block; a.sf = z.sf; a.st = z.st;
+    a.n_full = n_full; a.B = block_bytes; a.T = tail_bytes; a.records = records; a.map_offsets = map_offsets;
+    a.seg_data = ws + z.seg_data; a.seg_len = (uint32_t*)(ws + z.seg_len); a.seg_adler = (uint32_t*)(ws + z.seg_adler);
+    a.chunk_len = (uint32_t*)(ws + z.chunk_len); a.chunk_adler = (uint32_t*)(ws + z.chunk_adler); a.chunk_off = (int64_t*)(ws + z.chunk_off);
+    hipLaunchKernelGGL(zip_segment_kernel, dim3((unsigned)z.n_segs), dim3(kZipThreads), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(zip_chunk_kernel, dim3((unsigned)std::min<int64_t>((z.n_chunks + 255) / 256, 8192)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(zip_offsets_kernel, dim3(1), dim3(kZipScanThreads), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(zip_emit_kernel, dim3((unsigned)z.n_chunks), dim3(kZipThreads), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }

@@ -129,6 +129,8 @@ def main(argv=None):
     parser.add_argument("--batch_rays", type=int, default=BATCH_RAYS, help="paths per integrator call (the reference: 10240*128)")
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--compression", type=str, default="zip", choices=["none", "zips", "zip"])
+    parser.add_argument("--exr_encoder", type=str, default="host", choices=["host", "device"],
+                        help="where ZIP / ZIPS deflate runs: host (zlib) or device (GPU kernels); the pixels are the same, so --resume does not key on it")
     parser.add_argument("--overwrite", action="store_true", help="(accepted for symmetry with bake_shading; refining always overwrites, as the reference does)")
     parser.add_argument("--resume", action="store_true", help="skip the views a previous refine run with the same settings has completed (marked by a .refined sidecar)")
     parser.add_argument("--denoise", type=str, default="atrous", choices=["atrous", "none"])
@@ -171,7 +173,7 @@ def main(argv=None):
     if args.denoise == "atrous":
         from .utils.denoise import Denoiser
         denoiser = Denoiser(img_hw[::-1], device)
-    writer = MapWriter(device, img_hw, args.compression)
+    writer = MapWriter(device, img_hw, args.compression, encoder=args.exr_encoder)
     start_time = time.time()
     # The reference runs bake_shading and refine_shading on the SAME --output: the refined maps replace the bake's 13 files of every view in place
     # (refine_shading.py:126,172-173).  So a view's files existing says nothing about whether it has been refined: every view is rendered and

@@ -4,7 +4,8 @@ The reference writes its 13 maps per view with ``cv2.imwrite(path, img[:, :, [2,
 EXR files whose channels are named B, G, R and hold blue, green, red, and reads them back with
 ``cv2.imread(path, -1)[..., [2, 1, 0]]`` (utils/dataset/synthetic_ldr.py:58-64).  This module produces / consumes the same
 files without OpenCV: channels R, G, B (stored alphabetically B, G, R as the format requires), FLOAT pixels, NO_COMPRESSION or
-ZIP on write; NONE / ZIPS / ZIP, FLOAT / HALF on read.  Host-side I/O, not part of the hot path.
+ZIP on write; NONE / ZIPS / ZIP, FLOAT / HALF on read.  Deflate runs on the host (zlib) or, opt-in, on the GPU (zip_encode_torch: the kernels of
+csrc/iris_deflate.h); the files of both are standard OpenEXR ZIP / ZIPS files.
 """
 import struct
 import os
@@ -128,7 +129,7 @@ def scanline_blocks_torch(maps, compression):
     comp = {"none": _COMP_NONE, "zips": _COMP_ZIPS, "zip": _COMP_ZIP}[compression]
     M, H, W, _ = maps.shape
     lines = _LINES[comp]
-    planes = maps.to(torch.float32).flip(-1).permute(0, 1, 3, 2).contiguous().view(torch.uint8).reshape(M, H, 3 * W * 4)    # (M, H, row bytes)
+    planes = maps.to(torch.float32).flip(-1).permute(0, 1, 3, 2).contiguous().reshape(M, H, 3 * W).view(torch.uint8)    # (M, H, row bytes)
 
     def blocks(rows, n):                                            # (M, n * lines', row_bytes) -> (M, n, lines' * row_bytes) in file byte order
         b = rows.reshape(M, n, -1)
@@ -160,6 +161,63 @@ def write_exr_blocks(path, H, W, compression, full, tail, pool=None):
     idx = range(len(parts))
     chunks = list(pool.map(encode, idx)) if (pool is not None and comp != _COMP_NONE) else [encode(i) for i in idx]
     _write_chunks(path, hdr, chunks)
+
+
+def zip_records_capacity(full, tail):
+    """bytes zip_encode_torch reserves for the records of all maps: every chunk at its raw size plus its 8-byte (y, size) prefix"""
+    M, n_full, B = full.shape
+    T = tail.shape[1]
+    return M * (n_full * (B + 8) + (T + 8 if T else 0))
+
+
+def zip_encode_torch(full, tail, compression):
+    """Device half of the writer, deflate included: (full, tail) of scanline_blocks_torch(maps, compression) for "zip" / "zips" -> (records, map_offsets),
+    device tensors: records (uint8) holds, map by map, every chunk record as the file stores it (int32 y, int32 size, data: a zlib stream of the predicted
+    block when that is shorter than the block, else the raw block -- OpenEXR's rule) and map_offsets (int64, M + 1) where each map's records start, then
+    their end.  Enqueued on the current stream; nothing is read back.  records is sized for the worst case (zip_records_capacity)."""
+    import torch
+    from .. import _lib as L
+    lines = {"zips": _LINES[_COMP_ZIPS], "zip": _LINES[_COMP_ZIP]}[compression]
+    full = L.require_gpu(full, torch.uint8, "full")
+    tail = L.require_gpu(tail, torch.uint8, "tail")
+    if full.dim() != 3 or tail.dim() != 2 or tail.shape[0] != full.shape[0]:
+        raise L.IrisError("zip_encode_torch: expected full (M, n_full, block_bytes) and tail (M, tail_bytes)")
+    M, n_full, B = full.shape
+    T = tail.shape[1]
+    ws_bytes = int(L.lib().iris_exr_zip_workspace_bytes(M, n_full, B, T))
+    if ws_bytes == 0:
+        raise L.IrisError(f"zip_encode_torch: unsupported sizes (M={M}, n_full={n_full}, block_bytes={B}, tail_bytes={T})")
+    dev = full.device
+    records = torch.empty(zip_records_capacity(full, tail), dtype=torch.uint8, device=dev)
+    offsets = torch.empty(M + 1, dtype=torch.int64, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().iris_exr_zip_encode(L.ptr(full) if n_full else None, L.ptr(tail) if T else None, M, n_full, B, T, lines, L.ptr(records),
+                                            L.ptr(offsets), L.ptr(ws), ws_bytes, L.stream()))
+    return records, offsets
+
+
+def write_exr_records(path, H, W, compression, records):
+    """records: the chunk records of ONE map, back to back, as the file stores them (zip_encode_torch's records[map_offsets[m]:map_offsets[m + 1]], or
+    any (y, size, data) records of this size) -> the file: header, offset table and records in one write."""
+    comp = {"none": _COMP_NONE, "zips": _COMP_ZIPS, "zip": _COMP_ZIP}[compression]
+    hdr = _header(H, W, comp)
+    n_chunks = (H + _LINES[comp] - 1) // _LINES[comp]
+    buf = memoryview(records).cast("B")
+    offs, o = [], 0
+    for _ in range(n_chunks):
+        if o + 8 > len(buf):
+            break
+        offs.append(o)
+        (size,) = struct.unpack_from("<i", buf, o + 4)
+        o += 8 + size
+    if len(offs) != n_chunks or o != len(buf):
+        raise ValueError(f"write_exr_records: {len(buf)} bytes of records, {o} in {n_chunks} chunks")
+    base = len(hdr) + 8 * n_chunks
+    table = struct.pack("<%dQ" % n_chunks, *[base + x for x in offs])
+    with open(path, "wb") as fh:
+        fh.write(hdr + table)
+        fh.write(buf)
 
 
 def read_exr_header(path):

@@ -4,7 +4,9 @@ to disk in the reference's file formats and ScanNet++ layout (data/<scene>/scans
 sequence of 1080p views -- mesh load + BVH build, per view rays / primary hits / 7-lobe bake / denoise, 13 EXR files per view.
 bench.py times the path with inputs resident in HBM; this is the number a user of the CLI sees.  One JSON line per configuration.
 
-    python tools/bench_cli.py [--views 8] [--tris 1000000] [--out /tmp/iris_cli]
+    python tools/bench_cli.py [--views 8] [--tris 1000000] [--out /tmp/iris_cli] [--configs zip:atrous:host,zip:atrous:device,none:atrous] [--repeat 2]
+
+A configuration is compression:denoise[:exr_encoder] (encoder host by default); --repeat runs the whole list that many times, alternating.
 """
 import argparse
 import json
@@ -32,6 +34,26 @@ def write_ply(path, v, f):
         fh.write(rec.tobytes())
 
 
+def usable_cpus():
+    """what this process may actually run on: its affinity mask and the cgroup's CPU quota (cpu.max; bench.py's cpu_baseline reads the same)"""
+    try:
+        aff = len(os.sched_getaffinity(0))
+    except Exception:     # noqa
+        aff = None
+    cpu_max, quota = None, None
+    for f in ("/sys/fs/cgroup/cpu.max", "/sys/fs/cgroup/cpu/cpu.cfs_quota_us"):
+        try:
+            cpu_max = open(f).read().strip(); break
+        except Exception:     # noqa
+            pass
+    try:
+        q, per = cpu_max.split()[:2]
+        quota = None if q == "max" else round(float(q) / float(per), 2)
+    except Exception:     # noqa
+        pass
+    return {"sched_getaffinity": aff, "cgroup_cpu_max": cpu_max, "cgroup_cpus": quota}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--views", type=int, default=8)
@@ -41,6 +63,7 @@ def main():
     ap.add_argument("--slf-res", type=int, default=256)
     ap.add_argument("--out", type=str, default="/tmp/iris_cli")
     ap.add_argument("--configs", type=str, default="zip:atrous,none:atrous,none:none")
+    ap.add_argument("--repeat", type=int, default=1, help="passes over --configs (alternated: A B C A B C ...)")
     args = ap.parse_args()
     from tools import synth
     shutil.rmtree(args.out, ignore_errors=True)
@@ -74,12 +97,12 @@ def main():
               open(os.path.join(psdf_dir, "transforms_all.json"), "w"))
     print("# dataset written in %.1f s: %d triangles, %d views of %dx%d" % (time.time() - t0, len(f), args.views, W, H), file=sys.stderr)
 
-    for cfg in args.configs.split(","):
-        comp, den = cfg.split(":")
+    for cfg in args.configs.split(",") * max(1, args.repeat):
+        comp, den, enc = (cfg.split(":") + ["host"])[:3]
         out_dir = os.path.join(args.out, "shading_" + cfg.replace(":", "_"))
         # scripts/scannetpp/bathroom2/train.sh:49-54's argument list (+ the two additions under test)
         cmd = [sys.executable, "-m", "iris_amd.bake_shading", "--dataset_root", args.out, "--scene", SCENE, "--dataset", "scannetpp", "--res_scale", "1.0",
-               "--slf_path", slf_path, "--emitter_path", emi_path, "--output", out_dir, "--compression", comp, "--denoise", den]
+               "--slf_path", slf_path, "--emitter_path", emi_path, "--output", out_dir, "--compression", comp, "--denoise", den, "--exr_encoder", enc]
         t = time.time()
         r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True)
         dt = time.time() - t
@@ -91,7 +114,7 @@ def main():
         size = sum(os.path.getsize(os.path.join(d, x)) for d, _, fs in os.walk(out_dir) for x in fs)
         from iris_amd import bake_shading as bs
         rays = args.views * H * W * (bs.SPP_DIFFUSE + sum(bs.SPPS_SPECULAR))     # upper bound: every pixel valid
-        print(json.dumps({"config": {"compression": comp, "denoise": den, "views": args.views, "image": [W, H], "triangles": int(len(f)), "host_cpus": os.cpu_count(), "command": "python -m iris_amd.bake_shading --dataset_root R --scene S --dataset scannetpp --res_scale 1.0 --slf_path ... --emitter_path ... --output ... (scripts/scannetpp/bathroom2/train.sh:49-54)"},
+        print(json.dumps({"config": {"compression": comp, "denoise": den, "views": args.views, "image": [W, H], "triangles": int(len(f)), "exr_encoder": enc, "host_cpus": os.cpu_count(), "usable_cpus": usable_cpus(), "command": "python -m iris_amd.bake_shading --dataset_root R --scene S --dataset scannetpp --res_scale 1.0 --slf_path ... --emitter_path ... --output ... (scripts/scannetpp/bathroom2/train.sh:49-54)"},
                           "wall_s": round(dt, 2), "s_per_view_incl_startup": round(dt / args.views, 3), "cli_report": inner[-1] if inner else None,
                           "files": n_files, "bytes_written": size, "upper_bound_Mrays_per_s": round(rays / dt / 1e6, 1)}), flush=True)
         shutil.rmtree(out_dir, ignore_errors=True)
