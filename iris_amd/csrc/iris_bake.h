@@ -25,21 +25,12 @@ struct BakeArgs {
     // tile kernels only
     uint32_t* stack_ovf;        // gridDim.x * (kStackCapacity - LDS depth) * 256 dwords: traversal-stack entries beyond the LDS part
     float4* scratch;            // gridDim.x * kTileRays * (SPEC ? 2 : 1) float4: per-ray slots (sampled direction -> hit; GGX weights)
-#if IRIS_PARK
-    iris_u4v* park;             // gridDim.x * 4 waves * kParkCap records of 80 B (straggler parking, iris_trace.h)
-#endif
     unsigned int* tile_counter; // 8 counters (one per XCD, claim_tile), zeroed before the launch
     int tile_px;                // pixels per tile (tile_px * spp <= kTileRays)
 };
 
 #ifndef IRIS_TILE_RAYS
 #define IRIS_TILE_RAYS 5120
-#endif
-#ifndef IRIS_EXP_NOSAMPLE
-#define IRIS_EXP_NOSAMPLE 0
-#endif
-#ifndef IRIS_EXP_NOSHADE
-#define IRIS_EXP_NOSHADE 0
 #endif
 constexpr int kTileRays = IRIS_TILE_RAYS;   // capacity of the LDS ray list (10 KiB) = largest spp of the tile kernels; the host aims at tiles of this size
 
@@ -207,9 +198,6 @@ __global__ __launch_bounds__(kBlock) void bake_kernel(BakeArgs a) {
 #ifndef IRIS_TILE_WAVES          // resident waves per SIMD the tile kernels are compiled for (= workgroups per CU): 7 x 20 488 B of LDS, 72 VGPRs.
 #define IRIS_TILE_WAVES 7        // Measured: 6 waves (80 VGPRs) 7.11, 7 waves 7.24, 8 waves (64 VGPRs, 9-entry stacks) 7.17 Grays/s  (LDS now 7 x 22 536 B: 12-entry stacks)
 #endif
-#ifndef IRIS_RESOLVE_AT_RETIRE       // (A/B: 0 = a retiring ray parks (u, v, leaf slot) and the shading pass reads the triangle's record)
-#define IRIS_RESOLVE_AT_RETIRE 1
-#endif
 #ifndef IRIS_TILE_STACK          // per-lane LDS stack entries of the tile kernels; deeper entries go to the workgroup's slab in the workspace
 #define IRIS_TILE_STACK 12       // (a.stack_ovf), NOT to private scratch: without a scratch-resident stack array the kernel fits 6 (7) waves/SIMD (measured +6.5 %)
 #endif
@@ -238,9 +226,7 @@ __device__ __forceinline__ void tile_body(const BakeArgs& a, int64_t p0, int np,
     const int sub = lane / lpp, sl = lane - sub * lpp;
     const float inv_spp = 1.0f / (float)spp;
     const int nr = np * spp;
-#if IRIS_RESOLVE_AT_RETIRE
     const bool resolve = !a.em.emit_ord && !a.tri_next;      // fused records, and nobody asks for the per-sample triangle ids
-#endif
 
     // r / spp for a tile-local ray index without the 25-instruction integer division: exact for r * spp < 2^32 (r < kTileRays, spp <= kTileRays)
     const uint32_t spp_m = spp > 1 ? (uint32_t)(0x100000000ull / (uint64_t)(uint32_t)spp) + 1u : 0u;
@@ -263,7 +249,7 @@ __device__ __forceinline__ void tile_body(const BakeArgs& a, int64_t p0, int np,
     }
 
     // phases A-C (iris_tile.h): sample every ray (uniforms -> direction + GGX weights) and park it; sort by direction; trace
-    tile_sort_trace<LAYOUT, COUNT, kTileRays, TILE_STACK, true, (IRIS_PARK != 0)>(
+    tile_sort_trace<LAYOUT, COUNT, kTileRays, TILE_STACK, true>(
         a.sc, nr, s_sorted, s_stack, s_chunk, ovf, ts,
         [&](int r) -> uint32_t {
             const int pl = div_spp(r), s = r - pl * spp;
@@ -274,13 +260,7 @@ __device__ __forceinline__ void tile_body(const BakeArgs& a, int64_t p0, int np,
             if (frames) { const float* f = s_frames + pl * 6; t = mk3(f[0], f[1], f[2]); b = mk3(f[3], f[4], f[5]); }
             else normal_space(n, t, b);
             f3 wi; float g0, g1;
-#if IRIS_EXP_NOSAMPLE
-            // (UPPER-BOUND EXPERIMENT, wrong results: what does the sampling arithmetic cost?  A direction from three multiplies instead of Philox + the samplers; never shipped)
-            { const float fs = (float)(s & 15) * 0.0625f - 0.47f, ft = (float)(s >> 4) * 0.125f - 0.45f;
-              wi = t_normalize(mk3(n.x + fs * t.x + ft * b.x, n.y + fs * t.y + ft * b.y, n.z + fs * t.z + ft * b.z)); g0 = 1.f; g1 = 0.5f; (void)base; (void)w; }
-#else
             sample_lobe<SPEC>(a, p, s, n, w, t, b, base, wi, g0, g1);
-#endif
             res[r] = make_float4(wi.x, wi.y, wi.z, 0.f);
             if (SPEC) res_g[r] = make_float2(g1, g0);
             return dir_bin(wi);
@@ -294,7 +274,6 @@ __device__ __forceinline__ void tile_body(const BakeArgs& a, int64_t p0, int np,
         // position + RayEpsilon*wi (bake_shading.py:117, :180)
         [&](f3& o, f3& d) { o = mk3(o.x + kRayEps * d.x, o.y + kRayEps * d.y, o.z + kRayEps * d.z); },
         [&](int r, const Hit& h) {
-#if IRIS_RESOLVE_AT_RETIRE
             if (resolve) {
                 // the hit is resolved while its record is still near: position + emitter ordinal instead of (u, v, leaf slot); w = -2: a miss
                 float4 q = make_float4(0.f, 0.f, 0.f, __int_as_float(-2));
@@ -307,12 +286,8 @@ __device__ __forceinline__ void tile_body(const BakeArgs& a, int64_t p0, int np,
                 }
                 res[r] = q;
             } else
-#endif
             res[r] = make_float4(h.u, h.v, __int_as_float(h.slot), 0.f);
             if (COUNT) n_rays++; }   // every ray retires once
-#if IRIS_PARK
-        , a.park + (size_t)blockIdx.x * (kBlock / 64) * kParkCap * kParkWords4
-#endif
         );
 
     // ---- phase D: shade every sample (hit -> p_next -> eval_emitter(p_next, wi, tri_next, ones, trace_roughness=0.0),
@@ -324,7 +299,6 @@ __device__ __forceinline__ void tile_body(const BakeArgs& a, int64_t p0, int np,
         const int pl = g * ppw + sub;
         const bool pvalid = pl < np;
         float a0x = 0.f, a0y = 0.f, a0z = 0.f, a1x = 0.f, a1y = 0.f, a1z = 0.f;
-#if IRIS_RESOLVE_AT_RETIRE
         // Resolved slots (position + emitter ordinal): what is left of eval_emitter is a chain of three dependent loads per sample -- slot -> voxel index -> radiance row --
         // with four live registers per sample in flight, so TWO rounds of a pixel run side by side, stage by stage (the sums take them in the order of the plain loop).
         if (resolve) {
@@ -358,16 +332,10 @@ __device__ __forceinline__ void tile_body(const BakeArgs& a, int64_t p0, int np,
                 }
             }
         } else
-#endif
         for (int rr = 0; rr < rounds; ++rr) {
             const int s = rr * 64 + sl;
             if (pvalid && s < spp) {
                 const float4 qa = res[pl * spp + s];
-#if IRIS_EXP_NOSHADE
-                // (UPPER-BOUND EXPERIMENT, wrong results: what does the shading pass cost?  The hit record is summed as it is; never shipped)
-                a0x += qa.x; a0y += qa.y; a0z += qa.z; if (SPEC) { a1x += qa.x; a1y += qa.y; a1z += qa.z; }
-                continue;
-#endif
                 Hit h; h.u = qa.x; h.v = qa.y; h.slot = __float_as_int(qa.z); h.t = 0.f; h.id = 0;
                 f3 pn = mk3(0.f, 0.f, 0.f);
                 int64_t tri = -1;

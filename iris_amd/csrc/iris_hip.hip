@@ -115,7 +115,7 @@ struct iris_emitter {
 // (iris_trace.h trace_q8_joint: node and triangle loads of an iteration issued together): they do not fill the chip, and what they wait for is their longest wave's
 // dependent round trips.  iris_debug_set("joint_max_rays") overrides (0 = never).  Results do not depend on it.
 constexpr long long kJointMaxRays = 1 << 20;
-static bool joint_launch(int64_t n_rays) { return n_rays <= (g_opt_joint_max_rays >= 0 ? g_opt_joint_max_rays : kJointMaxRays) && !IRIS_NODE80; }
+static bool joint_launch(int64_t n_rays) { return n_rays <= (g_opt_joint_max_rays >= 0 ? g_opt_joint_max_rays : kJointMaxRays); }
 
 static int grid_for(int64_t n, int block, int max_blocks) {
     int64_t g = (n + block - 1) / block;
@@ -193,10 +193,8 @@ extern "C" IRIS_API int iris_debug_scene_create(const float* verts, int64_t nv, 
             }
             uint32_t ebytes = 0;
             uint8_t q[6][4];   // planes lo_x lo_y lo_z hi_x hi_y hi_z
-            double ext_max = 0.0;
-            for (int k = 0; k < 3; ++k) ext_max = std::max(ext_max, (double)hi3[k] - (double)org[k]);
             for (int k = 0; k < 3; ++k) {
-                const double ext = IRIS_NODE80 ? ext_max : (double)hi3[k] - (double)org[k];     // (80-B nodes: ONE plane scale per node, that of the longest axis)
+                const double ext = (double)hi3[k] - (double)org[k];
                 int e = -126;
                 if (ext > 0) e = std::max(-126, (int)std::ceil(std::log2(ext / 255.0)));
                 while (std::ldexp(255.0, e) < ext) ++e;                       // 255 * 2^e must cover the extent
@@ -226,22 +224,6 @@ extern "C" IRIS_API int iris_debug_scene_create(const float* verts, int64_t nv, 
             for (int o = 0; o < 8; ++o) {
                 float* po = nodes.data() + ((size_t)o * nn + i) * node_floats;
                 po[0] = org[0]; po[1] = org[1]; po[2] = org[2];
-#if IRIS_NODE80
-                // {origin.xyz, scale} {ref[4]} {x planes of children 0..3} {y planes} {z planes}: a plane word = near byte | far byte << 16 (two f16 subnormals)
-                po[3] = std::ldexp(1.0f, (int)(ebytes & 0xffu) - 127 + 24);
-                for (int j = 0; j < 4; ++j) {
-                    const int sl = j < w.n ? (int)w.order[o][j] : j;
-                    const uint32_t ref = child_ref(w, sl);
-                    std::memcpy(&po[4 + j], &ref, 4);
-                    for (int k = 0; k < 3; ++k) {
-                        const bool neg = (o >> k) & 1;
-                        const uint32_t near_q = neg ? q[3 + k][sl] : q[k][sl], far_q = neg ? q[k][sl] : q[3 + k][sl];
-                        const uint32_t word = near_q | (far_q << 16);
-                        std::memcpy(&po[8 + 4 * k + j], &word, 4);
-                    }
-                }
-                continue;
-#endif
                 for (int k = 0; k < 3; ++k) po[3 + k] = std::ldexp(1.0f, (int)((ebytes >> (8 * k)) & 0xffu) - 127 + 24);
                 uint8_t qo[6][4];
                 for (int j = 0; j < 4; ++j) {
@@ -1008,9 +990,6 @@ static uint64_t stack_ovf_bytes() {
     return (uint64_t)std::max(bake_grid_blocks(), view_grid_blocks()) * (kStackCapacity - IRIS_TILE_STACK) * kBlock * sizeof(uint32_t);
 }
 
-static uint64_t park_bytes() {      // IRIS_PARK: wave-private pools of parked rays (iris_trace.h)
-    return IRIS_PARK ? (uint64_t)std::max(bake_grid_blocks(), view_grid_blocks()) * (kBlock / 64) * kParkCap * kParkWords4 * 16 : 0;
-}
 extern "C" IRIS_API int iris_bake_tile_max_spp(void) { return kTileRays; }
 extern "C" IRIS_API uint64_t iris_bake_workspace_bytes(int64_t P, int spp, int specular) {
     if (spp < 1 || spp > kTileRays || P < 0) return 0;  // v1 kernel only
@@ -1018,7 +997,7 @@ extern "C" IRIS_API uint64_t iris_bake_workspace_bytes(int64_t P, int spp, int s
     // (packing the pixel tensors into 48-B records was measured 7 % SLOWER than reading pos/nrm/wo directly: not done)
     // + [blocks x (96 - LDS depth) x 256 dwords: traversal-stack entries beyond the LDS part]   (specular sizing also serves iris_bake_view)
     const uint64_t blocks = (uint64_t)std::max(bake_grid_blocks(), view_grid_blocks());
-    return 256 + blocks * kTileRays * (specular ? 2 : 1) * sizeof(float4) + park_bytes() + stack_ovf_bytes();
+    return 256 + blocks * kTileRays * (specular ? 2 : 1) * sizeof(float4) + stack_ovf_bytes();
 }
 
 static const float4* fused_tris(const iris_scene* sc, const iris_emitter* em, hipStream_t st);
@@ -1054,9 +1033,6 @@ static int bake_launch(bool spec, const iris_scene* sc, const iris_emitter* em, 
         a.tile_counter = (unsigned int*)workspace;
         a.scratch = (float4*)((char*)workspace + 256);
         a.stack_ovf = (uint32_t*)((char*)workspace + need - stack_ovf_bytes());
-#if IRIS_PARK
-        a.park = (iris_u4v*)((char*)workspace + need - stack_ovf_bytes() - park_bytes());
-#endif
         HIP_TRY(hipMemsetAsync(workspace, 0, 256, st));
         if (const float4* ft = fused_tris(sc, em, st)) { a.sc.tris = ft; a.em.emit_ord = nullptr; }      // (tile kernels only: their shading pass reads the ordinal from the record)
         const int64_t n_tiles = (P + tile_px - 1) / tile_px;
@@ -1142,9 +1118,6 @@ extern "C" IRIS_API int iris_bake_view(const iris_scene* sc, const iris_emitter*
     v.base.tile_counter = (unsigned int*)workspace;
     v.base.scratch = (float4*)((char*)workspace + 256);
     v.base.stack_ovf = (uint32_t*)((char*)workspace + need - stack_ovf_bytes());
-#if IRIS_PARK
-    v.base.park = (iris_u4v*)((char*)workspace + need - stack_ovf_bytes() - park_bytes());
-#endif
     v.n_lobes = n_lobes;
     const int blocks = view_grid_blocks();
     long long t = 0;

@@ -8,22 +8,9 @@ namespace iris {
 constexpr int kBlock = 256;          // threads per workgroup for every traversal kernel
 constexpr int kStackLds = 24;        // per-lane stack entries kept in LDS (24 KiB per workgroup)
 constexpr int kStackSpill = 72;      // rarely-touched overflow in scratch (correctness only)
-// Q8 node record.  IRIS_NODE80 = 0: 64 B, 8-bit planes four to a word (a visit isolates near / far byte pairs with 12 v_perm_b32).
-// IRIS_NODE80 = 1 (round 5): 80 B = {origin.xyz, scale} {ref[4]} {12 plane words}: every (axis, child) has its OWN word, near byte in the low half, far byte in the
-// high half, each zero-extended to 16 bits -- i.e. ALREADY the pair of f16 subnormals v_fma_mix_f32 reads: no v_perm_b32 in a visit (12 of its 91 vector
-// instructions, all of the 4-cycle class), five 16-B loads instead of four, ONE plane scale per node (the largest axis extent; 80 B = five loads exactly) --
-// tools/bvh_eval: +0.8 % node visits, +1.6 % triangle tests from the coarser planes on a node's short axes.
-#ifndef IRIS_NODE80
-#define IRIS_NODE80 0
-#endif
-#ifndef IRIS_SLAB_CVT
-#define IRIS_SLAB_CVT 0
-#endif
-#ifndef IRIS_EXP_NODRAIN
-#define IRIS_EXP_NODRAIN 0
-#endif
-constexpr uint32_t kNodeBytes = IRIS_NODE80 ? 80u : 64u;
-__device__ __forceinline__ uint32_t node_offset(uint32_t cur) { return IRIS_NODE80 ? cur * 80u : cur << 6; }
+// Q8 node record: 64 B, 8-bit planes four to a word (a visit isolates near / far byte pairs with 12 v_perm_b32).
+constexpr uint32_t kNodeBytes = 64u;
+__device__ __forceinline__ uint32_t node_offset(uint32_t cur) { return cur << 6; }
 constexpr uint32_t kLeafBit = 0x80000000u;
 constexpr uint32_t kEmptyRef = 0xFFFFFFFFu;
 
@@ -97,9 +84,6 @@ struct Stack {
     }
 };
 
-#ifndef IRIS_TRI_FLAT
-#define IRIS_TRI_FLAT 1
-#endif
 // Watertight ray / triangle test (Woop, Benthin, Wald 2013, "Watertight Ray/Triangle Intersection", JCGT 2(1), section 3): the ray is
 // made the z axis of a sheared, axis-permuted space -- kz = the axis of d's largest magnitude, (kx, ky) the two after it, S = (d[kx], d[ky], 1) / d[kz]
 // --, every vertex is translated by the origin and sheared by the same function of (vertex, ray) in whichever triangle it appears, and the
@@ -153,18 +137,12 @@ __device__ __forceinline__ void tri_eval(const iris_f4v X, const iris_f4v Y, con
     const float u = V * inv_det, v = W * inv_det;
     // no two edge functions of strictly opposite sign; det == 0 gives t = NaN or +-inf: a NaN fails every comparison, and +inf can only tie with the
     // initial h.t, whose h.id = INT_MIN no index is smaller than
-#if IRIS_TRI_FLAT
     // (bitwise, not short-circuit: as `&&` / `||` hipcc turns the acceptance test into four divergent branches with their execution-mask bookkeeping -- ~25 scalar
     //  instructions per triangle test; the same comparisons combined as masks are five compares and four scalar mask operations)
     const bool mixed = (int)(fminf(fminf(U, V), W) < 0.f) & (int)(fmaxf(fmaxf(U, V), W) > 0.f);
     const bool ok = (int)!mixed & (int)(t >= 0.f);
     const bool closer = (int)(t < h.t) | ((int)(t == h.t) & (int)(id < h.id));       // closest hit = lexicographic min of (t, original index)
     if ((int)ok & (int)closer) { h.t = t; h.u = u; h.v = v; h.slot = slot; h.id = id; }
-#else
-    const bool ok = !(fminf(fminf(U, V), W) < 0.f && fmaxf(fmaxf(U, V), W) > 0.f) && t >= 0.f;
-    // closest hit = lexicographic min of (t, original index)
-    if (ok && (t < h.t || (t == h.t && id < h.id))) { h.t = t; h.u = u; h.v = v; h.slot = slot; h.id = id; }
-#endif
 }
 
 __device__ __forceinline__ void tri_test(const SceneDev& sc, int slot, const RayXf& x, Hit& h) {
@@ -184,29 +162,10 @@ __device__ __forceinline__ void tri_test(const SceneDev& sc, int slot, const Ray
 // (Loop control: `__popcll(m) >= k` stays a 64-bit comparison, which the scalar ALU cannot do, so hipcc runs it on the vector ALU -- v_cmp_lt_u64 on scalar
 //  operands, in front of every node and leaf step.  Counting the two mask halves with 32-bit scalar instructions instead was measured SLOWER, -0.8 %: the longer
 //  scalar dependency chain in front of the step costs more than the vector issue slot, EXPERIMENTS.md round 4.)
-#ifndef IRIS_POPC_ASM
-#define IRIS_POPC_ASM 1
-#endif
-#ifndef IRIS_IDLE_GATE
-#define IRIS_IDLE_GATE 1
-#endif
-#ifndef IRIS_LOOP_NEST
-#define IRIS_LOOP_NEST 1
-#endif
-#ifndef IRIS_FAST_PUSH
-#define IRIS_FAST_PUSH 1
-#endif
-#ifndef IRIS_FAST_POP
-#define IRIS_FAST_POP 1
-#endif
 __device__ __forceinline__ int popc_mask(unsigned long long m) {
-#if IRIS_POPC_ASM
     int n;
     asm("s_bcnt1_i32_b64 %0, %1" : "=s"(n) : "s"(m) : "scc");     // ONE scalar instruction and a 32-bit result: the comparison that follows stays on the scalar ALU
     return n;
-#else
-    return (int)__popcll(m);
-#endif
 }
 __device__ __forceinline__ bool first_active_lane() {
     unsigned long long m = __ballot(1);
@@ -247,7 +206,6 @@ constexpr int kPhaseMin = 12;      // (round 3 sweep at 4096-ray tiles: 10: 7.47
 // own box (4 dwordx4 per visit): plane = origin + q * 2^e per axis (the node stores 2^(e+24) as a float, see node_step), lo rounded down /
 // hi rounded up, so the decoded box contains the f32 box.
 constexpr int kLayoutF32 = 1, kLayoutQ8 = 3;
-__device__ __forceinline__ float ubyte(uint32_t v, int c) { return (float)((v >> (8 * c)) & 0xffu); }
 
 // Per-lane traversal state shared by the two drivers below (kept in registers; the struct is scalar-replaced).
 struct RayState {
@@ -284,24 +242,6 @@ __device__ __forceinline__ void node_step(const SceneDev& sc, RayState& r, STACK
         // by the ray's signs and sorts nothing.  32-bit byte offset from the (scalar) table base: one shift-add per visit.
         glb_u4v* n = (glb_u4v*)(reinterpret_cast<const char*>(sc.nodes) + (size_t)(uint32_t)(node_offset(r.cur) + r.oct_base));
         typedef _Float16 iris_h2 __attribute__((ext_vector_type(2)));
-#if IRIS_NODE80
-        iris_u4v hd = n[0], rf = n[1], px = n[2], py = n[3], pz = n[4];            // {origin.xyz, scale} {ref[4]} {x planes of children 0..3} {y planes} {z planes}
-        // (all five 16-B loads HERE: left alone hipcc narrows the plane loads to single words and sinks those of children 1..3 behind the test of child 0 --
-        //  dependent round trips inside a visit)
-        asm volatile("" : "+v"(px), "+v"(py), "+v"(pz));
-        r0 = rf.x; r1 = rf.y; r2 = rf.z; r3 = rf.w;
-        const float sc24 = __uint_as_float(hd.w);                                   // 2^(e+24), one per node
-        const float ax = sc24 * ix, ay = sc24 * iy, az = sc24 * iz;
-        const float bx = fmaf(__uint_as_float(hd.x), ix, nx), by = fmaf(__uint_as_float(hd.y), iy, ny), bz = fmaf(__uint_as_float(hd.z), iz, nz);
-        // a plane word IS the (near, far) pair of f16 subnormals q * 2^-24: v_fma_mix_f32 reads its halves directly
-#define IRIS_SLABQ(D, C)                                                                                                          \
-    {                                                                                                                             \
-        const iris_h2 hx = __builtin_bit_cast(iris_h2, (uint32_t)px[C]), hy = __builtin_bit_cast(iris_h2, (uint32_t)py[C]), hz = __builtin_bit_cast(iris_h2, (uint32_t)pz[C]);   /* (a prvalue: __builtin_bit_cast of the vector ELEMENT lvalue reads element 0 whatever the index -- hipcc 7.2) */ \
-        float tn = fmaxf(fmaxf(fmaf((float)hx.x, ax, bx), fmaf((float)hy.x, ay, by)), fmaxf(fmaf((float)hz.x, az, bz), 0.f));      \
-        float tf = fminf(fminf(fmaf((float)hx.y, ax, bx), fmaf((float)hy.y, ay, by)), fminf(fmaf((float)hz.y, az, bz), r.h.t));    \
-        D = tf - tn;                                                                                                              \
-    }
-#else
         const iris_u4v hd = n[0], q1 = n[1], q2 = n[2], rf = n[3];
         r0 = rf.x; r1 = rf.y; r2 = rf.z; r3 = rf.w;
         // per-axis: t(q) = q * 2^e * idir + (origin * idir - o * idir); the node stores 2^(e+24) as a float (see below)
@@ -312,19 +252,6 @@ __device__ __forceinline__ void node_step(const SceneDev& sc, RayState& r, STACK
         // child into the two halves of a register and v_fma_mix_f32 reads an f16 operand directly: 1 + 2 instructions per axis and child
         // instead of 2 conversions + 2 FMAs.  The node stores scale * 2^24, so q*2^-24 * (scale*2^24*idir) + b is the same real number,
         // rounded once by the FMA.
-#if IRIS_SLAB_CVT
-        // (round 5 experiment) the plane bytes converted by v_cvt_f32_ubyteN and fed to PLAIN v_fma_f32: 12 instructions per child instead of 9, but of two classes that
-        // issue TOGETHER (tools/microbench pair: an integer-pipe instruction followed by a float-pipe one costs ~5 cycles the pair; v_fma_mix_f32 pairs with nothing, 4.4
-        // cycles each).  q * (scale * idir) + b is the same real number as (q * 2^-24) * (scale * 2^24 * idir) + b: the same t, bit for bit.
-        const float ax1 = ax * 0x1p-24f, ay1 = ay * 0x1p-24f, az1 = az * 0x1p-24f;
-#define IRIS_SLABQ(D, C)                                                                                                          \
-    {                                                                                                                             \
-        float tn = fmaxf(fmaxf(fmaf(ubyte(nxq, C), ax1, bx), fmaf(ubyte(nyq, C), ay1, by)), fmaxf(fmaf(ubyte(nzq, C), az1, bz), 0.f));      \
-        float tf = fminf(fminf(fmaf(ubyte(fxq, C), ax1, bx), fmaf(ubyte(fyq, C), ay1, by)), fminf(fmaf(ubyte(fzq, C), az1, bz), r.h.t));    \
-        D = tf - tn;                                                                                                              \
-    }
-#define IRIS_PLANES(NQ, FQ, C) 0
-#else
 #define IRIS_PLANES(NQ, FQ, C) __builtin_bit_cast(iris_h2, __builtin_amdgcn_perm(NQ, FQ, 0x0c000c04u | ((uint32_t)(C) << 16) | (uint32_t)(C)))
 #define IRIS_SLABQ(D, C)                                                                                                          \
     {                                                                                                                             \
@@ -333,14 +260,10 @@ __device__ __forceinline__ void node_step(const SceneDev& sc, RayState& r, STACK
         float tf = fminf(fminf(fmaf((float)hx.y, ax, bx), fmaf((float)hy.y, ay, by)), fminf(fmaf((float)hz.y, az, bz), r.h.t));    \
         D = tf - tn;                     /* sign clear: the child is hit (tn <= tf).  tn = tf gives +0; a NaN (inf - inf: tn = tf = inf) with a clear sign  */ \
     }                                    /* would only cost a wasted visit                                                                                */
-#endif
-#endif
         float d0, d1, d2, d3;
         IRIS_SLABQ(d0, 0) IRIS_SLABQ(d1, 1) IRIS_SLABQ(d2, 2) IRIS_SLABQ(d3, 3)
 #undef IRIS_SLABQ
-#if !IRIS_NODE80
 #undef IRIS_PLANES
-#endif
         // Slots are in visiting order: the first child hit is next, the others wait on the stack, the farthest at the bottom.  The conditions are
         // taken from the SIGN BITS of the interval lengths with integer and / or (2-cycle dual-issue instructions; boolean algebra on compare results is
         // what hipcc turns into 0 / 1 registers, and fminf / fmaxf bring a canonicalising v_max x, x per operand): "child j is hit" = sign clear.
@@ -402,21 +325,18 @@ __device__ __forceinline__ void node_step(const SceneDev& sc, RayState& r, STACK
 // them as scalar operands: no vector loads, no address arithmetic, no v_perm_b32 for that visit (50 instead of 63 vector instructions in front of the
 // push logic).  Same arithmetic, same bits; the few lanes at other nodes sit the step out.  Measured +2.5 % at a threshold of 44 lanes (32: +0.7 %,
 // 38-47: +1.0 ... +1.2 % before the detection reused the loop head's ballot, 50: -0.4 %, 56: -2.2 %: below ~36 lanes the lanes sitting out cost more than
-// the shared visit saves, above ~48 the test itself -- two vector instructions in front of EVERY node step -- is paid too often for nothing).  0 = off.
+// the shared visit saves, above ~48 the test itself -- two vector instructions in front of EVERY node step -- is paid too often for nothing).
 // The test costs two vector instructions and a scalar chain in front of a node step, and deep in the tree it never hits: after IRIS_SHARED_TRIES misses in a
 // row a wave skips it until its next refill (+1.3 ... +1.6 % on top: 1, 2, 3 misses equal, 4: +1.2 %, 8: +0.4 %; taking the reference lane from the rays of the
 // latest refill instead of the first lane at a node: no difference; a threshold of 36 / 40 with it: -0.4 / -0.6 %).
 #ifndef IRIS_SCALAR_TOP
 #define IRIS_SCALAR_TOP 44
 #endif
+static_assert(IRIS_SCALAR_TOP >= 1 && IRIS_SCALAR_TOP <= 64, "IRIS_SCALAR_TOP is a lane count");
 #ifndef IRIS_SHARED_TRIES
 #define IRIS_SHARED_TRIES 2
 #endif
 constexpr int kSharedTries = IRIS_SHARED_TRIES;
-#ifndef IRIS_SHARED_PAIRS
-#define IRIS_SHARED_PAIRS 1
-#endif
-#if IRIS_SCALAR_TOP
 typedef __attribute__((address_space(4))) const uint32_t cst_u32;
 template <class STACK>
 __device__ __forceinline__ void node_step_shared(const SceneDev& sc, RayState& r, STACK& st, uint32_t off0, bool fast_push = false) {
@@ -428,33 +348,11 @@ __device__ __forceinline__ void node_step_shared(const SceneDev& sc, RayState& r
     const uint64_t base = reinterpret_cast<uint64_t>(sc.nodes);
     const uint32_t off_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)off0);    // (inside `if (off == off0)` hipcc substitutes the per-lane value for the uniform one)
     const float ix = r.ix, iy = r.iy, iz = r.iz, nx = r.nx, ny = r.ny, nz = r.nz;
-#if IRIS_NODE80
-    // 20 words: {origin.xyz, scale} {ref[4]} {x planes of children 0..3} {y planes} | {z planes}: one x16 and one x4 scalar load; a plane word is the (near, far)
-    // pair of f16 subnormals as it stands -- no byte isolation on the scalar ALU either
-    typedef uint32_t iris_u4s __attribute__((ext_vector_type(4)));
-    iris_u16v w; iris_u4s wz;
-    asm volatile("s_load_dwordx16 %0, %2, %3\n\ts_load_dwordx4 %1, %2, %3 offset:64\n\ts_waitcnt lgkmcnt(0)" : "=&s"(w), "=&s"(wz) : "s"(base), "s"(off_s) : "memory");
-    uint32_t r0 = w[4], r1 = w[5], r2 = w[6], r3 = w[7];
-    const float sc24 = __uint_as_float(w[3]);
-    const float ax = sc24 * ix, ay = sc24 * iy, az = sc24 * iz;
-    const float bx = fmaf(__uint_as_float(w[0]), ix, nx), by = fmaf(__uint_as_float(w[1]), iy, ny), bz = fmaf(__uint_as_float(w[2]), iz, nz);
-#define IRIS_SLABS80(D, C)                                                                                                        \
-    {                                                                                                                             \
-        const iris_h2 hx = __builtin_bit_cast(iris_h2, (uint32_t)w[8 + (C)]), hy = __builtin_bit_cast(iris_h2, (uint32_t)w[12 + (C)]), hz = __builtin_bit_cast(iris_h2, (uint32_t)wz[C]);   \
-        float tn = fmaxf(fmaxf(fmaf((float)hx.x, ax, bx), fmaf((float)hy.x, ay, by)), fmaxf(fmaf((float)hz.x, az, bz), 0.f));      \
-        float tf = fminf(fminf(fmaf((float)hx.y, ax, bx), fmaf((float)hy.y, ay, by)), fminf(fmaf((float)hz.y, az, bz), r.h.t));    \
-        D = tf - tn;                                                                                                              \
-    }
-    float d0, d1, d2, d3;
-    IRIS_SLABS80(d0, 0) IRIS_SLABS80(d1, 1) IRIS_SLABS80(d2, 2) IRIS_SLABS80(d3, 3)
-#undef IRIS_SLABS80
-#else
     iris_u16v w;
     asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(base), "s"(off_s) : "memory");
     uint32_t r0 = w[12], r1 = w[13], r2 = w[14], r3 = w[15];
     const float ax = __uint_as_float(w[3]) * ix, ay = __uint_as_float(w[4]) * iy, az = __uint_as_float(w[5]) * iz;
     const float bx = fmaf(__uint_as_float(w[0]), ix, nx), by = fmaf(__uint_as_float(w[1]), iy, ny), bz = fmaf(__uint_as_float(w[2]), iz, nz);
-#if IRIS_SHARED_PAIRS
     // Bytes 0 / 2 and 1 / 3 of a plane word are isolated TOGETHER: w & 0x00ff00ff holds the planes of children 0 and 2 as the two f16 halves of one
     // scalar register, (w >> 8) & 0x00ff00ff those of children 1 and 3 -- on register PAIRS (the six plane words are adjacent), 9 scalar instructions
     // instead of the 24 single-byte extractions hipcc writes (asm: the compiler sees through the masks and goes back to single bytes).
@@ -478,22 +376,6 @@ __device__ __forceinline__ void node_step_shared(const SceneDev& sc, RayState& r
     IRIS_SLABS2(d0, m02, x) IRIS_SLABS2(d1, m13, x) IRIS_SLABS2(d2, m02, y) IRIS_SLABS2(d3, m13, y)
 #undef IRIS_SLABS2
 #undef IRIS_H2
-#else
-    const uint32_t nxq = w[6], nyq = w[7], nzq = w[8], fxq = w[9], fyq = w[10], fzq = w[11];
-#define IRIS_PAIR(NQ, FQ, C) __builtin_bit_cast(iris_h2, (uint32_t)((((NQ) >> (8 * (C))) & 0xffu) | ((((FQ) >> (8 * (C))) & 0xffu) << 16)))
-#define IRIS_SLABS(D, C)                                                                                                          \
-    {                                                                                                                             \
-        const iris_h2 hx = IRIS_PAIR(nxq, fxq, C), hy = IRIS_PAIR(nyq, fyq, C), hz = IRIS_PAIR(nzq, fzq, C);                       \
-        float tn = fmaxf(fmaxf(fmaf((float)hx.x, ax, bx), fmaf((float)hy.x, ay, by)), fmaxf(fmaf((float)hz.x, az, bz), 0.f));      \
-        float tf = fminf(fminf(fmaf((float)hx.y, ax, bx), fmaf((float)hy.y, ay, by)), fminf(fmaf((float)hz.y, az, bz), r.h.t));    \
-        D = tf - tn;                                                                                                              \
-    }
-    float d0, d1, d2, d3;
-    IRIS_SLABS(d0, 0) IRIS_SLABS(d1, 1) IRIS_SLABS(d2, 2) IRIS_SLABS(d3, 3)
-#undef IRIS_SLABS
-#undef IRIS_PAIR
-#endif
-#endif
     const int32_t b0 = __float_as_int(d0), b1 = __float_as_int(d1), b2 = __float_as_int(d2), b3 = __float_as_int(d3);
     const int32_t n01 = b0 & b1, n012 = n01 & b2;
     if (fast_push) {
@@ -516,7 +398,6 @@ __device__ __forceinline__ void node_step_shared(const SceneDev& sc, RayState& r
         r.cur = st.sp > 0 ? st.pop() : kEmptyRef;
     }
 }
-#endif
 
 // One triangle of the current leaf.
 __device__ __forceinline__ RayXf leaf_phase_xform(const RayState& r) {
@@ -547,7 +428,6 @@ __device__ __forceinline__ void leaf_step(const SceneDev& sc, RayState& r, const
 // advances in every iteration, one round trip each.  More instructions per ray (both streams are issued whenever any lane needs them), which a launch that leaves
 // the vector ALUs idle does not pay for.  Same arithmetic per ray; the closest hit does not depend on the schedule (lexicographic minimum of (t, index)).
 // -------------------------------------------------------------------------------------------------------
-#if !IRIS_NODE80
 template <class STACK>
 __device__ __forceinline__ void node_eval_q8(RayState& r, STACK& st, const iris_u4v hd, const iris_u4v q1, const iris_u4v q2, const iris_u4v rf) {
     // (node_step's Q8 arithmetic on words that are already loaded; checked pushes)
@@ -610,14 +490,11 @@ __device__ __forceinline__ Hit trace_q8_joint(const SceneDev& sc, f3 o, f3 d, ui
     }
     return r.h;
 }
-#endif
 
 // One ray per lane, run to completion (primary rays, the path-tracing stages, the pixel-per-wave bake kernel).
 template <int LAYOUT, bool COUNT = false, int LDS_DEPTH = kStackLds, bool GLOBAL_OVF = false, bool JOINT = false>
 __device__ __forceinline__ Hit trace_bvh4(const SceneDev& sc, f3 o, f3 d, uint32_t* lds_stack, TraceStats* ts = nullptr, uint32_t* ovf = nullptr) {
-#if !IRIS_NODE80
     if (JOINT && !COUNT && LAYOUT == kLayoutQ8) return trace_q8_joint<LDS_DEPTH, GLOBAL_OVF>(sc, o, d, lds_stack, ovf);      // (its own instantiation: 104 VGPRs against 77-83)
-#endif
     RayState r;
     ray_begin(sc, r, o, d);
     Stack<LDS_DEPTH, GLOBAL_OVF> st; st.lds = (lds_u32*)lds_stack; st.ovf = ovf; st.sp = 0; st.tid = threadIdx.x;
@@ -669,45 +546,9 @@ __device__ __forceinline__ Hit trace_bvh4(const SceneDev& sc, f3 o, f3 d, uint32
 #define IRIS_REFILL_MIN 48
 #endif
 constexpr int kRefillMin = IRIS_REFILL_MIN;
-// STRAGGLER PARKING (round 6, -DIRIS_PARK=1; tools/bvh_eval/wavesim `wpark+tile`).  When a wave refills, the <= 16 rays it still carries are deep in the tree and share
-// nothing with the 48 rays that start at the root: the fresh rays never reach the 44 lanes the shared scalar visit needs, and the wave keeps two populations apart
-// for the rest of their lives.  With parking the refilling wave writes those rays' traversal state -- hit so far, current reference, the LDS part of the stack and the
-// ray's id: 5 x 16 B -- to a WAVE-PRIVATE pool in the workspace (no exchange between waves: nothing to synchronise) and starts 64 fresh rays together; once the pool
-// holds a wave's worth it is taken instead of fresh rays (the stragglers run with each other), and whatever is left is taken when the list is exhausted.  A ray whose
-// stack has entries beyond the LDS part stays where it is.  Per-ray results do not change (the state is restored bit for bit; origin and direction are re-fetched).
-#ifndef IRIS_PARK
-#define IRIS_PARK 0
-#endif
-#ifndef IRIS_PARK_TAKE
-#define IRIS_PARK_TAKE 64
-#endif
-#ifndef IRIS_PARK_TAIL           // no parking once fewer than this many rays are left in the tile's list, and the pool is taken from IRIS_PARK_TAIL_TAKE records on:
-#define IRIS_PARK_TAIL 64        // the pools are then (nearly) empty when the list ends, instead of being drained at the end of the tile at a few lanes per wave
-#endif
-#ifndef IRIS_PARK_TAIL_TAKE
-#define IRIS_PARK_TAIL_TAKE 64
-#endif
-constexpr int kParkCap = 128;            // records per wave (<= 63 waiting + 16 per refill round; 5 x 16 B each)
-constexpr int kParkWords4 = 5;
-// (records are addressed as a scalar base + a 32-bit per-lane byte offset through address-space-1 pointers, like the tables: a per-lane 64-bit pointer is two
-//  registers that live across the refill round -- and were spilled to scratch there)
-typedef __attribute__((address_space(1))) iris_u4v glb_u4v_rw;
-__device__ __forceinline__ iris_u4v park_ld(const iris_u4v* base, uint32_t byte_off) { return *(glb_u4v*)(reinterpret_cast<const char*>(base) + (size_t)byte_off); }
-__device__ __forceinline__ void park_st(iris_u4v* base, uint32_t byte_off, iris_u4v v) { *(glb_u4v_rw*)(reinterpret_cast<char*>(base) + (size_t)byte_off) = v; }
-struct NoPark { static constexpr bool enabled = false; };
-template <class GetId, class SetId, class Refetch, class Left, class Claim>
-struct ParkOps {
-    static constexpr bool enabled = true;
-    iris_u4v* rec;        // this wave's records
-    GetId get_id;         // the id of the ray this lane carries
-    SetId set_id;         // ... set (an unparked ray)
-    Refetch refetch;      // (id, o, d): issue the loads of a ray's raw origin / direction again
-    Left left;            // rays left in the tile's list (wave-uniform)
-    Claim claim;          // the idle lanes claim the next rays of the list together: -> ray id, or -1
-};
-template <int LAYOUT, bool COUNT, int LDS_DEPTH, bool GLOBAL_OVF, class Fetch, class Prepare, class Retire, class Park = NoPark>
+template <int LAYOUT, bool COUNT, int LDS_DEPTH, bool GLOBAL_OVF, class Fetch, class Prepare, class Retire>
 __device__ __forceinline__ void trace_stream(const SceneDev& sc, uint32_t* lds_stack, uint32_t tid, uint32_t* ovf, TraceStats* ts, Fetch fetch, Prepare prepare,
-                                             Retire retire, Park park = Park()) {
+                                             Retire retire) {
     RayState r;
     r.o = mk3(0.f, 0.f, 0.f); r.d = mk3(0.f, 0.f, 1.f);
     ray_begin(sc, r, r.o, r.d);
@@ -716,7 +557,6 @@ __device__ __forceinline__ void trace_stream(const SceneDev& sc, uint32_t* lds_s
     int shared_tries = kSharedTries;   // wave-uniform: misses the shared-visit test may still have before it is skipped until the next refill
     bool live = false;             // this lane holds a ray (in flight, or finished and not yet retired)
     bool more = true;              // wave-uniform: the ray list is not exhausted
-    int n_pool = 0;                // wave-uniform: parked rays of this wave
     int max_sp = 0;
     const int kPhaseMinRt = sc.phase_min;
     for (;;) {
@@ -725,78 +565,6 @@ __device__ __forceinline__ void trace_stream(const SceneDev& sc, uint32_t* lds_s
         const int n_idle = __popcll(__ballot(idle0));
         if (more && (n_idle >= kRefillMin || n_idle == __popcll(__ballot(1)))) {
             bool got = false;
-            if constexpr (Park::enabled) {
-                bool idle = idle0;
-                // ---- park what is still in flight (while the list has a wave's worth of fresh rays left), then fill ALL lanes from one source
-                const int left = park.left();
-                if (left >= IRIS_PARK_TAIL) {
-                    const bool can = !idle && st.sp <= LDS_DEPTH;
-                    const unsigned long long mp = __ballot(can);
-                    const int np = popc_mask(mp);
-                    if (np > 0 && n_pool + np <= kParkCap) {
-                        if (can) {
-                            const int slot = n_pool + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mp >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mp, 0u));
-                            const uint32_t qo = (uint32_t)slot * (kParkWords4 * 16u);
-                            iris_u4v a0 = {__float_as_uint(r.h.t), __float_as_uint(r.h.u), __float_as_uint(r.h.v), (uint32_t)r.h.slot};
-                            iris_u4v a1 = {(uint32_t)r.h.id, r.cur, (uint32_t)st.sp, (uint32_t)park.get_id()};
-                            park_st(park.rec, qo, a0); park_st(park.rec, qo + 16u, a1);
-#pragma unroll
-                            for (int k = 0; k < 3; ++k) {
-                                iris_u4v e = {st.lds[(4 * k) * kBlock], st.lds[(4 * k + 1) * kBlock], st.lds[(4 * k + 2) * kBlock], st.lds[(4 * k + 3) * kBlock]};   // (entries beyond sp: garbage nobody reads)
-                                asm volatile("" : "+v"(e));      // (four entries in flight at a time: the scheduler would otherwise read all twelve first)
-                                park_st(park.rec, qo + 32u + 16u * k, e);
-                            }
-                            r.cur = kEmptyRef; live = false; idle = true;
-                        }
-                        n_pool += np;
-                    }
-                }
-                const bool from_pool = n_pool >= IRIS_PARK_TAKE || (left < IRIS_PARK_TAIL && n_pool >= IRIS_PARK_TAIL_TAKE) || (left <= 0 && n_pool > 0);
-                int uslot = -1;            // the record an unparked lane restores from (read in two steps: few registers live across ray_begin)
-                int id = -1;               // the ray this lane starts: from the pool or from the list -- ONE place below issues its loads
-                if (from_pool) {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // the records were written by other LANES of this wave, rounds ago: their stores are waited for HERE, once per take, not at every parking
-                    const unsigned long long mi = __ballot(idle);
-                    if (idle) {
-                        if (live) retire(r.h);
-                        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mi >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mi, 0u));
-                        if (rank < n_pool) {
-                            uslot = n_pool - 1 - rank;
-                            const uint32_t qo = (uint32_t)uslot * (kParkWords4 * 16u);
-                            id = (int)park_ld(park.rec, qo + 16u).w;
-#pragma unroll
-                            for (int k = 0; k < 3; ++k) {      // the stack goes straight back to this lane's LDS column, four entries at a time
-                                iris_u4v e = park_ld(park.rec, qo + 32u + 16u * k);
-                                asm volatile("" : "+v"(e));
-                                st.lds[(4 * k) * kBlock] = e.x; st.lds[(4 * k + 1) * kBlock] = e.y; st.lds[(4 * k + 2) * kBlock] = e.z; st.lds[(4 * k + 3) * kBlock] = e.w;
-                            }
-                        }
-                    }
-                    n_pool -= min(n_pool, popc_mask(mi));
-                } else if (idle) {
-                    if (live) retire(r.h);
-                    id = park.claim();
-                }
-                f3 o_ = mk3(0.f, 0.f, 0.f), d_ = mk3(0.f, 0.f, 1.f);      // (locals, dead at the end of the round: as members of the loop-carried state they were spilled around the restore below)
-                if (idle) {
-                    live = got = id >= 0;
-                    if (got) { park.set_id(id); park.refetch(id, o_, d_); }
-                }
-                if (__ballot(got) == 0 && n_pool == 0) more = false;
-                shared_tries = kSharedTries;
-                if (got) {
-                    prepare(o_, d_);
-                    ray_begin(sc, r, o_, d_);
-                    st.sp = 0;
-                    if (uslot >= 0) {
-                        const uint32_t qo = (uint32_t)uslot * (kParkWords4 * 16u);
-                        const iris_u4v a0 = park_ld(park.rec, qo), a1 = park_ld(park.rec, qo + 16u);
-                        r.h.t = __uint_as_float(a0.x); r.h.u = __uint_as_float(a0.y); r.h.v = __uint_as_float(a0.z); r.h.slot = (int)a0.w;
-                        r.h.id = (int)a1.x; r.cur = a1.y; st.sp = (int)a1.z;
-                    }
-                    if (COUNT) { ts->sp_gt8 += max_sp > 8; ts->sp_gt12 += max_sp > 12; ts->sp_gt16 += max_sp > 16; max_sp = 0; }
-                }
-            } else {
             if (idle0) {
                 if (live) retire(r.h);
                 live = got = fetch(r.o, r.d);
@@ -809,22 +577,15 @@ __device__ __forceinline__ void trace_stream(const SceneDev& sc, uint32_t* lds_s
                 st.sp = 0;
                 if (COUNT) { ts->sp_gt8 += max_sp > 8; ts->sp_gt12 += max_sp > 12; ts->sp_gt16 += max_sp > 16; max_sp = 0; }
             }
-            }
         }
         if (__ballot(r.cur != kEmptyRef) == 0) {
             if (!more) break;
             continue;
         }
-#if IRIS_EXP_NODRAIN
-        // (UPPER-BOUND EXPERIMENT, wrong results: what would a tile cost without its drain?  When the list is exhausted the rays still in flight are dropped -- retired as misses --
-        //  instead of being traversed to the end at falling lane utilisation.  Never defined in a shipped build.)
-        if (!more) { r.h.slot = -1; r.h.u = r.h.v = 0.f; break; }
-#endif
         // ---------------- node phase
         for (;;) {
             const bool at_node = r.cur != kEmptyRef && !(r.cur & kLeafBit);
             const unsigned long long m_node = __ballot(at_node);
-#if IRIS_LOOP_NEST
             // (nested tests with an empty asm in front of each inner one: hipcc otherwise folds them into ONE boolean -- s_cselect / s_and / s_or on mask pairs and a
             //  v_cmp on a 64-bit count -- where each test is a scalar compare and a branch)
             const int n_node = popc_mask(m_node);
@@ -833,20 +594,13 @@ __device__ __forceinline__ void trace_stream(const SceneDev& sc, uint32_t* lds_s
                 asm volatile("");
                 if (popc_mask(__ballot(r.cur != kEmptyRef && (r.cur & kLeafBit))) >= kPhaseMinRt) break;
             }
-            if (n_node <= 64 - kRefillMin) {
+            if (n_node <= 64 - kRefillMin) {          // (kRefillMin lanes can be idle only then: the ballot below is not paid for while the wave is busy)
                 asm volatile("");
                 if (more) {
                     asm volatile("");
                     if (popc_mask(__ballot(r.cur == kEmptyRef)) >= kRefillMin) break;   // enough idle lanes: go refill
                 }
             }
-#else
-            const int n_node = __popcll(m_node);
-            if (n_node == 0) break;
-            if (n_node < kPhaseMinRt && __popcll(__ballot(r.cur != kEmptyRef && (r.cur & kLeafBit))) >= kPhaseMinRt) break;
-            if ((!IRIS_IDLE_GATE || n_node <= 64 - kRefillMin) && more && popc_mask(__ballot(r.cur == kEmptyRef)) >= kRefillMin) break;   // enough idle lanes: go refill
-#endif
-#if IRIS_SCALAR_TOP
             if (LAYOUT == kLayoutQ8 && shared_tries > 0) {
                 const uint32_t off = node_offset(r.cur) + r.oct_base;           // (meaningless in the lanes that are not at a node: masked out below)
                 const uint32_t off0 = (uint32_t)__builtin_amdgcn_readlane((int)off, __builtin_ctzll(m_node));   // (m_node != 0 here: ctz, not ffs - 1 with its zero case)
@@ -856,17 +610,16 @@ __device__ __forceinline__ void trace_stream(const SceneDev& sc, uint32_t* lds_s
                         if (at_node && off == off0) { ts->nodes++; ts->count_top(r.cur); if (!more) ts->drain_nodes++; }
                         if (first_active_lane()) { ts->node_iters++; ts->shared_path_iters++; if (!more) ts->drain_node_iters++; }
                     }
-                    if (at_node && off == off0) node_step_shared(sc, r, st, off0, IRIS_FAST_PUSH && LDS_DEPTH >= 3 && __ballot(st.sp > LDS_DEPTH - 3) == 0);
+                    if (at_node && off == off0) node_step_shared(sc, r, st, off0, LDS_DEPTH >= 3 && __ballot(st.sp > LDS_DEPTH - 3) == 0);
                     if (COUNT) max_sp = max(max_sp, st.sp);
                     shared_tries = kSharedTries;
                     continue;
                 }
                 --shared_tries;       // the wave has diverged: after kSharedTries misses in a row the test is skipped until the next refill brings rays that start together
             }
-#endif
             if (at_node) {
                 if (COUNT) { ts->nodes++; ts->count_top(r.cur); ts->count_shared(r.cur, r.oct_base); if (first_active_lane()) ts->node_iters++; if (!more) { ts->drain_nodes++; if (first_active_lane()) ts->drain_node_iters++; } }
-                const bool fast_push = IRIS_FAST_PUSH && LDS_DEPTH >= 3 && __ballot(st.sp > LDS_DEPTH - 3) == 0;
+                const bool fast_push = LDS_DEPTH >= 3 && __ballot(st.sp > LDS_DEPTH - 3) == 0;
                 if (COUNT && !fast_push && first_active_lane()) ts->slow_push_iters++;
                 node_step<LAYOUT>(sc, r, st, fast_push);
                 if (COUNT) max_sp = max(max_sp, st.sp);
@@ -876,7 +629,6 @@ __device__ __forceinline__ void trace_stream(const SceneDev& sc, uint32_t* lds_s
         const RayXf xf = leaf_phase_xform(r);
         for (;;) {
             const bool at_leaf = r.cur != kEmptyRef && (r.cur & kLeafBit);
-#if IRIS_LOOP_NEST
             const int n_leaf = popc_mask(__ballot(at_leaf));
             if (n_leaf == 0) break;
             if (n_leaf < kPhaseMinRt) {
@@ -890,15 +642,9 @@ __device__ __forceinline__ void trace_stream(const SceneDev& sc, uint32_t* lds_s
                     if (popc_mask(__ballot(r.cur == kEmptyRef)) >= kRefillMin) break;
                 }
             }
-#else
-            const int n_leaf = __popcll(__ballot(at_leaf));
-            if (n_leaf == 0) break;
-            if (n_leaf < kPhaseMinRt && __popcll(__ballot(r.cur != kEmptyRef && !(r.cur & kLeafBit))) >= kPhaseMinRt) break;
-            if ((!IRIS_IDLE_GATE || n_leaf <= 64 - kRefillMin) && more && popc_mask(__ballot(r.cur == kEmptyRef)) >= kRefillMin) break;
-#endif
             if (at_leaf) {
                 if (COUNT) { ts->tris++; if (first_active_lane()) ts->leaf_iters++; }
-                leaf_step(sc, r, xf, st, IRIS_FAST_POP && __ballot(st.sp > LDS_DEPTH) == 0);
+                leaf_step(sc, r, xf, st, __ballot(st.sp > LDS_DEPTH) == 0);
             }
         }
     }
