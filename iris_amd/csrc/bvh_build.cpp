@@ -1,4 +1,4 @@
-// Binned-SAH BVH2 build (down to single triangles) + SAH-optimal collapse to a W-wide tree by dynamic programming (host only).
+// Binned-SAH BVH2 build (down to single triangles) + SAH-optimal collapse to a W-wide tree by dynamic programming + the device encoding of the result (host only).
 // See bvh_build.h.
 #include "bvh_build.h"
 
@@ -359,6 +359,120 @@ WideBvh build_wide_bvh(const float* verts, int64_t /*nv*/, const int32_t* faces,
         out.nodes[(size_t)it.wide] = w;
     }
     return out;
+}
+
+// ======================================================================================================
+// encoding for the device
+// ======================================================================================================
+bool quantise_node(const WideNode& w, int width, QuantNode& q) {
+    q.n = w.n;
+    for (int k = 0; k < 3; ++k) {
+        float org = kInf, top = -kInf;
+        for (int s = 0; s < w.n; ++s) { org = std::min(org, w.lo[s][k]); top = std::max(top, w.hi[s][k]); }
+        if (w.n == 0) { org = 0.f; top = 0.f; }
+        const double ext = (double)top - (double)org;
+        int e = -126;
+        if (ext > 0) e = std::max(-126, (int)std::ceil(std::log2(ext / 255.0)));
+        while (std::ldexp(255.0, e) < ext) ++e;                       // 255 * 2^e must cover the extent
+        const double sc = std::ldexp(1.0, e);
+        q.origin[k] = org; q.exp[k] = e;
+        for (int s = 0; s < width; ++s) {
+            if (s >= w.n) { q.lo[k][s] = 255; q.hi[k][s] = 0; continue; }   // inverted box: never hit
+            int lo = (int)std::floor(((double)w.lo[s][k] - (double)org) / sc);
+            int hi = (int)std::ceil(((double)w.hi[s][k] - (double)org) / sc);
+            lo = std::min(255, std::max(0, lo)); hi = std::min(255, std::max(0, hi));
+            while (lo > 0 && (double)org + lo * sc > (double)w.lo[s][k]) --lo;       // decoded box must contain the f32 box
+            while (hi < 255 && (double)org + hi * sc < (double)w.hi[s][k]) ++hi;
+            if ((double)org + hi * sc < (double)w.hi[s][k]) return false;
+            q.lo[k][s] = (uint8_t)lo; q.hi[k][s] = (uint8_t)hi;
+        }
+    }
+    return true;
+}
+
+void decode_node(const QuantNode& q, NodeBoxes& out) {
+    for (int s = 0; s < kMaxWidth; ++s)
+        for (int k = 0; k < 3; ++k) {
+            out.lo[s][k] = s < q.n ? decode_plane(q.origin[k], q.exp[k], q.lo[k][s]) : kInf;
+            out.hi[s][k] = s < q.n ? decode_plane(q.origin[k], q.exp[k], q.hi[k][s]) : -kInf;
+        }
+}
+
+std::vector<float> encode_nodes(const WideBvh& bvh, int layout) {
+    if (bvh.width != 4) return {};
+    const size_t nn = bvh.nodes.size();
+    // Unused child slots carry an inverted quantised box, which the slab test rejects -- except when the planes of a tiny node far from
+    // the ray origin collapse onto one t (b absorbs q * a): their reference is therefore a 1-triangle leaf on a degenerate record appended
+    // to the triangle table (all zeros: det = 0, never accepted), never kEmptyRef, which the traversal also uses as "lane idle".
+    const uint32_t dummy_leaf = leaf_ref((uint32_t)bvh.tri_order.size(), 1u);
+    auto ref_of = [&](const WideNode& w, int s) { return s < w.n ? child_ref(w, s) : dummy_leaf; };
+    if (layout == kLayoutF32) {          // 128 B: lox[4] hix[4] loy[4] hiy[4] loz[4] hiz[4] ref[4] pad[4]
+        std::vector<float> nodes(nn * (kNodeBytesF32 / 4));
+        for (size_t i = 0; i < nn; ++i) {
+            const WideNode& w = bvh.nodes[i];
+            float* p = nodes.data() + i * (kNodeBytesF32 / 4);
+            for (int s = 0; s < 4; ++s) {
+                for (int k = 0; k < 3; ++k) { p[8 * k + s] = w.lo[s][k]; p[8 * k + 4 + s] = w.hi[s][k]; }
+                const uint32_t ref = ref_of(w, s);
+                std::memcpy(&p[24 + s], &ref, 4);
+                p[28 + s] = 0.f;
+            }
+        }
+        return nodes;
+    }
+    // Q8, 64 B.  The plane scales 2^e are stored as floats (not as exponent bytes): decoding them on the device -- two ALU operations per axis
+    // right behind the load, in front of every slab test -- was measured 10 % slower on the whole bake
+    // (times 2^24: the kernel feeds the plane bytes to v_fma_mix_f32 as f16 subnormals q * 2^-24, iris_trace.h node_step)
+    //
+    // ONE COPY PER RAY OCTANT (round 3): copy o (bit 0: d.x < 0, bit 1: d.y < 0, bit 2: d.z < 0) holds the children in the front-to-back order
+    // the node's binary splits give a ray of that octant (WideNode::order), and per axis the plane the ray meets FIRST in the "near" bytes:
+    //   {origin.xyz, scale.x} {scale.y, scale.z, near_x[4], near_y[4]} {near_z[4], far_x[4], far_y[4], far_z[4]} {ref[4]}
+    // so that a node visit neither selects planes by the ray's signs (6 selects) nor sorts the children (5 compare-exchanges): 8 x 64 B per
+    // node -- 105 MB for the bench scene next to 288 GB -- against ~30 vector instructions per visit.  Child references are node indices
+    // (the same in every copy); a ray adds its copy's base offset (SceneDev::oct_stride).
+    constexpr size_t node_floats = kNodeBytes / 4;
+    std::vector<float> nodes(nn * node_floats * 8);
+    for (size_t i = 0; i < nn; ++i) {
+        const WideNode& w = bvh.nodes[i];
+        QuantNode q;
+        if (!quantise_node(w, 4, q)) return {};
+        for (int o = 0; o < 8; ++o) {
+            float* po = nodes.data() + ((size_t)o * nn + i) * node_floats;
+            for (int k = 0; k < 3; ++k) { po[k] = q.origin[k]; po[3 + k] = std::ldexp(1.0f, q.exp[k] + 24); }
+            uint8_t qo[6][4];
+            for (int j = 0; j < 4; ++j) {
+                const int sl = j < w.n ? (int)w.order[o][j] : j;          // (unused slots: the canonical inverted box (lo 255, hi 0) goes through the same swap, so it is empty for either sign)
+                for (int k = 0; k < 3; ++k) {
+                    const bool neg = (o >> k) & 1;
+                    qo[k][j] = neg ? q.hi[k][sl] : q.lo[k][sl];           // near
+                    qo[3 + k][j] = neg ? q.lo[k][sl] : q.hi[k][sl];       // far
+                }
+                const uint32_t ref = ref_of(w, sl);
+                std::memcpy(&po[12 + j], &ref, 4);
+            }
+            for (int k = 0; k < 6; ++k) std::memcpy(&po[6 + k], qo[k], 4);
+        }
+    }
+    return nodes;
+}
+
+// 64 B, one per 64-B line, component-major so that the watertight test's axis permutation is an address offset:
+// (p0.x, p1.x, p2.x, id) (p0.y, p1.y, p2.y, id) (p0.z, p1.z, p2.z, id) (0, 0, 0, 0)
+std::vector<float> encode_leaf_records(const WideBvh& bvh, const float* verts, const int32_t* faces) {
+    constexpr size_t rec = kLeafRecordBytes / 4;
+    const size_t nt = bvh.tri_order.size();
+    std::vector<float> tris((nt + 1) * rec, 0.f);      // + the degenerate record unused child slots point to (id -1, never accepted: det = 0)
+    { const int32_t none = -1; for (int k = 0; k < 3; ++k) std::memcpy(&tris[nt * rec + 4 * k + 3], &none, 4); }
+    for (size_t i = 0; i < nt; ++i) {
+        const int32_t f = bvh.tri_order[i];
+        float* p = tris.data() + i * rec;
+        for (int v = 0; v < 3; ++v) {
+            const float* pv = verts + (int64_t)faces[(int64_t)f * 3 + v] * 3;
+            for (int k = 0; k < 3; ++k) p[4 * k + v] = pv[k];
+        }
+        for (int k = 0; k < 3; ++k) std::memcpy(&p[4 * k + 3], &f, 4);
+    }
+    return tris;
 }
 
 }  // namespace iris

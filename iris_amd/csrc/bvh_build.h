@@ -1,6 +1,8 @@
-// Host-side BVH construction for libiris_hip.so: binned-SAH binary build, collapse to a W-wide tree.
+// Host-side BVH construction for libiris_hip.so: binned-SAH binary build, collapse to a W-wide tree, and the encoding of that tree into the
+// node / leaf-record tables the kernels read (host-only C++: the library, tools/bvh_eval and tests/native use the same encoder).
 // (The reference has no counterpart: it calls mitsuba.load_dict -> OptiX GAS build, bake_shading.py:55-61.)
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -37,5 +39,47 @@ struct WideBvh {
 // presplit x the median triangle's (0 = off), see bvh_build.cpp.
 WideBvh build_wide_bvh(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, int width, int leaf_tris,
                        float pad_rel = 2e-5f, float tri_cost = 0.7f, float presplit = 8.f);
+
+// ------------------------------------------------------------------------------------------------------
+// The tree as the kernels read it (iris_trace.h): what this encoder and the traversal share.
+// ------------------------------------------------------------------------------------------------------
+// Node layouts (iris_hip.h): BVH4_F32 = 128-B node with f32 planes (7 dwordx4 per visit); BVH4_Q8 = 64-B node
+// {origin.xyz, scale.x | scale.y, scale.z, qlo_x, qlo_y | qlo_z, qhi_x, qhi_y, qhi_z | ref[4]} with 8-bit planes relative to the node's
+// own box (4 dwordx4 per visit): plane = origin + q * 2^e per axis (the node stores 2^(e+24) as a float, see node_step), lo rounded down /
+// hi rounded up, so the decoded box contains the f32 box.
+constexpr int kLayoutF32 = 1, kLayoutQ8 = 3;
+// Q8 node record: 64 B, 8-bit planes four to a word (a visit isolates near / far byte pairs with 12 v_perm_b32).
+constexpr uint32_t kNodeBytes = 64u;
+constexpr uint32_t kNodeBytesF32 = 128u;
+constexpr uint32_t kLeafRecordBytes = 64u;   // one leaf triangle per 64-B line
+// A child reference is the index of an internal node, or a leaf: kLeafBit | first record << 3 | number of records (1..7).
+constexpr uint32_t kLeafBit = 0x80000000u;
+constexpr uint32_t leaf_ref(uint32_t start, uint32_t count) { return kLeafBit | (start << 3) | count; }
+constexpr uint32_t leaf_ref_start(uint32_t ref) { return (ref & ~kLeafBit) >> 3; }
+constexpr uint32_t leaf_ref_count(uint32_t ref) { return ref & 7u; }
+inline uint32_t child_ref(const WideNode& w, int s) {   // slot s < w.n
+    return w.child[s] >= 0 ? (uint32_t)w.child[s] : leaf_ref((uint32_t)w.leaf_start[s], (uint32_t)w.leaf_count[s]);
+}
+
+// The 8-bit planes of one node: per axis k the plane q stands for origin[k] + q * 2^exp[k].  Slots [n, width) carry the inverted box (lo 255, hi 0).
+struct QuantNode {
+    int n;                           // children in use, as WideNode::n
+    float origin[3];
+    int exp[3];
+    uint8_t lo[3][kMaxWidth], hi[3][kMaxWidth];
+};
+struct NodeBoxes { float lo[kMaxWidth][3], hi[kMaxWidth][3]; };
+// Conservative: every decoded child box contains the builder's f32 box.  false when 255 steps of the axis' scale cannot reach a child's upper plane.
+bool quantise_node(const WideNode& w, int width, QuantNode& q);
+inline float decode_plane(float origin, int exp, uint8_t q) { return (float)((double)origin + (double)q * std::ldexp(1.0, exp)); }
+// The boxes those bytes stand for; unused slots come back as the empty box (+inf, -inf).
+void decode_node(const QuantNode& q, NodeBoxes& out);
+
+// The node table of a 4-wide tree in `layout`, as floats (references bit-copied).  F32: one 128-B record per node, lox[4] hix[4] loy[4] hiy[4] loz[4]
+// hiz[4] ref[4] pad[4].  Q8: EIGHT tables of 64-B records, one per ray octant, one behind the other (see bvh_build.cpp).  Unused child slots refer to the
+// degenerate leaf record encode_leaf_records appends.  Empty when a node cannot be quantised (or the tree is not 4-wide).
+std::vector<float> encode_nodes(const WideBvh& bvh, int layout);
+// The leaf records (64 B each, in tri_order) + the degenerate record: tri_order.size() + 1 records.
+std::vector<float> encode_leaf_records(const WideBvh& bvh, const float* verts, const int32_t* faces);
 
 }  // namespace iris

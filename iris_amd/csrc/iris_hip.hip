@@ -7,6 +7,7 @@
 #include <cstring>
 #include <atomic>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -42,6 +43,25 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
     catch (...) { return fail(IRIS_ERR_BUILD, "unknown C++ exception"); }
 
 extern "C" IRIS_API const char* iris_last_error(void) { return g_err.c_str(); }
+
+// One device allocation / one event, owned: handles hold these, so that a constructor's early return and iris_*_destroy free the same things.
+struct DevBuf {
+    void* p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); return *this; }
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+    hipError_t upload(const void* host, size_t bytes) { return hipMemcpy(p, host, bytes, hipMemcpyHostToDevice); }     // into the allocation
+};
+struct DevEvent {
+    hipEvent_t ev = nullptr;
+    DevEvent() = default;
+    DevEvent(DevEvent&& o) noexcept : ev(o.ev) { o.ev = nullptr; }
+    DevEvent& operator=(DevEvent&& o) noexcept { std::swap(ev, o.ev); return *this; }
+    ~DevEvent() { if (ev) (void)hipEventDestroy(ev); }
+    hipError_t create() { return hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
+};
 
 // ---- diagnostics options (iris_hip_debug.h): process-wide, set by tests / experiments only; -1 = the built-in default
 static long long g_opt_bvh_tri_cost_x100 = -1, g_opt_bvh_max_leaf = -1, g_opt_phase_min = -1, g_opt_tile_target_rays = -1, g_opt_tiles_per_block = -1, g_opt_pt_tile_min = -1, g_opt_bvh_presplit_x10 = -1, g_opt_joint_max_rays = -1;
@@ -80,32 +100,34 @@ struct iris_scene {
     int device = 0;
     uint64_t uid = g_scene_uid.fetch_add(1);    // identity of this scene for caches keyed on it (a pointer can be reused after iris_scene_destroy)
     SceneDev dev{};
-    void* d_nodes = nullptr;
-    void* d_tris = nullptr;
+    DevBuf d_nodes, d_tris;
     iris_scene_info info{};
 };
 struct iris_slf {
     int device = 0;
     SlfDev dev{};
-    void* d_inds = nullptr;
-    void* d_rad = nullptr;
+    DevBuf d_inds, d_rad;
     int64_t kv = 0;
+    iris_slf(int device_, int64_t kv_) : device(device_), kv(kv_) {}
+    void bind(int H, double voxel_min, double voxel_max) {      // once both buffers are allocated
+        dev.inds = (const int32_t*)d_inds.p; dev.radiance = (const float4*)d_rad.p; dev.H = H;
+        dev.vmin = (float)voxel_min;
+        dev.den = (float)(voxel_max - voxel_min);
+    }
 };
 struct iris_emitter {
     int device = 0;
     EmitDev dev{};
-    void* d_ord = nullptr;
-    void* d_rad = nullptr;
-    void* d_area = nullptr;
-    void* d_verts = nullptr;   // (K,3,3) emitter_vertices   (sample_emitter only)
-    void* d_cdf = nullptr;     // (K) emitter_cdf
-    void* d_ord2tri = nullptr; // (K) triangle index per emitter ordinal
+    DevBuf d_ord, d_rad, d_area;
+    DevBuf d_verts;            // (K,3,3) emitter_vertices   (sample_emitter only)
+    DevBuf d_cdf;              // (K) emitter_cdf
+    DevBuf d_ord2tri;          // (K) triangle index per emitter ordinal
     EmitSampleDev sample{};
     bool can_sample = false;
     int64_t n_rad = 0, k = 0;
     // Fused leaf records (round 5): the scene's leaf-record table with this emitter's ordinal of every triangle in the record's free fourth plane, so that the shading pass of
     // the bake kernels reads it from the line it fetches anyway.  Built on first use per scene (iris_bake_view), kept for the handle's life (at most two scenes).
-    struct Fused { uint64_t scene_uid; void* d_tris; hipEvent_t ready; bool done; };
+    struct Fused { uint64_t scene_uid; DevBuf d_tris; DevEvent ready; bool done; };
     mutable std::mutex fused_mu;
     mutable std::vector<Fused> fused;
     mutable std::vector<Fused> retired;      // tables pushed out by a third scene: a launch that was handed one may still be on its way -- freed with the handle, never earlier
@@ -117,11 +139,42 @@ struct iris_emitter {
 constexpr long long kJointMaxRays = 1 << 20;
 static bool joint_launch(int64_t n_rays) { return n_rays <= (g_opt_joint_max_rays >= 0 ? g_opt_joint_max_rays : kJointMaxRays); }
 
+// The template arguments of a traversal kernel as a value: a launcher picks them once and hands them to the generic lambda that holds the launch (and its one argument list).
+template <int LAYOUT, bool JOINT = false> struct TraceTag { static constexpr int layout = LAYOUT; static constexpr bool joint = JOINT; };
+template <class F> static void with_layout(const SceneDev& sc, F&& f) {
+    if (sc.layout == kLayoutQ8) f(TraceTag<kLayoutQ8>{});
+    else f(TraceTag<kLayoutF32>{});
+}
+// the one-ray-per-lane kernels: <Q8, joint> for a small launch, else the plain kernel of the layout (there is no joint F32 traversal)
+template <class F> static void with_trace(const SceneDev& sc, int64_t n_rays, F&& f) {
+    if (sc.layout == kLayoutQ8 && joint_launch(n_rays)) f(TraceTag<kLayoutQ8, true>{});
+    else with_layout(sc, f);
+}
+// the bake kernels: <specular, instrumented, layout>
+template <bool SPEC, bool STATS, int LAYOUT> struct BakeTag { static constexpr bool spec = SPEC, stats = STATS; static constexpr int layout = LAYOUT; };
+template <class F> static void with_bake(bool spec, bool stats, const SceneDev& sc, F&& f) {
+    const bool q8 = sc.layout == kLayoutQ8;
+    if (stats) {
+        if (spec) { if (q8) f(BakeTag<true, true, kLayoutQ8>{}); else f(BakeTag<true, true, kLayoutF32>{}); }
+        else      { if (q8) f(BakeTag<false, true, kLayoutQ8>{}); else f(BakeTag<false, true, kLayoutF32>{}); }
+    } else {
+        if (spec) { if (q8) f(BakeTag<true, false, kLayoutQ8>{}); else f(BakeTag<true, false, kLayoutF32>{}); }
+        else      { if (q8) f(BakeTag<false, false, kLayoutQ8>{}); else f(BakeTag<false, false, kLayoutF32>{}); }
+    }
+}
+
 static int grid_for(int64_t n, int block, int max_blocks) {
     int64_t g = (n + block - 1) / block;
     if (g < 1) g = 1;
     if (g > max_blocks) g = max_blocks;
     return (int)g;
+}
+// A plain grid-stride launch: 256-thread blocks, at most max_blocks of them, and the launch's error.
+template <class... P, class... A>
+static int launch1d(void (*kernel)(P...), int64_t n, int max_blocks, iris_stream_t stream, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n, 256, max_blocks)), dim3(256), 0, (hipStream_t)stream, args...);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
 }
 static int num_cus() {
     static int cus = 0;
@@ -158,112 +211,17 @@ extern "C" IRIS_API int iris_debug_scene_create(const float* verts, int64_t nv, 
     if (3 * bvh.depth + 4 > kStackLds + kStackSpill) return fail(IRIS_ERR_BUILD, "iris_scene_create: BVH too deep for the traversal stack");
     if (layout == IRIS_BVH4_Q8 && bvh.nodes.size() * kNodeBytes * 8 >= ((size_t)1 << 32)) return fail(IRIS_ERR_BUILD, "iris_scene_create: the eight octant copies of the node table exceed 4 GiB (32-bit byte offsets)");
 
-    // ---- encode nodes ----
-    const size_t nn = bvh.nodes.size();
-    // Unused child slots carry an inverted quantised box, which the slab test rejects -- except when the planes of a tiny node far from
-    // the ray origin collapse onto one t (b absorbs q * a): their reference is therefore a 1-triangle leaf on a degenerate record appended
-    // to the triangle table (all zeros: det = 0, never accepted), never kEmptyRef, which the traversal also uses as "lane idle".
-    const uint32_t dummy_leaf = kLeafBit | ((uint32_t)bvh.tri_order.size() << 3) | 1u;
-    auto child_ref = [&](const WideNode& w, int s) -> uint32_t {
-        if (s >= w.n) return dummy_leaf;
-        if (w.child[s] >= 0) return (uint32_t)w.child[s];
-        return kLeafBit | ((uint32_t)w.leaf_start[s] << 3) | (uint32_t)w.leaf_count[s];
-    };
-    const int node_floats = layout == IRIS_BVH4_Q8 ? (int)kNodeBytes / 4 : 32;
-    const int n_copies = layout == IRIS_BVH4_Q8 ? 8 : 1;       // Q8: one copy of the node table per ray octant (see below)
-    std::vector<float> nodes(nn * node_floats * n_copies);
-    for (size_t i = 0; i < nn; ++i) {
-        const WideNode& w = bvh.nodes[i];
-        float* p = nodes.data() + i * node_floats;
-        if (layout == IRIS_BVH4_F32) {   // 128 B: lox[4] hix[4] loy[4] hiy[4] loz[4] hiz[4] ref[4] pad[4]
-            for (int s = 0; s < 4; ++s) {
-                p[0 + s] = w.lo[s][0]; p[4 + s] = w.hi[s][0];
-                p[8 + s] = w.lo[s][1]; p[12 + s] = w.hi[s][1];
-                p[16 + s] = w.lo[s][2]; p[20 + s] = w.hi[s][2];
-                uint32_t ref = child_ref(w, s);
-                std::memcpy(&p[24 + s], &ref, 4);
-                p[28 + s] = 0.f;
-            }
-        } else {                         // 64 B: origin.xyz, scale.x | scale.yz, qlo_x, qlo_y | qlo_z, qhi_x, qhi_y, qhi_z | ref[4]
-            float org[3], hi3[3];
-            for (int k = 0; k < 3; ++k) {
-                org[k] = INFINITY; hi3[k] = -INFINITY;
-                for (int s = 0; s < w.n; ++s) { org[k] = std::min(org[k], w.lo[s][k]); hi3[k] = std::max(hi3[k], w.hi[s][k]); }
-                if (w.n == 0) { org[k] = 0.f; hi3[k] = 0.f; }
-            }
-            uint32_t ebytes = 0;
-            uint8_t q[6][4];   // planes lo_x lo_y lo_z hi_x hi_y hi_z
-            for (int k = 0; k < 3; ++k) {
-                const double ext = (double)hi3[k] - (double)org[k];
-                int e = -126;
-                if (ext > 0) e = std::max(-126, (int)std::ceil(std::log2(ext / 255.0)));
-                while (std::ldexp(255.0, e) < ext) ++e;                       // 255 * 2^e must cover the extent
-                const double sc = std::ldexp(1.0, e);
-                ebytes |= (uint32_t)(e + 127) << (8 * k);
-                for (int s = 0; s < 4; ++s) {
-                    if (s >= w.n) { q[k][s] = 255; q[3 + k][s] = 0; continue; }   // inverted box: never hit
-                    int lo = (int)std::floor(((double)w.lo[s][k] - (double)org[k]) / sc);
-                    int hi = (int)std::ceil(((double)w.hi[s][k] - (double)org[k]) / sc);
-                    lo = std::min(255, std::max(0, lo)); hi = std::min(255, std::max(0, hi));
-                    while (lo > 0 && (double)org[k] + lo * sc > (double)w.lo[s][k]) --lo;       // decoded box must contain the f32 box
-                    while (hi < 255 && (double)org[k] + hi * sc < (double)w.hi[s][k]) ++hi;
-                    if ((double)org[k] + hi * sc < (double)w.hi[s][k]) return fail(IRIS_ERR_BUILD, "iris_scene_create: node quantisation failed");
-                    q[k][s] = (uint8_t)lo; q[3 + k][s] = (uint8_t)hi;
-                }
-            }
-            // the plane scales 2^e are stored as floats (not as exponent bytes): decoding them on the device -- two ALU operations per axis
-            // right behind the load, in front of every slab test -- was measured 10 % slower on the whole bake
-            // (times 2^24: the kernel feeds the plane bytes to v_fma_mix_f32 as f16 subnormals q * 2^-24, iris_trace.h node_step)
-            //
-            // ONE COPY PER RAY OCTANT (round 3): copy o (bit 0: d.x < 0, bit 1: d.y < 0, bit 2: d.z < 0) holds the children in the front-to-back order
-            // the node's binary splits give a ray of that octant (WideNode::order), and per axis the plane the ray meets FIRST in the "near" bytes:
-            //   {origin.xyz, scale.x} {scale.y, scale.z, near_x[4], near_y[4]} {near_z[4], far_x[4], far_y[4], far_z[4]} {ref[4]}
-            // so that a node visit neither selects planes by the ray's signs (6 selects) nor sorts the children (5 compare-exchanges): 8 x 64 B per
-            // node -- 105 MB for the bench scene next to 288 GB -- against ~30 vector instructions per visit.  Child references are node indices
-            // (the same in every copy); a ray adds its copy's base offset (SceneDev::oct_stride).
-            for (int o = 0; o < 8; ++o) {
-                float* po = nodes.data() + ((size_t)o * nn + i) * node_floats;
-                po[0] = org[0]; po[1] = org[1]; po[2] = org[2];
-                for (int k = 0; k < 3; ++k) po[3 + k] = std::ldexp(1.0f, (int)((ebytes >> (8 * k)) & 0xffu) - 127 + 24);
-                uint8_t qo[6][4];
-                for (int j = 0; j < 4; ++j) {
-                    const int sl = j < w.n ? (int)w.order[o][j] : j;          // (unused slots: the canonical inverted box (lo 255, hi 0) goes through the same swap, so it is empty for either sign)
-                    for (int k = 0; k < 3; ++k) {
-                        const bool neg = (o >> k) & 1;
-                        qo[k][j] = neg ? q[3 + k][sl] : q[k][sl];             // near
-                        qo[3 + k][j] = neg ? q[k][sl] : q[3 + k][sl];         // far
-                    }
-                    const uint32_t ref = child_ref(w, sl);
-                    std::memcpy(&po[12 + j], &ref, 4);
-                }
-                for (int k = 0; k < 6; ++k) std::memcpy(&po[6 + k], qo[k], 4);
-            }
-        }
-    }
-    // ---- encode leaf triangles (64 B, one per 64-B line), component-major so that the watertight test's axis permutation is an address
-    // offset: (p0.x, p1.x, p2.x, id) (p0.y, p1.y, p2.y, id) (p0.z, p1.z, p2.z, id) (0, 0, 0, 0) ----
-    const size_t nt = bvh.tri_order.size();
-    std::vector<float> tris((nt + 1) * 16, 0.f);      // + the degenerate record unused child slots point to (id -1, never accepted: det = 0)
-    { const int32_t none = -1; for (int k = 0; k < 3; ++k) std::memcpy(&tris[nt * 16 + 4 * k + 3], &none, 4); }
-    for (size_t i = 0; i < nt; ++i) {
-        int32_t f = bvh.tri_order[i];
-        float* p = tris.data() + i * 16;
-        for (int v = 0; v < 3; ++v) {
-            const float* pv = verts + (int64_t)faces[(int64_t)f * 3 + v] * 3;
-            for (int k = 0; k < 3; ++k) p[4 * k + v] = pv[k];
-        }
-        for (int k = 0; k < 3; ++k) std::memcpy(&p[4 * k + 3], &f, 4);
-    }
-    iris_scene* s = new iris_scene();
+    const std::vector<float> nodes = encode_nodes(bvh, layout == IRIS_BVH4_Q8 ? kLayoutQ8 : kLayoutF32);      // bvh_build.h: the tables as the kernels read them
+    if (nodes.empty()) return fail(IRIS_ERR_BUILD, "iris_scene_create: node quantisation failed");
+    const std::vector<float> tris = encode_leaf_records(bvh, verts, faces);
+    const size_t nn = bvh.nodes.size(), nt = bvh.tri_order.size();
+    auto s = std::make_unique<iris_scene>();
     s->device = device;
-    if (hipMalloc(&s->d_nodes, nodes.size() * 4) != hipSuccess || hipMalloc(&s->d_tris, tris.size() * 4) != hipSuccess ||
-        hipMemcpy(s->d_nodes, nodes.data(), nodes.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(s->d_tris, tris.data(), tris.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(s->d_nodes); (void)hipFree(s->d_tris); delete s;
+    if (s->d_nodes.alloc(nodes.size() * 4) != hipSuccess || s->d_tris.alloc(tris.size() * 4) != hipSuccess ||
+        s->d_nodes.upload(nodes.data(), nodes.size() * 4) != hipSuccess || s->d_tris.upload(tris.data(), tris.size() * 4) != hipSuccess)
         return fail(IRIS_ERR_HIP, "iris_scene_create: device allocation / upload failed");
-    }
-    s->dev.nodes = (const float4*)s->d_nodes;
-    s->dev.tris = (const float4*)s->d_tris;
+    s->dev.nodes = (const float4*)s->d_nodes.p;
+    s->dev.tris = (const float4*)s->d_tris.p;
     s->dev.n_nodes = (int)nn;
     s->dev.n_tris = (int)nt;
     s->dev.layout = layout == IRIS_BVH4_Q8 ? kLayoutQ8 : kLayoutF32;
@@ -271,18 +229,14 @@ extern "C" IRIS_API int iris_debug_scene_create(const float* verts, int64_t nv, 
     s->dev.phase_min = kPhaseMin;
     if (g_opt_phase_min >= 0) s->dev.phase_min = (int)g_opt_phase_min;  // iris_debug_set("phase_min") (results do not depend on it)
     s->info.n_vertices = nv; s->info.n_triangles = nf; s->info.layout = layout; s->info.n_nodes = (int32_t)nn;
-    s->info.node_bytes = layout == IRIS_BVH4_Q8 ? (int)kNodeBytes : 128; s->info.tri_bytes = 64; s->info.depth = bvh.depth;
+    s->info.node_bytes = (int)(layout == IRIS_BVH4_Q8 ? kNodeBytes : kNodeBytesF32); s->info.tri_bytes = (int)kLeafRecordBytes; s->info.depth = bvh.depth;
     s->info.sah_cost = bvh.sah_cost; s->info.n_leaf_records = (int32_t)nt;
     s->info.build_seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t0).count();
-    *out = s;
+    *out = s.release();
     return IRIS_OK;
     API_END
 }
-extern "C" IRIS_API void iris_scene_destroy(iris_scene* s) {
-    if (!s) return;
-    (void)hipFree(s->d_nodes); (void)hipFree(s->d_tris);
-    delete s;
-}
+extern "C" IRIS_API void iris_scene_destroy(iris_scene* s) { delete s; }
 extern "C" IRIS_API int iris_scene_get_info(const iris_scene* s, iris_scene_info* out) {
     if (!s || !out) return fail(IRIS_ERR_ARG, "iris_scene_get_info: null");
     *out = s->info;
@@ -303,16 +257,13 @@ extern "C" IRIS_API int iris_slf_create(const int64_t* inds, int H, const float*
     }
     std::vector<float> rad((size_t)std::max<int64_t>(kv, 1) * 4, 0.f);
     for (int64_t i = 0; i < kv; ++i) { rad[i * 4] = radiance[i * 3]; rad[i * 4 + 1] = radiance[i * 3 + 1]; rad[i * 4 + 2] = radiance[i * 3 + 2]; }
-    iris_slf* s = new iris_slf();
-    s->device = device; s->kv = kv;
-    HIP_TRY(hipMalloc(&s->d_inds, n * 4));
-    HIP_TRY(hipMalloc(&s->d_rad, rad.size() * 4));
-    HIP_TRY(hipMemcpy(s->d_inds, i32.data(), n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->d_rad, rad.data(), rad.size() * 4, hipMemcpyHostToDevice));
-    s->dev.inds = (const int32_t*)s->d_inds; s->dev.radiance = (const float4*)s->d_rad; s->dev.H = H;
-    s->dev.vmin = (float)voxel_min;
-    s->dev.den = (float)(voxel_max - voxel_min);
-    *out = s;
+    auto s = std::make_unique<iris_slf>(device, kv);
+    HIP_TRY(s->d_inds.alloc(n * 4));
+    HIP_TRY(s->d_rad.alloc(rad.size() * 4));
+    HIP_TRY(s->d_inds.upload(i32.data(), n * 4));
+    HIP_TRY(s->d_rad.upload(rad.data(), rad.size() * 4));
+    s->bind(H, voxel_min, voxel_max);
+    *out = s.release();
     return IRIS_OK;
     API_END
 }
@@ -325,40 +276,34 @@ __global__ void slf_inds_narrow_kernel(const int64_t* __restrict__ src, int32_t*
         dst[i] = (int32_t)v;
     }
 }
-__global__ void pad_rows_kernel(const float* __restrict__ src, float4* __restrict__ dst, int64_t n);
+__global__ void pad_rows_kernel(const float* __restrict__ src, float4* __restrict__ dst, int64_t n) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        dst[i] = make_float4(src[i * 3], src[i * 3 + 1], src[i * 3 + 2], 0.f);
+}
 extern "C" IRIS_API int iris_slf_create_dev(const int64_t* inds_dev, int H, const float* radiance_dev, int64_t kv, double voxel_min, double voxel_max,
                                    int device, iris_slf** out, iris_stream_t stream) {
     API_BEGIN
     if (!out || !inds_dev || H <= 0 || H > 1024 || kv < 0 || (kv > 0 && !radiance_dev)) return fail(IRIS_ERR_ARG, "iris_slf_create_dev: bad arguments");
     HIP_TRY(hipSetDevice(device));
     const size_t n = (size_t)H * H * H;
-    iris_slf* s = new iris_slf();
-    s->device = device; s->kv = kv;
-    int* d_bad = nullptr;
-    auto cleanup = [&](int rc, const char* msg) { (void)hipFree(s->d_inds); (void)hipFree(s->d_rad); (void)hipFree(d_bad); delete s; return fail(rc, msg); };
-    if (hipMalloc(&s->d_inds, n * 4) != hipSuccess || hipMalloc(&s->d_rad, (size_t)std::max<int64_t>(kv, 1) * 16) != hipSuccess || hipMalloc(&d_bad, 4) != hipSuccess)
-        return cleanup(IRIS_ERR_HIP, "iris_slf_create_dev: out of device memory");
+    auto s = std::make_unique<iris_slf>(device, kv);
+    DevBuf d_bad;
+    if (s->d_inds.alloc(n * 4) != hipSuccess || s->d_rad.alloc((size_t)std::max<int64_t>(kv, 1) * 16) != hipSuccess || d_bad.alloc(4) != hipSuccess)
+        return fail(IRIS_ERR_HIP, "iris_slf_create_dev: out of device memory");
     hipStream_t st = (hipStream_t)stream;
-    (void)hipMemsetAsync(d_bad, 0, 4, st);
-    (void)hipMemsetAsync(s->d_rad, 0, (size_t)std::max<int64_t>(kv, 1) * 16, st);
-    hipLaunchKernelGGL(slf_inds_narrow_kernel, dim3(grid_for((int64_t)n, 256, 8192)), dim3(256), 0, st, inds_dev, (int32_t*)s->d_inds, (int64_t)n, kv, d_bad);
-    if (kv > 0) hipLaunchKernelGGL(pad_rows_kernel, dim3(grid_for(kv, 256, 1024)), dim3(256), 0, st, radiance_dev, (float4*)s->d_rad, kv);
+    (void)hipMemsetAsync(d_bad.p, 0, 4, st);
+    (void)hipMemsetAsync(s->d_rad.p, 0, (size_t)std::max<int64_t>(kv, 1) * 16, st);
+    hipLaunchKernelGGL(slf_inds_narrow_kernel, dim3(grid_for((int64_t)n, 256, 8192)), dim3(256), 0, st, inds_dev, (int32_t*)s->d_inds.p, (int64_t)n, kv, (int*)d_bad.p);
+    if (kv > 0) hipLaunchKernelGGL(pad_rows_kernel, dim3(grid_for(kv, 256, 1024)), dim3(256), 0, st, radiance_dev, (float4*)s->d_rad.p, kv);
     int bad = 0;
-    if (hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return cleanup(IRIS_ERR_HIP, "iris_slf_create_dev: HIP error");
-    if (bad) return cleanup(IRIS_ERR_ARG, "iris_slf_create_dev: inds entry out of range");
-    (void)hipFree(d_bad);
-    s->dev.inds = (const int32_t*)s->d_inds; s->dev.radiance = (const float4*)s->d_rad; s->dev.H = H;
-    s->dev.vmin = (float)voxel_min;
-    s->dev.den = (float)(voxel_max - voxel_min);
-    *out = s;
+    if (hipMemcpyAsync(&bad, d_bad.p, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(IRIS_ERR_HIP, "iris_slf_create_dev: HIP error");
+    if (bad) return fail(IRIS_ERR_ARG, "iris_slf_create_dev: inds entry out of range");
+    s->bind(H, voxel_min, voxel_max);
+    *out = s.release();
     return IRIS_OK;
     API_END
 }
-extern "C" IRIS_API void iris_slf_destroy(iris_slf* s) {
-    if (!s) return;
-    (void)hipFree(s->d_inds); (void)hipFree(s->d_rad);
-    delete s;
-}
+extern "C" IRIS_API void iris_slf_destroy(iris_slf* s) { delete s; }
 
 // ======================================================================================================
 // NGPBRDF (model/brdf.py:213-260): hash-grid encoding + MLP, inference
@@ -366,15 +311,15 @@ extern "C" IRIS_API void iris_slf_destroy(iris_slf* s) {
 struct iris_ngp {
     int device = 0;
     NgpLevels lv{};
-    void* d_grid = nullptr;     // half2 entries
-    void* d_w = nullptr;        // kNgpMlpParams halves
-    void* d_feat = nullptr;     // [32 levels][kChunk] half2: the encoded features of one chunk of points
+    DevBuf d_grid;              // half2 entries
+    DevBuf d_w;                 // kNgpMlpParams halves
+    DevBuf d_feat;              // [32 levels][kChunk] half2: the encoded features of one chunk of points
     float vmin = 0.f, den = 1.f;
     uint64_t n_entries = 0;
     // d_feat is the handle's ONE scratch buffer: forwards of one handle are serialised on the device -- a call on another stream than the previous call's first
     // waits (on the device, not the host) for the event that call recorded behind its last kernel.  Host threads are serialised by the mutex.
     mutable std::mutex mu;
-    mutable hipEvent_t last_use = nullptr;
+    mutable DevEvent last_use;
     mutable hipStream_t last_stream = nullptr;
     mutable bool used = false;
 };
@@ -406,26 +351,22 @@ extern "C" IRIS_API int iris_ngp_create(const float* params, int64_t n_params, d
     API_BEGIN
     if (!out || !params) return fail(IRIS_ERR_ARG, "iris_ngp_create: bad arguments");
     HIP_TRY(hipSetDevice(device));              // (before anything is allocated: an invalid device leaves nothing behind)
-    iris_ngp* g = new iris_ngp();
+    auto g = std::make_unique<iris_ngp>();
     g->device = device;
     g->n_entries = ngp_levels(g->lv);
-    if (n_params != (int64_t)kNgpMlpParams + (int64_t)g->n_entries * 2) {
-        delete g;
+    if (n_params != (int64_t)kNgpMlpParams + (int64_t)g->n_entries * 2)
         return fail(IRIS_ERR_ARG, "iris_ngp_create: mlp.params has " + std::to_string(n_params) + " entries, the NGPBRDF configuration has " + std::to_string(iris_ngp_n_params()));
-    }
     std::vector<uint16_t> h((size_t)n_params);
     for (int64_t i = 0; i < n_params; ++i) h[(size_t)i] = f32_to_f16_bits(params[i]);
-    auto cleanup = [&](const char* msg) { (void)hipFree(g->d_grid); (void)hipFree(g->d_w); (void)hipFree(g->d_feat); if (g->last_use) (void)hipEventDestroy(g->last_use); delete g; return fail(IRIS_ERR_HIP, msg); };
-    if (hipMalloc(&g->d_w, (size_t)kNgpMlpParams * 2) != hipSuccess || hipMalloc(&g->d_grid, (size_t)g->n_entries * 4) != hipSuccess ||
-        hipMalloc(&g->d_feat, (size_t)kNgpLevels * kNgpChunk * 4) != hipSuccess)
-        return cleanup("iris_ngp_create: out of device memory");
-    if (hipEventCreateWithFlags(&g->last_use, hipEventDisableTiming) != hipSuccess) return cleanup("iris_ngp_create: hipEventCreate failed");
-    if (hipMemcpy(g->d_w, h.data(), (size_t)kNgpMlpParams * 2, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(g->d_grid, h.data() + kNgpMlpParams, (size_t)g->n_entries * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return cleanup("iris_ngp_create: upload failed");
+    if (g->d_w.alloc((size_t)kNgpMlpParams * 2) != hipSuccess || g->d_grid.alloc((size_t)g->n_entries * 4) != hipSuccess ||
+        g->d_feat.alloc((size_t)kNgpLevels * kNgpChunk * 4) != hipSuccess)
+        return fail(IRIS_ERR_HIP, "iris_ngp_create: out of device memory");
+    if (g->last_use.create() != hipSuccess) return fail(IRIS_ERR_HIP, "iris_ngp_create: hipEventCreate failed");
+    if (g->d_w.upload(h.data(), (size_t)kNgpMlpParams * 2) != hipSuccess || g->d_grid.upload(h.data() + kNgpMlpParams, (size_t)g->n_entries * 4) != hipSuccess)
+        return fail(IRIS_ERR_HIP, "iris_ngp_create: upload failed");
     g->vmin = (float)voxel_min;
     g->den = (float)(voxel_max - voxel_min);           // (the difference of the two python floats, taken in double, enters the float32 tensor arithmetic as one scalar)
-    *out = g;
+    *out = g.release();
     return IRIS_OK;
     API_END
 }
@@ -436,9 +377,9 @@ extern "C" IRIS_API int iris_ngp_forward(const iris_ngp* g, const float* positio
     hipStream_t st = (hipStream_t)stream;
     if (N == 0) return IRIS_OK;
     std::lock_guard<std::mutex> lock(g->mu);
-    if (g->used && g->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, g->last_use, 0));      // the previous forward of this handle still owns d_feat
+    if (g->used && g->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, g->last_use.ev, 0));      // the previous forward of this handle still owns d_feat
     NgpArgs a{};
-    a.lv = g->lv; a.grid = (const uint32_t*)g->d_grid; a.w = (const _Float16*)g->d_w; a.pos = position; a.feat = (uint32_t*)g->d_feat;
+    a.lv = g->lv; a.grid = (const uint32_t*)g->d_grid.p; a.w = (const _Float16*)g->d_w.p; a.pos = position; a.feat = (uint32_t*)g->d_feat.p;
     a.albedo = albedo; a.rough = roughness; a.metal = metallic; a.n_chunk = kNgpChunk; a.vmin = g->vmin; a.den = g->den;
     for (int64_t n0 = 0; n0 < N; n0 += kNgpChunk) {          // (stream-ordered: the feature planes of a chunk are consumed before the next chunk's encode overwrites them)
         a.n0 = n0; a.n = (int)std::min<int64_t>(kNgpChunk, N - n0);
@@ -447,7 +388,7 @@ extern "C" IRIS_API int iris_ngp_forward(const iris_ngp* g, const float* positio
         hipLaunchKernelGGL(ngp_mlp_kernel, dim3(std::min(std::max((tiles + 3) / 4, 1), 2048)), dim3(256), 0, st, a);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(g->last_use, st));
+    HIP_TRY(hipEventRecord(g->last_use.ev, st));
     g->last_stream = st; g->used = true;
     return IRIS_OK;
     API_END
@@ -458,19 +399,14 @@ extern "C" IRIS_API int iris_debug_ngp_encode(const iris_ngp* g, const float* po
     if (N == 0) return IRIS_OK;
     HIP_TRY(hipSetDevice(g->device));
     NgpArgs a{};
-    a.lv = g->lv; a.grid = (const uint32_t*)g->d_grid; a.w = (const _Float16*)g->d_w; a.pos = position; a.feat = feat;
+    a.lv = g->lv; a.grid = (const uint32_t*)g->d_grid.p; a.w = (const _Float16*)g->d_w.p; a.pos = position; a.feat = feat;
     a.n_chunk = (int)N; a.vmin = g->vmin; a.den = g->den; a.n0 = 0; a.n = (int)N;
     hipLaunchKernelGGL(ngp_encode_kernel, dim3((a.n + 255) / 256, kNgpLevels), dim3(256), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
     API_END
 }
-extern "C" IRIS_API void iris_ngp_destroy(iris_ngp* g) {
-    if (!g) return;
-    (void)hipFree(g->d_grid); (void)hipFree(g->d_w); (void)hipFree(g->d_feat);
-    if (g->last_use) (void)hipEventDestroy(g->last_use);
-    delete g;
-}
+extern "C" IRIS_API void iris_ngp_destroy(iris_ngp* g) { delete g; }
 
 extern "C" IRIS_API int iris_emitter_create(const uint8_t* is_emitter, int64_t nf, const float* radiance, int64_t n_rad, const float* area,
                                    int64_t k, const float* verts, const float* cdf, int device, iris_emitter** out) {
@@ -484,59 +420,45 @@ extern "C" IRIS_API int iris_emitter_create(const uint8_t* is_emitter, int64_t n
     if (c > n_rad) return fail(IRIS_ERR_ARG, "iris_emitter_create: radiance has fewer rows than emitters");
     std::vector<float> rad((size_t)std::max<int64_t>(n_rad, 1) * 4, 0.f);
     for (int64_t i = 0; i < n_rad; ++i) { rad[i * 4] = radiance[i * 3]; rad[i * 4 + 1] = radiance[i * 3 + 1]; rad[i * 4 + 2] = radiance[i * 3 + 2]; }
-    iris_emitter* e = new iris_emitter();
+    auto e = std::make_unique<iris_emitter>();
     e->device = device; e->n_rad = n_rad; e->k = k;
-    HIP_TRY(hipMalloc(&e->d_ord, ord.size() * 4));
-    HIP_TRY(hipMalloc(&e->d_rad, rad.size() * 4));
-    HIP_TRY(hipMalloc(&e->d_area, (size_t)std::max<int64_t>(k, 1) * 4));
-    HIP_TRY(hipMemcpy(e->d_ord, ord.data(), ord.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->d_rad, rad.data(), rad.size() * 4, hipMemcpyHostToDevice));
-    if (k > 0) HIP_TRY(hipMemcpy(e->d_area, area, (size_t)k * 4, hipMemcpyHostToDevice));
-    e->dev.emit_ord = (const int32_t*)e->d_ord; e->dev.radiance = (const float4*)e->d_rad; e->dev.area = (const float*)e->d_area;
+    HIP_TRY(e->d_ord.alloc(ord.size() * 4));
+    HIP_TRY(e->d_rad.alloc(rad.size() * 4));
+    HIP_TRY(e->d_area.alloc((size_t)std::max<int64_t>(k, 1) * 4));
+    HIP_TRY(e->d_ord.upload(ord.data(), ord.size() * 4));
+    HIP_TRY(e->d_rad.upload(rad.data(), rad.size() * 4));
+    if (k > 0) HIP_TRY(e->d_area.upload(area, (size_t)k * 4));
+    e->dev.emit_ord = (const int32_t*)e->d_ord.p; e->dev.radiance = (const float4*)e->d_rad.p; e->dev.area = (const float*)e->d_area.p;
     e->dev.nf = nf;
     float kf = (float)k; if (kf < 1e-12f) kf = 1e-12f;  // NF.normalize(ones(k), p=1)
     e->dev.emitter_pdf = 1.0f / kf;
     if (verts && cdf && k > 0) {                          // tables of sample_emitter (model/emitter.py:224-255)
         std::vector<int32_t> o2t((size_t)k);
         for (int64_t i = 0; i < nf; ++i) if (ord[(size_t)i] >= 0) o2t[(size_t)ord[(size_t)i]] = (int32_t)i;
-        HIP_TRY(hipMalloc(&e->d_verts, (size_t)k * 36));
-        HIP_TRY(hipMalloc(&e->d_cdf, (size_t)k * 4));
-        HIP_TRY(hipMalloc(&e->d_ord2tri, (size_t)k * 4));
-        HIP_TRY(hipMemcpy(e->d_verts, verts, (size_t)k * 36, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(e->d_cdf, cdf, (size_t)k * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(e->d_ord2tri, o2t.data(), (size_t)k * 4, hipMemcpyHostToDevice));
-        e->sample.cdf = (const float*)e->d_cdf; e->sample.verts = (const float*)e->d_verts; e->sample.area = (const float*)e->d_area;
-        e->sample.ord2tri = (const int32_t*)e->d_ord2tri; e->sample.k = k; e->sample.emitter_pdf = e->dev.emitter_pdf;
+        HIP_TRY(e->d_verts.alloc((size_t)k * 36));
+        HIP_TRY(e->d_cdf.alloc((size_t)k * 4));
+        HIP_TRY(e->d_ord2tri.alloc((size_t)k * 4));
+        HIP_TRY(e->d_verts.upload(verts, (size_t)k * 36));
+        HIP_TRY(e->d_cdf.upload(cdf, (size_t)k * 4));
+        HIP_TRY(e->d_ord2tri.upload(o2t.data(), (size_t)k * 4));
+        e->sample.cdf = (const float*)e->d_cdf.p; e->sample.verts = (const float*)e->d_verts.p; e->sample.area = (const float*)e->d_area.p;
+        e->sample.ord2tri = (const int32_t*)e->d_ord2tri.p; e->sample.k = k; e->sample.emitter_pdf = e->dev.emitter_pdf;
         e->can_sample = true;
     }
-    *out = e;
+    *out = e.release();
     return IRIS_OK;
     API_END
 }
-extern "C" IRIS_API void iris_emitter_destroy(iris_emitter* e) {
-    if (!e) return;
-    (void)hipFree(e->d_ord); (void)hipFree(e->d_rad); (void)hipFree(e->d_area);
-    (void)hipFree(e->d_verts); (void)hipFree(e->d_cdf); (void)hipFree(e->d_ord2tri);
-    for (const auto* v : {&e->fused, &e->retired}) for (const auto& f : *v) { (void)hipFree(f.d_tris); if (f.ready) (void)hipEventDestroy(f.ready); }
-    delete e;
-}
+extern "C" IRIS_API void iris_emitter_destroy(iris_emitter* e) { delete e; }      // (the fused and the retired tables go with it)
 
-__global__ void pad_rows_kernel(const float* __restrict__ src, float4* __restrict__ dst, int64_t n) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        dst[i] = make_float4(src[i * 3], src[i * 3 + 1], src[i * 3 + 2], 0.f);
-}
 extern "C" IRIS_API int iris_slf_set_radiance(iris_slf* s, const float* radiance_dev, int64_t kv, iris_stream_t stream) {
     if (!s || kv != s->kv || (kv > 0 && !radiance_dev)) return fail(IRIS_ERR_ARG, "iris_slf_set_radiance: bad arguments");
     if (kv == 0) return IRIS_OK;
-    hipLaunchKernelGGL(pad_rows_kernel, dim3(grid_for(kv, 256, 1024)), dim3(256), 0, (hipStream_t)stream, radiance_dev, (float4*)s->d_rad, kv);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(pad_rows_kernel, kv, 1024, stream, radiance_dev, (float4*)s->d_rad.p, kv);
 }
 extern "C" IRIS_API int iris_emitter_set_radiance(iris_emitter* e, const float* radiance_dev, int64_t n_rad, iris_stream_t stream) {
     if (!e || !radiance_dev || n_rad != e->n_rad) return fail(IRIS_ERR_ARG, "iris_emitter_set_radiance: bad arguments");
-    hipLaunchKernelGGL(pad_rows_kernel, dim3(grid_for(n_rad, 256, 1024)), dim3(256), 0, (hipStream_t)stream, radiance_dev, (float4*)e->d_rad, n_rad);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(pad_rows_kernel, n_rad, 1024, stream, radiance_dev, (float4*)e->d_rad.p, n_rad);
 }
 
 // ======================================================================================================
@@ -577,9 +499,7 @@ __global__ void raygen_kernel(RaygenArgs a, float* __restrict__ rays_o, float* _
 }
 static int raygen_launch(RaygenArgs a, float* o, float* d, float* dx, float* dy, iris_stream_t stream) {
     if (a.H <= 0 || a.W <= 0 || !o || !d || (a.ray_diff && (!dx || !dy))) return fail(IRIS_ERR_ARG, "iris_raygen: bad arguments");
-    hipLaunchKernelGGL(raygen_kernel, dim3(grid_for((int64_t)a.H * a.W, 256, 4096)), dim3(256), 0, (hipStream_t)stream, a, o, d, dx, dy);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(raygen_kernel, (int64_t)a.H * a.W, 4096, stream, a, o, d, dx, dy);
 }
 extern "C" IRIS_API int iris_raygen_real(const float K[9], const float c2w[12], int H, int W, int ray_diff, float* rays_o, float* rays_d,
                                 float* dxdu, float* dydv, iris_stream_t stream) {
@@ -634,15 +554,11 @@ extern "C" IRIS_API int iris_intersect(const iris_scene* s, const float* xs, con
                               int64_t* idx, uint8_t* valid, iris_stream_t stream) {
     if (!s || B < 0 || (B > 0 && (!xs || !ds))) return fail(IRIS_ERR_ARG, "iris_intersect: bad arguments");
     if (B == 0) return IRIS_OK;
-    if (s->dev.layout == kLayoutQ8 && joint_launch(B))
-        hipLaunchKernelGGL((intersect_kernel<kLayoutQ8, true>), dim3(grid_for(B, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, s->dev, xs, ds, B,
+    with_trace(s->dev, B, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((intersect_kernel<T::layout, T::joint>), dim3(grid_for(B, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, s->dev, xs, ds, B,
                            pos, nrm, uv, idx, valid);
-    else if (s->dev.layout == kLayoutQ8)
-        hipLaunchKernelGGL(intersect_kernel<kLayoutQ8>, dim3(grid_for(B, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, s->dev, xs, ds, B,
-                           pos, nrm, uv, idx, valid);
-    else
-        hipLaunchKernelGGL(intersect_kernel<kLayoutF32>, dim3(grid_for(B, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, s->dev, xs, ds, B,
-                           pos, nrm, uv, idx, valid);
+    });
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }
@@ -665,9 +581,7 @@ extern "C" IRIS_API int iris_sample_diffuse(const float* u2, const float* normal
                                    iris_stream_t stream) {
     if (B < 0 || (B > 0 && (!u2 || !normal || !wi))) return fail(IRIS_ERR_ARG, "iris_sample_diffuse: bad arguments");
     if (B == 0) return IRIS_OK;
-    hipLaunchKernelGGL(sample_diffuse_kernel, dim3(grid_for(B, 256, 8192)), dim3(256), 0, (hipStream_t)stream, u2, normal, B, wi, pdf, weight);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(sample_diffuse_kernel, B, 8192, stream, u2, normal, B, wi, pdf, weight);
 }
 
 __global__ void sample_specular_kernel(const float* __restrict__ u2, const float* __restrict__ wo, const float* __restrict__ normal,
@@ -689,19 +603,15 @@ extern "C" IRIS_API int iris_sample_specular(const float* u2, const float* wo, c
                                     float* pdf, float* w0, float* w1, iris_stream_t stream) {
     if (B < 0 || (B > 0 && (!u2 || !wo || !normal || !wi))) return fail(IRIS_ERR_ARG, "iris_sample_specular: bad arguments");
     if (B == 0) return IRIS_OK;
-    hipLaunchKernelGGL(sample_specular_kernel, dim3(grid_for(B, 256, 8192)), dim3(256), 0, (hipStream_t)stream, u2, wo, normal, roughness,
+    return launch1d(sample_specular_kernel, B, 8192, stream, u2, wo, normal, roughness,
                        (const float*)nullptr, B, wi, pdf, w0, w1);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
 }
 extern "C" IRIS_API int iris_sample_specular_v(const float* u2, const float* wo, const float* normal, const float* roughness, int64_t B, float* wi,
                                       float* pdf, float* w0, float* w1, iris_stream_t stream) {
     if (B < 0 || (B > 0 && (!u2 || !wo || !normal || !roughness || !wi))) return fail(IRIS_ERR_ARG, "iris_sample_specular_v: bad arguments");
     if (B == 0) return IRIS_OK;
-    hipLaunchKernelGGL(sample_specular_kernel, dim3(grid_for(B, 256, 8192)), dim3(256), 0, (hipStream_t)stream, u2, wo, normal, 0.f, roughness, B,
+    return launch1d(sample_specular_kernel, B, 8192, stream, u2, wo, normal, 0.f, roughness, B,
                        wi, pdf, w0, w1);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
 }
 
 __global__ void slf_lookup_kernel(SlfDev s, const float* __restrict__ x, int64_t B, int64_t* __restrict__ idx, float* __restrict__ rgb) {
@@ -719,9 +629,7 @@ __global__ void slf_lookup_kernel(SlfDev s, const float* __restrict__ x, int64_t
 extern "C" IRIS_API int iris_slf_lookup(const iris_slf* s, const float* x, int64_t B, int64_t* idx, float* rgb, iris_stream_t stream) {
     if (!s || B < 0 || (B > 0 && !x)) return fail(IRIS_ERR_ARG, "iris_slf_lookup: bad arguments");
     if (B == 0) return IRIS_OK;
-    hipLaunchKernelGGL(slf_lookup_kernel, dim3(grid_for(B, 256, 8192)), dim3(256), 0, (hipStream_t)stream, s->dev, x, B, idx, rgb);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(slf_lookup_kernel, B, 8192, stream, s->dev, x, B, idx, rgb);
 }
 
 __global__ void eval_emitter_kernel(EmitDev e, SlfDev s, const float* __restrict__ pos, const int64_t* __restrict__ tri,
@@ -740,10 +648,8 @@ extern "C" IRIS_API int iris_eval_emitter(const iris_emitter* e, const iris_slf*
                                  uint8_t* valid_next, iris_stream_t stream) {
     if (!e || !s || B < 0 || (B > 0 && (!position || !triangle_idx || !Le))) return fail(IRIS_ERR_ARG, "iris_eval_emitter: bad arguments");
     if (B == 0) return IRIS_OK;
-    hipLaunchKernelGGL(eval_emitter_kernel, dim3(grid_for(B, 256, 8192)), dim3(256), 0, (hipStream_t)stream, e->dev, s->dev, position,
+    return launch1d(eval_emitter_kernel, B, 8192, stream, e->dev, s->dev, position,
                        triangle_idx, roughness, trace_roughness, B, Le, emit_pdf, valid_next);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
 }
 
 __global__ void lerp_specular_kernel(const float* __restrict__ spec, const float* __restrict__ rough, int64_t B, int R, float* __restrict__ out) {
@@ -757,9 +663,7 @@ __global__ void lerp_specular_kernel(const float* __restrict__ spec, const float
 extern "C" IRIS_API int iris_lerp_specular(const float* specular, const float* roughness, int64_t B, int R, float* out, iris_stream_t stream) {
     if (B < 0 || R < 1 || (B > 0 && (!specular || !roughness || !out))) return fail(IRIS_ERR_ARG, "iris_lerp_specular: bad arguments");
     if (B == 0) return IRIS_OK;
-    hipLaunchKernelGGL(lerp_specular_kernel, dim3(grid_for(B, 256, 8192)), dim3(256), 0, (hipStream_t)stream, specular, roughness, B, R, out);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(lerp_specular_kernel, B, 8192, stream, specular, roughness, B, R, out);
 }
 
 // ---- multi-GPU: the gathered stripes of a view back into image order (iris_amd/sharding.py; the reference is single-GPU, bake_shading.py:41).
@@ -786,9 +690,7 @@ extern "C" IRIS_API int iris_unstripe_maps(const float* gathered, int world, int
     const int64_t total = (int64_t)H * W * n_maps * 3;
     if (total == 0) return IRIS_OK;
     if (!gathered || !full) return fail(IRIS_ERR_ARG, "iris_unstripe_maps: null pointer");
-    hipLaunchKernelGGL(unstripe_maps_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, (hipStream_t)stream, gathered, world, n_maps, n_max, H, W, stripe_rows, full);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(unstripe_maps_kernel, total, 16384, stream, gathered, world, n_maps, n_max, H, W, stripe_rows, full);
 }
 
 // ---- the small helpers of utils/ops.py as calls of their own (inside the bake / path-tracing kernels the same device functions are fused)
@@ -831,32 +733,24 @@ __global__ void ggx_terms_kernel(int op, const float* a, const float* b, const f
 extern "C" IRIS_API int iris_get_normal_space(const float* normal, int64_t B, float* out, iris_stream_t stream) {
     if (B < 0 || (B > 0 && (!normal || !out))) return fail(IRIS_ERR_ARG, "iris_get_normal_space: bad arguments");
     if (B == 0) return IRIS_OK;
-    hipLaunchKernelGGL(normal_space_kernel, dim3(grid_for(B, 256, 8192)), dim3(256), 0, (hipStream_t)stream, normal, B, out);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(normal_space_kernel, B, 8192, stream, normal, B, out);
 }
 extern "C" IRIS_API int iris_double_sided(const float* V, float* N, int64_t B, iris_stream_t stream) {
     if (B < 0 || (B > 0 && (!V || !N))) return fail(IRIS_ERR_ARG, "iris_double_sided: bad arguments");
     if (B == 0) return IRIS_OK;
-    hipLaunchKernelGGL(double_sided_kernel, dim3(grid_for(B, 256, 8192)), dim3(256), 0, (hipStream_t)stream, V, N, B);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(double_sided_kernel, B, 8192, stream, V, N, B);
 }
 extern "C" IRIS_API int iris_angle2xyz(const float* theta, const float* phi, int64_t B, float* out, iris_stream_t stream) {
     if (B < 0 || (B > 0 && (!theta || !phi || !out))) return fail(IRIS_ERR_ARG, "iris_angle2xyz: bad arguments");
     if (B == 0) return IRIS_OK;
-    hipLaunchKernelGGL(angle2xyz_kernel, dim3(grid_for(B, 256, 8192)), dim3(256), 0, (hipStream_t)stream, theta, phi, B, out);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(angle2xyz_kernel, B, 8192, stream, theta, phi, B, out);
 }
 extern "C" IRIS_API int iris_ggx_terms(int op, const float* a, const float* b, const float* c, int64_t B, float* out, float* out2, iris_stream_t stream) {
     const bool need_b = op != 4, need_c = op == 2, need_2 = op == 4;
     if (op < 0 || op > 4 || B < 0 || (B > 0 && (!a || !out || (need_b && !b) || (need_c && !c) || (need_2 && !out2))))
         return fail(IRIS_ERR_ARG, "iris_ggx_terms: bad arguments");
     if (B == 0) return IRIS_OK;
-    hipLaunchKernelGGL(ggx_terms_kernel, dim3(grid_for(B, 256, 8192)), dim3(256), 0, (hipStream_t)stream, op, a, b, c, B, out, out2);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(ggx_terms_kernel, B, 8192, stream, op, a, b, c, B, out, out2);
 }
 
 // ---- 8(f)-3: packed shading cache + shading combine (iris_cache.h)
@@ -871,26 +765,20 @@ extern "C" IRIS_API int iris_cache_pack(const float* diffuse, const float* const
         if (!spec0[j] || !spec1[j]) return fail(IRIS_ERR_ARG, "iris_cache_pack: null map");
         m.s0[j] = spec0[j]; m.s1[j] = spec1[j];
     }
-    hipLaunchKernelGGL(cache_pack_kernel, dim3(grid_for(n * (cache_row_floats(R) / 4), 256, 16384)), dim3(256), 0, (hipStream_t)stream, m, n, R, rows);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(cache_pack_kernel, n * (cache_row_floats(R) / 4), 16384, stream, m, n, R, rows);
 }
 extern "C" IRIS_API int iris_cache_gather(const float* rows, const int64_t* idx, int64_t B, int R, float* out, iris_stream_t stream) {
     if (B < 0 || R < 1 || R > kMaxLevels || (B > 0 && (!rows || !out))) return fail(IRIS_ERR_ARG, "iris_cache_gather: bad arguments");
     if (B == 0) return IRIS_OK;
-    hipLaunchKernelGGL(cache_gather_kernel, dim3(grid_for(B * (3 + 6 * R), 256, 16384)), dim3(256), 0, (hipStream_t)stream, rows, idx, B, R, out);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(cache_gather_kernel, B * (3 + 6 * R), 16384, stream, rows, idx, B, R, out);
 }
 extern "C" IRIS_API int iris_shade_cached_fwd(const float* rows, const int64_t* idx, const float* albedo, const float* metallic,
                                               const float* roughness, int64_t B, int R, float* L, iris_stream_t stream) {
     if (B < 0 || R < 1 || R > kMaxLevels || (B > 0 && (!rows || !albedo || !metallic || !roughness || !L)))
         return fail(IRIS_ERR_ARG, "iris_shade_cached_fwd: bad arguments");
     if (B == 0) return IRIS_OK;
-    hipLaunchKernelGGL(shade_cached_fwd_kernel, dim3(grid_for(B, 256, 16384)), dim3(256), 0, (hipStream_t)stream, rows, idx, albedo, metallic,
+    return launch1d(shade_cached_fwd_kernel, B, 16384, stream, rows, idx, albedo, metallic,
                        roughness, B, R, L);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
 }
 extern "C" IRIS_API int iris_shade_cached_bwd(const float* rows, const int64_t* idx, const float* albedo, const float* metallic,
                                               const float* roughness, const float* gL, int64_t B, int R, float* g_albedo, float* g_metallic,
@@ -898,10 +786,8 @@ extern "C" IRIS_API int iris_shade_cached_bwd(const float* rows, const int64_t* 
     if (B < 0 || R < 1 || R > kMaxLevels || (B > 0 && (!rows || !albedo || !metallic || !roughness || !gL)))
         return fail(IRIS_ERR_ARG, "iris_shade_cached_bwd: bad arguments");
     if (B == 0) return IRIS_OK;
-    hipLaunchKernelGGL(shade_cached_bwd_kernel, dim3(grid_for(B, 256, 16384)), dim3(256), 0, (hipStream_t)stream, rows, idx, albedo, metallic,
+    return launch1d(shade_cached_bwd_kernel, B, 16384, stream, rows, idx, albedo, metallic,
                        roughness, gL, B, R, g_albedo, g_metallic, g_roughness);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
 }
 
 // ---- 8(f)-4: denoiser substitute (iris_denoise.h)
@@ -962,9 +848,7 @@ __global__ void philox_kernel(uint64_t seed, uint64_t idx0, uint32_t stream_id, 
 extern "C" IRIS_API int iris_philox_u2(uint64_t seed, uint64_t idx0, uint32_t stream_id, int64_t n, float* u2, iris_stream_t stream) {
     if (n < 0 || (n > 0 && !u2)) return fail(IRIS_ERR_ARG, "iris_philox_u2: bad arguments");
     if (n == 0) return IRIS_OK;
-    hipLaunchKernelGGL(philox_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, seed, idx0, stream_id, n, u2);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(philox_kernel, n, 8192, stream, seed, idx0, stream_id, n, u2);
 }
 
 // ======================================================================================================
@@ -985,9 +869,8 @@ static int tile_pixels(int spp) {
 #define IRIS_TILE_GRID IRIS_TILE_WAVES
 #endif
 static int bake_grid_blocks() { return num_cus() * IRIS_TILE_GRID; }  // resident 256-thread workgroups per CU (VGPR- and LDS-bound)
-static int view_grid_blocks() { return bake_grid_blocks(); }
 static uint64_t stack_ovf_bytes() {
-    return (uint64_t)std::max(bake_grid_blocks(), view_grid_blocks()) * (kStackCapacity - IRIS_TILE_STACK) * kBlock * sizeof(uint32_t);
+    return (uint64_t)bake_grid_blocks() * (kStackCapacity - IRIS_TILE_STACK) * kBlock * sizeof(uint32_t);
 }
 
 extern "C" IRIS_API int iris_bake_tile_max_spp(void) { return kTileRays; }
@@ -996,7 +879,7 @@ extern "C" IRIS_API uint64_t iris_bake_workspace_bytes(int64_t P, int spp, int s
     // [256 B counters][blocks x kTileRays x (16|32) B per-ray slots]
     // (packing the pixel tensors into 48-B records was measured 7 % SLOWER than reading pos/nrm/wo directly: not done)
     // + [blocks x (96 - LDS depth) x 256 dwords: traversal-stack entries beyond the LDS part]   (specular sizing also serves iris_bake_view)
-    const uint64_t blocks = (uint64_t)std::max(bake_grid_blocks(), view_grid_blocks());
+    const uint64_t blocks = (uint64_t)bake_grid_blocks();
     return 256 + blocks * kTileRays * (specular ? 2 : 1) * sizeof(float4) + stack_ovf_bytes();
 }
 
@@ -1037,27 +920,18 @@ static int bake_launch(bool spec, const iris_scene* sc, const iris_emitter* em, 
         if (const float4* ft = fused_tris(sc, em, st)) { a.sc.tris = ft; a.em.emit_ord = nullptr; }      // (tile kernels only: their shading pass reads the ordinal from the record)
         const int64_t n_tiles = (P + tile_px - 1) / tile_px;
         const int grid = (int)std::min<int64_t>(blocks, n_tiles);
-#define IRIS_LAUNCH_BAKE(KERNEL, GRID)                                                                                            \
-    do {                                                                                                                         \
-        const bool q8 = a.sc.layout == kLayoutQ8;                                                                                \
-        if (stats) {                                                                                                             \
-            if (spec) { if (q8) hipLaunchKernelGGL((KERNEL<true, true, kLayoutQ8>), dim3(GRID), dim3(kBlock), 0, st, a);          \
-                        else hipLaunchKernelGGL((KERNEL<true, true, kLayoutF32>), dim3(GRID), dim3(kBlock), 0, st, a); }          \
-            else      { if (q8) hipLaunchKernelGGL((KERNEL<false, true, kLayoutQ8>), dim3(GRID), dim3(kBlock), 0, st, a);         \
-                        else hipLaunchKernelGGL((KERNEL<false, true, kLayoutF32>), dim3(GRID), dim3(kBlock), 0, st, a); }         \
-        } else {                                                                                                                 \
-            if (spec) { if (q8) hipLaunchKernelGGL((KERNEL<true, false, kLayoutQ8>), dim3(GRID), dim3(kBlock), 0, st, a);         \
-                        else hipLaunchKernelGGL((KERNEL<true, false, kLayoutF32>), dim3(GRID), dim3(kBlock), 0, st, a); }         \
-            else      { if (q8) hipLaunchKernelGGL((KERNEL<false, false, kLayoutQ8>), dim3(GRID), dim3(kBlock), 0, st, a);        \
-                        else hipLaunchKernelGGL((KERNEL<false, false, kLayoutF32>), dim3(GRID), dim3(kBlock), 0, st, a); }        \
-        }                                                                                                                        \
-    } while (0)
-        IRIS_LAUNCH_BAKE(bake_tile_kernel, grid);
+        with_bake(spec, stats != nullptr, a.sc, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((bake_tile_kernel<T::spec, T::stats, T::layout>), dim3(grid), dim3(kBlock), 0, st, a);
+        });
     } else {
         const int ppw = (spp < 64 && (spp & (spp - 1)) == 0) ? 64 / spp : 1;
         const int64_t n_groups = (P + ppw - 1) / ppw;
         const int grid = grid_for(n_groups * 64, kBlock, num_cus() * 6);
-        IRIS_LAUNCH_BAKE(bake_kernel, grid);
+        with_bake(spec, stats != nullptr, a.sc, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((bake_kernel<T::spec, T::stats, T::layout>), dim3(grid), dim3(kBlock), 0, st, a);
+        });
     }
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
@@ -1079,25 +953,25 @@ static const float4* fused_tris(const iris_scene* sc, const iris_emitter* em, hi
         // the table is filled by a kernel on the stream of the call that built it: a call on another stream waits for that kernel ON THE DEVICE (no host
         // synchronisation inside a bake call -- legal under stream capture) until the event has been seen complete once
         if (!f.done) {
-            if (hipEventQuery(f.ready) == hipSuccess) f.done = true;
-            else { (void)hipGetLastError(); if (hipStreamWaitEvent(st, f.ready, 0) != hipSuccess) { (void)hipGetLastError(); return nullptr; } }
+            if (hipEventQuery(f.ready.ev) == hipSuccess) f.done = true;
+            else { (void)hipGetLastError(); if (hipStreamWaitEvent(st, f.ready.ev, 0) != hipSuccess) { (void)hipGetLastError(); return nullptr; } }
         }
-        return (const float4*)f.d_tris;
+        return (const float4*)f.d_tris.p;
     }
-    if (em->fused.size() >= 2) { em->retired.push_back(em->fused.front()); em->fused.erase(em->fused.begin()); }      // (a training loop uses one scene: the live set stays at two)
+    if (em->fused.size() >= 2) { em->retired.push_back(std::move(em->fused.front())); em->fused.erase(em->fused.begin()); }      // (a training loop uses one scene: the live set stays at two)
     int prev = 0;
     if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(sc->device) != hipSuccess) { (void)hipGetLastError(); return nullptr; }     // allocate where the scene lives, whatever the caller's current device
-    void* d = nullptr; hipEvent_t ev = nullptr;
+    DevBuf d; DevEvent ev;
     const int64_t n_rec = (int64_t)sc->dev.n_tris + 1;
-    bool ok = hipMalloc(&d, (size_t)n_rec * 64) == hipSuccess && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+    bool ok = d.alloc((size_t)n_rec * kLeafRecordBytes) == hipSuccess && ev.create() == hipSuccess;
     if (ok) {
-        hipLaunchKernelGGL(fuse_ord_kernel, dim3(grid_for(n_rec, 256, 4096)), dim3(256), 0, st, sc->dev.tris, em->dev.emit_ord, n_rec, (float4*)d);
-        ok = hipGetLastError() == hipSuccess && hipEventRecord(ev, st) == hipSuccess;
+        hipLaunchKernelGGL(fuse_ord_kernel, dim3(grid_for(n_rec, 256, 4096)), dim3(256), 0, st, sc->dev.tris, em->dev.emit_ord, n_rec, (float4*)d.p);
+        ok = hipGetLastError() == hipSuccess && hipEventRecord(ev.ev, st) == hipSuccess;
     }
     (void)hipSetDevice(prev);
-    if (!ok) { (void)hipGetLastError(); if (d) (void)hipFree(d); if (ev) (void)hipEventDestroy(ev); return nullptr; }
-    em->fused.push_back({sc->uid, d, ev, false});
-    return (const float4*)d;            // (this call's own launch follows the fill on the same stream)
+    if (!ok) { (void)hipGetLastError(); return nullptr; }
+    em->fused.push_back({sc->uid, std::move(d), std::move(ev), false});
+    return (const float4*)em->fused.back().d_tris.p;            // (this call's own launch follows the fill on the same stream)
 }
 extern "C" IRIS_API int iris_bake_view(const iris_scene* sc, const iris_emitter* em, const iris_slf* slf, const float* pos, const float* nrm,
                               const float* wo, const int32_t* pix_id, int64_t P, int n_lobes, const float* roughness, const int32_t* spp,
@@ -1119,7 +993,7 @@ extern "C" IRIS_API int iris_bake_view(const iris_scene* sc, const iris_emitter*
     v.base.scratch = (float4*)((char*)workspace + 256);
     v.base.stack_ovf = (uint32_t*)((char*)workspace + need - stack_ovf_bytes());
     v.n_lobes = n_lobes;
-    const int blocks = view_grid_blocks();
+    const int blocks = bake_grid_blocks();
     long long t = 0;
     int tile_px_min = kTileRays;
     for (int l = 0; l < n_lobes; ++l) {
@@ -1142,8 +1016,7 @@ extern "C" IRIS_API int iris_bake_view(const iris_scene* sc, const iris_emitter*
     v.n_tiles = ((n_spans + 7) / 8) * 8 * n_lobes * kTileChunk;
     HIP_TRY(hipMemsetAsync(workspace, 0, 256, st));
     const int grid = (int)std::min<long long>(blocks, t);
-    if (v.base.sc.layout == kLayoutQ8) hipLaunchKernelGGL(bake_view_kernel<kLayoutQ8>, dim3(grid), dim3(kBlock), 0, st, v);
-    else hipLaunchKernelGGL(bake_view_kernel<kLayoutF32>, dim3(grid), dim3(kBlock), 0, st, v);
+    with_layout(v.base.sc, [&](auto t) { hipLaunchKernelGGL(bake_view_kernel<decltype(t)::layout>, dim3(grid), dim3(kBlock), 0, st, v); });
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }
@@ -1201,26 +1074,18 @@ static bool pt_tiling(int64_t N, int& tile_rays, int& grid) {
     grid = (int)std::min<int64_t>(blocks, (N + tile_rays - 1) / tile_rays);
     return true;
 }
-#define LAUNCH1D(kernel, n, st, ...)                                                                          \
-    do {                                                                                                      \
-        hipLaunchKernelGGL(kernel, dim3(grid_for((n), 256, 8192)), dim3(256), 0, (hipStream_t)(st), __VA_ARGS__); \
-        HIP_TRY(hipGetLastError());                                                                           \
-    } while (0)
-
 extern "C" IRIS_API int iris_sample_emitter(const iris_emitter* e, const float* s1, const float* s2, const float* position, int64_t N, float* wi,
                                    float* pdf, int64_t* tri, iris_stream_t stream) {
     if (!e || !e->can_sample) return fail(IRIS_ERR_ARG, "iris_sample_emitter: emitter was created without vertices / cdf");
     if (N < 0 || (N > 0 && (!s1 || !s2 || !position || !wi || !pdf || !tri))) return fail(IRIS_ERR_ARG, "iris_sample_emitter: bad arguments");
     if (N == 0) return IRIS_OK;
-    LAUNCH1D(sample_emitter_kernel, N, stream, e->sample, s1, s2, position, N, wi, pdf, tri);
-    return IRIS_OK;
+    return launch1d(sample_emitter_kernel, N, 8192, stream, e->sample, s1, s2, position, N, wi, pdf, tri);
 }
 extern "C" IRIS_API int iris_eval_brdf(const float* wi, const float* wo, const float* normal, const float* albedo, const float* roughness,
                               const float* metallic, int64_t N, float* brdf, float* pdf, iris_stream_t stream) {
     if (N < 0 || (N > 0 && (!wi || !wo || !normal || !albedo || !roughness || !metallic || !brdf || !pdf))) return fail(IRIS_ERR_ARG, "iris_eval_brdf: bad arguments");
     if (N == 0) return IRIS_OK;
-    LAUNCH1D(eval_brdf_kernel, N, stream, wi, wo, normal, albedo, roughness, metallic, N, brdf, pdf);
-    return IRIS_OK;
+    return launch1d(eval_brdf_kernel, N, 8192, stream, wi, wo, normal, albedo, roughness, metallic, N, brdf, pdf);
 }
 extern "C" IRIS_API int iris_sample_brdf(const float* s1, const float* s2, const float* wo, const float* normal, const float* albedo,
                                 const float* roughness, const float* metallic, int64_t N, float* wi, float* pdf, float* weight,
@@ -1228,15 +1093,13 @@ extern "C" IRIS_API int iris_sample_brdf(const float* s1, const float* s2, const
     if (N < 0 || (N > 0 && (!s1 || !s2 || !wo || !normal || !albedo || !roughness || !metallic || !wi || !pdf || !weight)))
         return fail(IRIS_ERR_ARG, "iris_sample_brdf: bad arguments");
     if (N == 0) return IRIS_OK;
-    LAUNCH1D(sample_brdf_kernel, N, stream, s1, s2, wo, normal, albedo, roughness, metallic, N, wi, pdf, weight);
-    return IRIS_OK;
+    return launch1d(sample_brdf_kernel, N, 8192, stream, s1, s2, wo, normal, albedo, roughness, metallic, N, wi, pdf, weight);
 }
 extern "C" IRIS_API int iris_pt_jitter(const float* rays_d, const float* dxdu, const float* dydv, const float* dudv, int64_t B, int spp, float* wi,
                               iris_stream_t stream) {
     if (B < 0 || spp < 1 || (B > 0 && (!rays_d || !dxdu || !dydv || !dudv || !wi))) return fail(IRIS_ERR_ARG, "iris_pt_jitter: bad arguments");
     if (B == 0) return IRIS_OK;
-    LAUNCH1D(pt_jitter_kernel, B * spp, stream, rays_d, dxdu, dydv, dudv, B, spp, wi);
-    return IRIS_OK;
+    return launch1d(pt_jitter_kernel, B * spp, 8192, stream, rays_d, dxdu, dydv, dudv, B, spp, wi);
 }
 __global__ void pt_primary_emit_kernel(EmitDev e, const int64_t* __restrict__ tri, int64_t N, int32_t* __restrict__ e0, uint8_t* __restrict__ valid_next) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
@@ -1249,8 +1112,7 @@ __global__ void pt_primary_emit_kernel(EmitDev e, const int64_t* __restrict__ tr
 extern "C" IRIS_API int iris_pt_primary_emit(const iris_emitter* e, const int64_t* tri, int64_t N, int32_t* e0, uint8_t* valid_next, iris_stream_t stream) {
     if (!e || N < 0 || (N > 0 && (!tri || !e0 || !valid_next))) return fail(IRIS_ERR_ARG, "iris_pt_primary_emit: bad arguments");
     if (N == 0) return IRIS_OK;
-    LAUNCH1D(pt_primary_emit_kernel, N, stream, e->dev, tri, N, e0, valid_next);
-    return IRIS_OK;
+    return launch1d(pt_primary_emit_kernel, N, 8192, stream, e->dev, tri, N, e0, valid_next);
 }
 // The head of path_tracing_single's un-compacted mode as ONE launch (round 5): :338-340 jitter -> :343 ray_intersect(rays_o.repeat_interleave(spp), wi) -> :344 the primary hit's
 // emitter ordinal -> which paths continue (path_of) -> wo = -wi.  The same arithmetic as iris_pt_jitter + iris_intersect + iris_pt_primary_emit and the torch glue between them
@@ -1296,12 +1158,10 @@ extern "C" IRIS_API int iris_pt_primary(const iris_scene* sc, const iris_emitter
     if (e->dev.nf != sc->info.n_triangles) return fail(IRIS_ERR_ARG, "iris_pt_primary: the emitter tables are for a mesh of another size than the scene's");
     const int64_t N = B * spp;
     const dim3 grid(grid_for(N, kBlock, num_cus() * 6));
-    if (sc->dev.layout == kLayoutQ8 && joint_launch(N))
-        hipLaunchKernelGGL((pt_primary_kernel<kLayoutQ8, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, sc->dev, e->dev, rays_o, rays_d, dxdu, dydv, dudv, B, spp, wi, wo, pos, nrm, e0, valid_next, path_of);
-    else if (sc->dev.layout == kLayoutQ8)
-        hipLaunchKernelGGL((pt_primary_kernel<kLayoutQ8, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, sc->dev, e->dev, rays_o, rays_d, dxdu, dydv, dudv, B, spp, wi, wo, pos, nrm, e0, valid_next, path_of);
-    else
-        hipLaunchKernelGGL((pt_primary_kernel<kLayoutF32, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, sc->dev, e->dev, rays_o, rays_d, dxdu, dydv, dudv, B, spp, wi, wo, pos, nrm, e0, valid_next, path_of);
+    with_trace(sc->dev, N, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pt_primary_kernel<T::layout, T::joint>), grid, dim3(kBlock), 0, (hipStream_t)stream, sc->dev, e->dev, rays_o, rays_d, dxdu, dydv, dudv, B, spp, wi, wo, pos, nrm, e0, valid_next, path_of);
+    });
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }
@@ -1316,12 +1176,13 @@ extern "C" IRIS_API int iris_pt_nee(const iris_scene* sc, const iris_emitter* e,
     a.pos = pos; a.nrm = nrm; a.wo = wo; a.albedo = albedo; a.rough = roughness; a.metal = metallic; a.s1 = s1; a.s2 = s2;
     a.coef1 = coef1; a.e1 = e1; a.g_eps = g_eps; a.pdf_eps = pdf_eps; a.mis_eps = mis_eps;
     int tile_rays, grid;
-    if (pt_tiling(N, tile_rays, grid)) {
-        if (a.sc.layout == kLayoutQ8) hipLaunchKernelGGL((pt_tiled_kernel<kLayoutQ8, true>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a, tile_rays);
-        else hipLaunchKernelGGL((pt_tiled_kernel<kLayoutF32, true>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a, tile_rays);
-    } else if (a.sc.layout == kLayoutQ8 && joint_launch(N)) hipLaunchKernelGGL((pt_nee_kernel<kLayoutQ8, true>), dim3(grid_for(N, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, a);
-    else if (a.sc.layout == kLayoutQ8) hipLaunchKernelGGL(pt_nee_kernel<kLayoutQ8>, dim3(grid_for(N, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(pt_nee_kernel<kLayoutF32>, dim3(grid_for(N, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, a);
+    if (pt_tiling(N, tile_rays, grid))
+        with_layout(a.sc, [&](auto t) { hipLaunchKernelGGL((pt_tiled_kernel<decltype(t)::layout, true>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a, tile_rays); });
+    else
+        with_trace(a.sc, N, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((pt_nee_kernel<T::layout, T::joint>), dim3(grid_for(N, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, a);
+        });
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }
@@ -1340,12 +1201,13 @@ extern "C" IRIS_API int iris_pt_brdf_trace(const iris_scene* sc, const float* po
     a.wi_out = wi; a.brdf_pdf = pdf; a.brdf_w = weight; a.pos_next = pos_next; a.nrm_next = nrm_next; a.tri_next = tri_next; a.valid_next_hit = valid;
     a.lobe = lobe; a.lobe_rough = lobe_roughness;
     int tile_rays, grid;
-    if (pt_tiling(N, tile_rays, grid)) {
-        if (a.sc.layout == kLayoutQ8) hipLaunchKernelGGL((pt_tiled_kernel<kLayoutQ8, false>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a, tile_rays);
-        else hipLaunchKernelGGL((pt_tiled_kernel<kLayoutF32, false>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a, tile_rays);
-    } else if (a.sc.layout == kLayoutQ8 && joint_launch(N)) hipLaunchKernelGGL((pt_brdf_trace_kernel<kLayoutQ8, true>), dim3(grid_for(N, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, a);
-    else if (a.sc.layout == kLayoutQ8) hipLaunchKernelGGL(pt_brdf_trace_kernel<kLayoutQ8>, dim3(grid_for(N, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(pt_brdf_trace_kernel<kLayoutF32>, dim3(grid_for(N, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, a);
+    if (pt_tiling(N, tile_rays, grid))
+        with_layout(a.sc, [&](auto t) { hipLaunchKernelGGL((pt_tiled_kernel<decltype(t)::layout, false>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, a, tile_rays); });
+    else
+        with_trace(a.sc, N, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((pt_brdf_trace_kernel<T::layout, T::joint>), dim3(grid_for(N, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, a);
+        });
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }
@@ -1377,8 +1239,7 @@ extern "C" IRIS_API int iris_pt_bounce(const iris_scene* sc, const iris_emitter*
     const int tile_paths = std::max(kBlock / 2, tile_rays / 2);
     const int64_t n_tiles = (N + tile_paths - 1) / tile_paths;
     const int g2 = (int)std::min<int64_t>((int64_t)num_cus() * IRIS_PT_WAVES, n_tiles);
-    if (a.sc.layout == kLayoutQ8) hipLaunchKernelGGL((pt_bounce_kernel<kLayoutQ8>), dim3(g2), dim3(kBlock), 0, (hipStream_t)stream, a, tile_paths);
-    else hipLaunchKernelGGL((pt_bounce_kernel<kLayoutF32>), dim3(g2), dim3(kBlock), 0, (hipStream_t)stream, a, tile_paths);
+    with_layout(a.sc, [&](auto t) { hipLaunchKernelGGL((pt_bounce_kernel<decltype(t)::layout>), dim3(g2), dim3(kBlock), 0, (hipStream_t)stream, a, tile_paths); });
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }
@@ -1393,8 +1254,7 @@ extern "C" IRIS_API int iris_pt_brdf_finish(const iris_emitter* e, const iris_sl
     a.em = e->dev; a.slf = slf->dev; a.N = N;
     a.pos = pos; a.pos_n_in = pos_next; a.nrm_n_in = nrm_next; a.wi_in = wi; a.tri_n_in = tri_next; a.rough_next = roughness_next; a.pdf_in = pdf; a.w_in = weight;
     a.coef2 = coef2; a.const2 = const2; a.e2 = e2; a.valid_next_hit = valid_next; a.trace_rough = trace_roughness; a.g_eps = g_eps;
-    LAUNCH1D(pt_brdf_finish_kernel, N, stream, a);
-    return IRIS_OK;
+    return launch1d(pt_brdf_finish_kernel, N, 8192, stream, a);
 }
 extern "C" IRIS_API int iris_pt_accumulate_fwd(const float* radiance, const int32_t* e0, const int32_t* path_of, const int32_t* e1, const float* coef1,
                                       const int32_t* e2, const float* coef2, const float* const2, int64_t B, int spp, float* L,
@@ -1404,24 +1264,20 @@ extern "C" IRIS_API int iris_pt_accumulate_fwd(const float* radiance, const int3
     int lpp = 1;
     while (lpp < spp && lpp < 64) lpp <<= 1;                     // lanes per pixel: min(64, next power of two >= spp)
     const int64_t n_groups = (B + 64 / lpp - 1) / (64 / lpp);    // one wave per group of 64 / lpp pixels
-    hipLaunchKernelGGL(pt_accumulate_fwd_kernel, dim3(grid_for(n_groups * 64, 256, 8192)), dim3(256), 0, (hipStream_t)stream, radiance, e0, path_of, e1, coef1, e2, coef2, const2, B, spp, lpp, L);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return launch1d(pt_accumulate_fwd_kernel, n_groups * 64, 8192, stream, radiance, e0, path_of, e1, coef1, e2, coef2, const2, B, spp, lpp, L);
 }
 extern "C" IRIS_API int iris_pt_accumulate_bwd(const float* gL, const int32_t* e0, const int32_t* path_of, const int32_t* e1, const float* coef1,
                                       const int32_t* e2, const float* coef2, int64_t B, int spp, float* g_radiance, iris_stream_t stream) {
     if (B < 0 || spp < 1 || (B > 0 && (!gL || !e0 || !path_of || !g_radiance))) return fail(IRIS_ERR_ARG, "iris_pt_accumulate_bwd: bad arguments");
     if (B == 0) return IRIS_OK;
-    LAUNCH1D(pt_accumulate_bwd_kernel, B * spp, stream, gL, e0, path_of, e1, coef1, e2, coef2, B, spp, g_radiance);
-    return IRIS_OK;
+    return launch1d(pt_accumulate_bwd_kernel, B * spp, 8192, stream, gL, e0, path_of, e1, coef1, e2, coef2, B, spp, g_radiance);
 }
 
 extern "C" IRIS_API int iris_pt_apply(float* L, const int32_t* rows, float* throughput, const float* radiance, const int32_t* e, const float* coef,
                              const float* cst, const float* weight, int64_t N, int nan_to_zero, iris_stream_t stream) {
     if (N < 0 || (N > 0 && (!L || (e && (!radiance || !coef))))) return fail(IRIS_ERR_ARG, "iris_pt_apply: bad arguments");
     if (N == 0) return IRIS_OK;
-    LAUNCH1D(pt_apply_kernel, N, stream, L, rows, throughput, radiance, e, coef, cst, weight, N, nan_to_zero);
-    return IRIS_OK;
+    return launch1d(pt_apply_kernel, N, 8192, stream, L, rows, throughput, radiance, e, coef, cst, weight, N, nan_to_zero);
 }
 
 extern "C" IRIS_API uint64_t iris_pt_compact_workspace_bytes(int64_t N) {
@@ -1515,8 +1371,7 @@ extern "C" IRIS_API int iris_slf_scatter_add(const iris_slf* s, const float* x, 
                                     iris_stream_t stream) {
     if (!s || B < 0 || (B > 0 && (!x || !rgb || !radiance_acc || !count))) return fail(IRIS_ERR_ARG, "iris_slf_scatter_add: bad arguments");
     if (B == 0) return IRIS_OK;
-    LAUNCH1D(slf_scatter_add_kernel, B, stream, s->dev, x, rgb, B, radiance_acc, (unsigned long long*)count);
-    return IRIS_OK;
+    return launch1d(slf_scatter_add_kernel, B, 8192, stream, s->dev, x, rgb, B, radiance_acc, (unsigned long long*)count);
 }
 // slf_bake.py:104-110: occupancy histogram of the voxel grid, hist[x + y*H + z*H*H] += 1 (float counts, exact below 2^24)
 __global__ void voxel_histogram_kernel(const float* __restrict__ x, int64_t B, float vmin, float den, int H, float* __restrict__ hist) {
@@ -1529,8 +1384,7 @@ __global__ void voxel_histogram_kernel(const float* __restrict__ x, int64_t B, f
 extern "C" IRIS_API int iris_voxel_histogram(const float* x, int64_t B, double voxel_min, double voxel_max, int H, float* hist, iris_stream_t stream) {
     if (B < 0 || H <= 0 || (B > 0 && (!x || !hist))) return fail(IRIS_ERR_ARG, "iris_voxel_histogram: bad arguments");
     if (B == 0) return IRIS_OK;
-    LAUNCH1D(voxel_histogram_kernel, B, stream, x, B, (float)voxel_min, (float)(voxel_max - voxel_min), H, hist);
-    return IRIS_OK;
+    return launch1d(voxel_histogram_kernel, B, 8192, stream, x, B, (float)voxel_min, (float)(voxel_max - voxel_min), H, hist);
 }
 // extract_emitter_ldr.py:90-95 (torch_scatter.scatter(..., reduce='sum')): out[idx[i]] += values[i], count[idx[i]] += 1; idx < 0 skipped
 __global__ void scatter_add_rows_kernel(const float* __restrict__ values, const int64_t* __restrict__ idx, int64_t B, int64_t F, float* __restrict__ out,
@@ -1545,6 +1399,5 @@ __global__ void scatter_add_rows_kernel(const float* __restrict__ values, const 
 extern "C" IRIS_API int iris_scatter_add_rows(const float* values, const int64_t* idx, int64_t B, int64_t F, float* out, float* count, iris_stream_t stream) {
     if (B < 0 || F < 0 || (B > 0 && (!values || !idx || !out))) return fail(IRIS_ERR_ARG, "iris_scatter_add_rows: bad arguments");
     if (B == 0) return IRIS_OK;
-    LAUNCH1D(scatter_add_rows_kernel, B, stream, values, idx, B, F, out, count);
-    return IRIS_OK;
+    return launch1d(scatter_add_rows_kernel, B, 8192, stream, values, idx, B, F, out, count);
 }

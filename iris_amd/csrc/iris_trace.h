@@ -1,6 +1,7 @@
 // BVH traversal + watertight ray / triangle closest hit (replaces utils/path_tracing.py:30-43, the Mitsuba/OptiX call).
 // One ray per lane, per-lane traversal stack in LDS (stack[k*BLOCK + tid] -> conflict-free for ds_read/write_b32).
 #pragma once
+#include "bvh_build.h"      // the table layout shared with the host encoder: kLayoutF32 / kLayoutQ8, kNodeBytes, kLeafBit and the leaf reference packing
 #include "iris_device.h"
 
 namespace iris {
@@ -8,10 +9,7 @@ namespace iris {
 constexpr int kBlock = 256;          // threads per workgroup for every traversal kernel
 constexpr int kStackLds = 24;        // per-lane stack entries kept in LDS (24 KiB per workgroup)
 constexpr int kStackSpill = 72;      // rarely-touched overflow in scratch (correctness only)
-// Q8 node record: 64 B, 8-bit planes four to a word (a visit isolates near / far byte pairs with 12 v_perm_b32).
-constexpr uint32_t kNodeBytes = 64u;
-__device__ __forceinline__ uint32_t node_offset(uint32_t cur) { return cur << 6; }
-constexpr uint32_t kLeafBit = 0x80000000u;
+__device__ __forceinline__ uint32_t node_offset(uint32_t cur) { return cur << 6; }      // cur * kNodeBytes
 constexpr uint32_t kEmptyRef = 0xFFFFFFFFu;
 
 // Scene as laid out in HBM
@@ -201,11 +199,7 @@ struct TraceStats {
 // keeping the whole wave in a nearly empty phase).  Per-lane results do not depend on the schedule.
 constexpr int kPhaseMin = 12;      // (round 3 sweep at 4096-ray tiles: 10: 7.47, 12: 7.50, 14: 7.50, 16: 7.47, 20: 7.32 Grays/s)
 
-// Node layouts (iris_hip.h): BVH4_F32 = 128-B node with f32 planes (7 dwordx4 per visit); BVH4_Q8 = 64-B node
-// {origin.xyz, scale.x | scale.y, scale.z, qlo_x, qlo_y | qlo_z, qhi_x, qhi_y, qhi_z | ref[4]} with 8-bit planes relative to the node's
-// own box (4 dwordx4 per visit): plane = origin + q * 2^e per axis (the node stores 2^(e+24) as a float, see node_step), lo rounded down /
-// hi rounded up, so the decoded box contains the f32 box.
-constexpr int kLayoutF32 = 1, kLayoutQ8 = 3;
+// (the node layouts kLayoutF32 / kLayoutQ8: bvh_build.h)
 
 // Per-lane traversal state shared by the two drivers below (kept in registers; the struct is scalar-replaced).
 struct RayState {
@@ -237,7 +231,7 @@ __device__ __forceinline__ void node_step(const SceneDev& sc, RayState& r, STACK
     const float ix = r.ix, iy = r.iy, iz = r.iz, nx = r.nx, ny = r.ny, nz = r.nz;
     const bool px = r.px, py = r.py, pz = r.pz;
     if (LAYOUT == kLayoutQ8) {
-        // The node table exists once per ray octant (iris_hip.hip): the copy a ray reads holds the children in ITS front-to-back order (the order of
+        // The node table exists once per ray octant (bvh_build.cpp encode_nodes): the copy a ray reads holds the children in ITS front-to-back order (the order of
         // the binary splits the node was collapsed from) and, per axis, the plane it meets first in the "near" bytes -- so a visit selects no planes
         // by the ray's signs and sorts nothing.  32-bit byte offset from the (scalar) table base: one shift-add per visit.
         glb_u4v* n = (glb_u4v*)(reinterpret_cast<const char*>(sc.nodes) + (size_t)(uint32_t)(node_offset(r.cur) + r.oct_base));

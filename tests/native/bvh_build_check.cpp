@@ -1,12 +1,14 @@
 // Host-only check of the BVH builder (iris_amd/csrc/bvh_build.cpp), meant to be compiled with
 //   g++ -O1 -g -fsanitize=address,undefined bvh_build_check.cpp ../../iris_amd/csrc/bvh_build.cpp -lpthread
 // (GPU AddressSanitizer is not available on the pool: sanitizers run on the CPU build only).  Builds trees over random
-// triangle soups, degenerate inputs and a grid, and checks the structural invariants the traversal kernels rely on.
+// triangle soups, degenerate inputs and a grid, and checks the structural invariants the traversal kernels rely on -- of the tree, and of
+// the node / leaf-record tables the same file encodes it into for the device (properties of the format: no tolerance anywhere).
 #include <algorithm>
 #include <cmath>
 #include <initializer_list>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <vector>
 
@@ -16,6 +18,95 @@ using namespace iris;
 
 static int fails = 0;
 #define CHECK(c, ...) do { if (!(c)) { std::printf("FAIL %s:%d: ", __FILE__, __LINE__); std::printf(__VA_ARGS__); std::printf("\n"); ++fails; } } while (0)
+
+// The encoder (bvh_build.h): the 8-bit planes of every node are conservative (widths 4 and 8); the 4-wide device tables hold, per ray octant, the children in
+// WideNode::order with the plane the ray meets first in the "near" bytes, unused slots as the empty box on the degenerate leaf, and the leaf records of tri_order.
+static uint32_t word(const float* p) { uint32_t u; std::memcpy(&u, p, 4); return u; }
+static void check_encoding(const char* name, const WideBvh& b, const std::vector<float>& v, const std::vector<int32_t>& f, int width) {
+    const size_t nn = b.nodes.size(), nt = b.tri_order.size();
+    std::vector<QuantNode> qn(nn);
+    for (size_t i = 0; i < nn; ++i) {
+        const WideNode& w = b.nodes[i];
+        const bool ok = quantise_node(w, width, qn[i]);
+        CHECK(ok, "%s: node %zu cannot be quantised", name, i);
+        if (!ok) return;
+        NodeBoxes d;
+        decode_node(qn[i], d);
+        for (int s = 0; s < width; ++s)
+            for (int k = 0; k < 3; ++k) {
+                if (s < w.n) CHECK(d.lo[s][k] <= w.lo[s][k] && d.hi[s][k] >= w.hi[s][k], "%s: node %zu slot %d axis %d: decoded [%g, %g] does not contain [%g, %g]", name, i, s, k, d.lo[s][k], d.hi[s][k], w.lo[s][k], w.hi[s][k]);
+                else CHECK(qn[i].lo[k][s] == 255 && qn[i].hi[k][s] == 0 && d.lo[s][k] > d.hi[s][k], "%s: node %zu: unused slot %d is not the empty box", name, i, s);
+            }
+    }
+    if (width != 4) { CHECK(encode_nodes(b, kLayoutQ8).empty(), "%s: a %d-wide tree has no device layout", name, width); return; }
+    // leaf records: record i = the vertices of triangle tri_order[i], component-major, its id in the fourth lane of the three planes; then the degenerate record
+    const std::vector<float> rec = encode_leaf_records(b, v.data(), f.data());
+    CHECK(rec.size() == (nt + 1) * 16, "%s: %zu floats of leaf records for %zu references", name, rec.size(), nt);
+    if (rec.size() != (nt + 1) * 16) return;
+    for (size_t i = 0; i <= nt; ++i) {
+        const float* r = rec.data() + i * 16;
+        const int32_t t = i < nt ? b.tri_order[i] : -1;
+        bool ok = true;
+        for (int k = 0; k < 3; ++k) {
+            for (int c = 0; c < 3; ++c) {
+                const float want = i < nt ? v[(size_t)f[(size_t)t * 3 + c] * 3 + k] : 0.f;
+                ok = ok && std::memcmp(&r[4 * k + c], &want, 4) == 0;
+            }
+            ok = ok && word(&r[4 * k + 3]) == (uint32_t)t && word(&r[12 + k]) == 0u;
+        }
+        CHECK(ok && word(&r[15]) == 0u, "%s: leaf record %zu is not triangle %d", name, i, t);
+    }
+    const uint32_t dummy = leaf_ref((uint32_t)nt, 1u);
+    auto check_ref = [&](uint32_t ref, size_t i) {
+        if (ref & kLeafBit) CHECK(leaf_ref_count(ref) >= 1 && (size_t)leaf_ref_start(ref) + leaf_ref_count(ref) <= nt + 1, "%s: node %zu: leaf reference %#x leaves the record table", name, i, ref);
+        else CHECK(ref < nn, "%s: node %zu: child reference %u", name, i, ref);
+    };
+    // F32: the builder's planes and the references, slot by slot
+    const std::vector<float> n32 = encode_nodes(b, kLayoutF32);
+    CHECK(n32.size() == nn * 32, "%s: F32 node table of %zu floats", name, n32.size());
+    for (size_t i = 0; i < nn && n32.size() == nn * 32; ++i) {
+        const WideNode& w = b.nodes[i];
+        const float* p = n32.data() + i * 32;
+        for (int s = 0; s < 4; ++s) {
+            const uint32_t ref = word(&p[24 + s]);
+            check_ref(ref, i);
+            CHECK(ref == (s < w.n ? child_ref(w, s) : dummy), "%s: F32 node %zu slot %d: reference %#x", name, i, s, ref);
+            for (int k = 0; k < 3 && s < w.n; ++k) CHECK(p[8 * k + s] == w.lo[s][k] && p[8 * k + 4 + s] == w.hi[s][k], "%s: F32 node %zu slot %d axis %d", name, i, s, k);
+        }
+    }
+    // Q8: eight copies
+    const std::vector<float> n8 = encode_nodes(b, kLayoutQ8);
+    CHECK(n8.size() == nn * 16 * 8, "%s: Q8 node table of %zu floats", name, n8.size());
+    if (n8.size() != nn * 16 * 8) return;
+    for (size_t i = 0; i < nn; ++i) {
+        const WideNode& w = b.nodes[i];
+        const QuantNode& q = qn[i];
+        for (int o = 0; o < 8; ++o) {
+            const float* p = n8.data() + ((size_t)o * nn + i) * 16;
+            for (int k = 0; k < 3; ++k) {
+                CHECK(p[k] == q.origin[k] && p[3 + k] == std::ldexp(1.0f, q.exp[k] + 24), "%s: node %zu octant %d axis %d: origin / scale", name, i, o, k);
+                const bool neg = (o >> k) & 1;
+                uint8_t near_[4], far_[4];
+                std::memcpy(near_, &p[6 + k], 4); std::memcpy(far_, &p[9 + k], 4);
+                for (int j = 0; j < 4; ++j) {
+                    const uint8_t lower = neg ? far_[j] : near_[j], upper = neg ? near_[j] : far_[j];      // "near" is the lower plane exactly when the ray travels up the axis
+                    if (j < w.n) {
+                        const int sl = w.order[o][j];
+                        CHECK(lower == q.lo[k][sl] && upper == q.hi[k][sl], "%s: node %zu octant %d child %d axis %d: planes %d..%d, slot %d has %d..%d", name, i, o, j, k, lower, upper, sl, q.lo[k][sl], q.hi[k][sl]);
+                        // what the kernel reconstructs, origin + q * 2^e, from the table's own words
+                        const int e = std::ilogb(p[3 + k]) - 24;
+                        CHECK(decode_plane(p[k], e, lower) <= w.lo[sl][k] && decode_plane(p[k], e, upper) >= w.hi[sl][k], "%s: node %zu octant %d child %d axis %d: table box does not contain the f32 box", name, i, o, j, k);
+                    } else CHECK(lower == 255 && upper == 0, "%s: node %zu octant %d: unused slot %d axis %d is %d..%d, not the empty box", name, i, o, j, k, lower, upper);
+                }
+            }
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t ref = word(&p[12 + j]);
+                check_ref(ref, i);
+                CHECK(ref == (j < w.n ? child_ref(w, w.order[o][j]) : dummy), "%s: node %zu octant %d child %d: reference %#x is not that of slot order[o][j]", name, i, o, j, ref);
+            }
+        }
+    }
+}
 
 static int64_t split_refs = 0;
 static void check_tree(const char* name, const std::vector<float>& v, const std::vector<int32_t>& f, int width, int max_leaf, int expect_split = -1) {
@@ -98,6 +189,7 @@ static void check_tree(const char* name, const std::vector<float>& v, const std:
             CHECK(in, "%s: a point of split triangle %lld (%d references) is in none of their leaf boxes", name, (long long)t, (int)boxes_of[(size_t)t].size());
         }
     }
+    check_encoding(name, b, v, f, width);
     split_refs = nr - nf;
     CHECK(3 * b.depth + 4 <= 96, "%s: depth %d too deep for the traversal stack", name, b.depth);
     std::printf("ok %-28s nf=%-8lld refs=%-8lld nodes=%-8zu depth=%-3d sah=%.2f\n", name, (long long)nf, (long long)nr, b.nodes.size(), b.depth, b.sah_cost);
@@ -147,6 +239,6 @@ int main() {
     }
     { auto s = soup(20000, 0.05f, 4.f); check_tree("soup 20k (uniform: no split)", s.first, s.second, 4, 4, 0); }
     if (fails) { std::printf("%d check(s) failed\n", fails); return 1; }
-    std::printf("all BVH builder checks passed\n");
+    std::printf("all BVH builder checks passed\n");      // (test_sanitizers.py looks for this line)
     return 0;
 }

@@ -1,8 +1,8 @@
 // Host-side quality check of the wide-BVH builder (iris_amd/csrc/bvh_build.cpp): builds the tree for a mesh dumped by
 // tools/bvh_eval/dump_room.py and traces a sample of bake-like secondary rays (origins on the surface, cosine-distributed directions
 // into the room) with the traversal rule of the kernels (iris_trace.h: ordered by entry distance, children culled by the best hit),
-// counting node visits and triangle tests per ray.  Applies the 8-bit plane quantisation of the Q8 node layout (iris_hip.hip) so that
-// the counts are those of the device tree.  Numbers agree with the instrumented GPU launches (bench.py roofline.nodes_per_ray).
+// counting node visits and triangle tests per ray.  Applies the 8-bit plane quantisation of the Q8 node layout with the library's own encoder
+// (bvh_build.h quantise_node) so that the counts are those of the device tree.  Numbers agree with the instrumented GPU launches (bench.py roofline.nodes_per_ray).
 //   g++ -O2 -std=c++17 -I iris_amd/csrc tools/bvh_eval/bvh_eval.cpp iris_amd/csrc/bvh_build.cpp -lpthread -o tools/bvh_eval/bvh_eval
 #include <algorithm>
 #include <chrono>
@@ -21,8 +21,6 @@ struct V3 { float x, y, z; };
 static V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 static V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 static float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
-struct QNode { float lo[kMaxWidth][3], hi[kMaxWidth][3]; };   // decoded (quantised, conservative) child boxes
 
 int main(int argc, char** argv) {
     const char* path = argc > 1 ? argv[1] : "/tmp/room.bin";
@@ -46,32 +44,14 @@ int main(int argc, char** argv) {
     WideBvh bvh = build_wide_bvh(verts.data(), nv, faces.data(), nf, width, max_leaf, 2e-5f, tri_cost, ps ? (float)atof(ps) : 8.f);
     const double build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     const size_t nn = bvh.nodes.size();
-    // Q8 decode: per node, origin = min of child lows, per axis the smallest power of two 2^e with 255 * 2^e >= extent
-    std::vector<QNode> q(nn);
-    const bool iso = getenv("BVH_EVAL_ISO") != nullptr;   // ONE plane scale per node (the largest axis extent) instead of one per axis: the 80-B node study of round 5
+    // the boxes a ray is tested against: what the device's 8-bit planes decode to (quantise_node / decode_node: the library's own encoder), or the builder's f32 boxes (quant = 0)
+    std::vector<NodeBoxes> q(nn);
     for (size_t i = 0; i < nn; ++i) {
         const WideNode& w = bvh.nodes[i];
-        double ext_max = 0;
-        for (int k = 0; k < 3; ++k) {
-            float org = INFINITY, hi3 = -INFINITY;
-            for (int s = 0; s < w.n; ++s) { org = std::min(org, w.lo[s][k]); hi3 = std::max(hi3, w.hi[s][k]); }
-            ext_max = std::max(ext_max, (double)hi3 - (double)org);
-        }
-        for (int k = 0; k < 3; ++k) {
-            float org = INFINITY, hi3 = -INFINITY;
-            for (int s = 0; s < w.n; ++s) { org = std::min(org, w.lo[s][k]); hi3 = std::max(hi3, w.hi[s][k]); }
-            const double ext = iso ? ext_max : (double)hi3 - (double)org;
-            int e = -126;
-            if (ext > 0) e = std::max(-126, (int)std::ceil(std::log2(ext / 255.0)));
-            while (std::ldexp(255.0, e) < ext) ++e;
-            const double sc = std::ldexp(1.0, e);
-            for (int s = 0; s < width; ++s) {
-                if (s >= w.n) { q[i].lo[s][k] = INFINITY; q[i].hi[s][k] = -INFINITY; continue; }
-                int lo = (int)std::floor(((double)w.lo[s][k] - org) / sc), hi = (int)std::ceil(((double)w.hi[s][k] - org) / sc);
-                lo = std::min(255, std::max(0, lo)); hi = std::min(255, std::max(0, hi));
-                q[i].lo[s][k] = quant ? (float)(org + lo * sc) : w.lo[s][k]; q[i].hi[s][k] = quant ? (float)(org + hi * sc) : w.hi[s][k];
-            }
-        }
+        QuantNode qn;
+        if (!quant) { for (int s = 0; s < w.n; ++s) for (int k = 0; k < 3; ++k) { q[i].lo[s][k] = w.lo[s][k]; q[i].hi[s][k] = w.hi[s][k]; } }
+        else if (quantise_node(w, width, qn)) decode_node(qn, q[i]);
+        else { fprintf(stderr, "node %zu cannot be quantised\n", i); return 1; }
     }
     // rays: BVH_EVAL_RAYS=<file from dump_rays.py>: the bake kernel's own rays, tile by tile in the order of its LDS counting sort; otherwise
     // area-weighted surface points, cosine hemisphere around the normal that faces the room centre
@@ -96,7 +76,7 @@ int main(int argc, char** argv) {
             --sp;
             const bool skip = cull_bits == -2 ? false : cull_bits == -1 ? dstack[sp] > best : code(dstack[sp]) > code(best);
             if (!skip) return stack[sp];
-            if (stack[sp] & 0x80000000u) ++skipped_leaves; else ++skipped_nodes;
+            if (stack[sp] & kLeafBit) ++skipped_leaves; else ++skipped_nodes;
         }
         return 0xffffffffu;
     };
@@ -113,10 +93,10 @@ int main(int argc, char** argv) {
         const int oct = (d.x < 0 ? 1 : 0) | (d.y < 0 ? 2 : 0) | (d.z < 0 ? 4 : 0);
         int64_t hit_tri = -1;
         int sp = 0;
-        uint32_t cur = 0;   // node index, or 0x80000000 | start << 3 | count
+        uint32_t cur = 0;   // node index or leaf reference (bvh_build.h child_ref)
         for (;;) {
-            if (cur & 0x80000000u) {
-                const int start = (cur & 0x7fffffffu) >> 3, cnt = cur & 7;
+            if (cur & kLeafBit) {
+                const int start = (int)leaf_ref_start(cur), cnt = (int)leaf_ref_count(cur);
                 for (int k = 0; k < cnt; ++k) {
                     ++tot_tris;
                     const int64_t ti = bvh.tri_order[start + k];
@@ -139,7 +119,7 @@ int main(int argc, char** argv) {
                     if (t0 > t1) std::swap(t0, t1);
                     tn = std::max(tn, t0); tf = std::min(tf, t1);
                 }
-                if (tn <= tf) { key[m] = tn; ref[m] = w.child[s] >= 0 ? (uint32_t)w.child[s] : (0x80000000u | (uint32_t)w.leaf_start[s] << 3 | (uint32_t)w.leaf_count[s]); ++m; }
+                if (tn <= tf) { key[m] = tn; ref[m] = child_ref(w, s); ++m; }
             }
             if (!oct_order) for (int i = 1; i < m; ++i) for (int j = i; j > 0 && key[j] < key[j - 1]; --j) { std::swap(key[j], key[j - 1]); std::swap(ref[j], ref[j - 1]); }
             if (m == 0) { cur = pop(sp, best); if (cur == 0xffffffffu) break; continue; }

@@ -31,10 +31,10 @@ static V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 static V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 static float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 
-static constexpr uint32_t kLeaf = 0x80000000u, kEmpty = 0xffffffffu;
+static constexpr uint32_t kLeaf = kLeafBit, kEmpty = 0xffffffffu;
 static int kRefillMin = 48, kRefillTop = 0 /* 0: = kRefillMin */, kPhaseMin = 12, kPhaseMinLeaf = 0 /* 0: = kPhaseMin */, kScalarTop = 44, kSharedTries = 2;   // the kernel's constants (iris_trace.h); WAVESIM_REFILL / _PHASE / _TOP / _TRIES override them
 
-struct QNode { float lo[4][3], hi[4][3]; uint32_t ref[4]; };   // decoded (quantised, conservative) child boxes; ref: node index or kLeaf | start << 3 | count; unused: inverted box
+struct QNode { NodeBoxes box; uint32_t ref[4]; };   // decoded (quantised, conservative) child boxes; ref: node index or leaf reference (bvh_build.h child_ref); unused: empty box
 
 struct Scene {
     std::vector<float> verts; std::vector<int32_t> faces; WideBvh bvh; std::vector<QNode> q;
@@ -52,25 +52,12 @@ static bool load_scene(const char* path, Scene& sc) {
     sc.bvh = build_wide_bvh(sc.verts.data(), nv, sc.faces.data(), nf, 4, 4, 2e-5f, 0.7f, 8.f);
     const size_t nn = sc.bvh.nodes.size();
     sc.q.resize(nn);
-    for (size_t i = 0; i < nn; ++i) {
+    for (size_t i = 0; i < nn; ++i) {      // the device's planes: the library's own encoder (bvh_build.h)
         const WideNode& w = sc.bvh.nodes[i];
-        for (int k = 0; k < 3; ++k) {
-            float org = INFINITY, hi3 = -INFINITY;
-            for (int s = 0; s < w.n; ++s) { org = std::min(org, w.lo[s][k]); hi3 = std::max(hi3, w.hi[s][k]); }
-            const double ext = (double)hi3 - (double)org;
-            int e = -126;
-            if (ext > 0) e = std::max(-126, (int)std::ceil(std::log2(ext / 255.0)));
-            while (std::ldexp(255.0, e) < ext) ++e;
-            const double scl = std::ldexp(1.0, e);
-            for (int s = 0; s < 4; ++s) {
-                if (s >= w.n) { sc.q[i].lo[s][k] = INFINITY; sc.q[i].hi[s][k] = -INFINITY; continue; }
-                int lo = (int)std::floor(((double)w.lo[s][k] - org) / scl), hi = (int)std::ceil(((double)w.hi[s][k] - org) / scl);
-                lo = std::min(255, std::max(0, lo)); hi = std::min(255, std::max(0, hi));
-                sc.q[i].lo[s][k] = (float)(org + lo * scl); sc.q[i].hi[s][k] = (float)(org + hi * scl);
-            }
-        }
-        for (int s = 0; s < 4; ++s)
-            sc.q[i].ref[s] = s >= w.n ? kEmpty : (w.child[s] >= 0 ? (uint32_t)w.child[s] : (kLeaf | (uint32_t)w.leaf_start[s] << 3 | (uint32_t)w.leaf_count[s]));
+        QuantNode qn;
+        if (!quantise_node(w, 4, qn)) return false;
+        decode_node(qn, sc.q[i].box);
+        for (int s = 0; s < 4; ++s) sc.q[i].ref[s] = s >= w.n ? kEmpty : child_ref(w, s);
     }
     return true;
 }
@@ -111,7 +98,7 @@ struct Sim {
             const int s = (int)w.order[L.oct][j];
             float tn = 0.f, tf = L.best;
             for (int k = 0; k < 3; ++k) {
-                float t0 = (n.lo[s][k] - L.o[k]) * L.id[k], t1 = (n.hi[s][k] - L.o[k]) * L.id[k];
+                float t0 = (n.box.lo[s][k] - L.o[k]) * L.id[k], t1 = (n.box.hi[s][k] - L.o[k]) * L.id[k];
                 if (t0 > t1) std::swap(t0, t1);
                 tn = std::max(tn, t0); tf = std::min(tf, t1);
             }
@@ -126,7 +113,7 @@ struct Sim {
     }
     // tests the first triangle of leaf reference `ref`; returns what is left of the leaf (kEmpty: finished)
     uint32_t tri_one(Lane& L, uint32_t ref) {
-        const int start = (int)((ref & 0x7fffffffu) >> 3);
+        const int start = (int)leaf_ref_start(ref);
         const int64_t ti = sc.bvh.tri_order[start];
         V3 o{L.o[0], L.o[1], L.o[2]}, d{L.d[0], L.d[1], L.d[2]};
         V3 q0 = sc.vert(ti, 0), f1 = sub(sc.vert(ti, 1), q0), f2 = sub(sc.vert(ti, 2), q0);
@@ -219,7 +206,7 @@ struct Sim {
                 for (auto& L : w.l) { if (at_leaf(L)) ++n_leaf; else if (at_node(L)) ++n_node; else ++n_idle; }
                 if (n_leaf == 0 || (n_leaf < (kPhaseMinLeaf ? kPhaseMinLeaf : kPhaseMin) && n_node >= (kPhaseMinLeaf ? kPhaseMinLeaf : kPhaseMin)) || (n_leaf <= 64 - kRefillMin && w.more && n_idle >= kRefillMin)) { w.phase = 0; continue; }
                 uint32_t keys[64]; int nk = 0;
-                for (auto& L : w.l) if (at_leaf(L)) keys[nk++] = (L.cur & 0x7fffffffu) >> 3;
+                for (auto& L : w.l) if (at_leaf(L)) keys[nk++] = leaf_ref_start(L.cur);
                 std::sort(keys, keys + nk);
                 st.leaf_lines += std::unique(keys, keys + nk) - keys;
                 for (auto& L : w.l) if (at_leaf(L)) { leaf_step(L); st.tri_tests++; }
