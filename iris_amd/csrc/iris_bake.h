@@ -104,11 +104,20 @@ __device__ __forceinline__ RayOut trace_shade(const BakeArgs& a, int64_t p, int 
     return r;
 }
 
+// Zero-weight specular samples.  When the sampled direction points into the surface (NoL = relu(wi . n) = 0, or VoH = 0), specular_weights gives
+// g0 = g1 = +0 exactly: the sample adds Le * 0 to both sums, and for FINITE radiance tables that changes no bit of them (the accumulators start at +0
+// and can never become -0).  The production kernels do not trace such a sample -- 13-23 % of a view's specular rays, half of the roughness-1 lobe's.
+// The rule is on the computed weights ("what is multiplied into Le is zero"), not on a re-derived geometric condition.  Kept tracing everything:
+// the instrumented (COUNT) instantiations, whose counters describe all P x spp rays (tests/test_stats.py: rays == P * spp, every ray visits the
+// root), and launches that return per-sample triangle ids / table rows.  With an inf / NaN radiance row the reference's Le * 0 is NaN, ours 0.
+__device__ __forceinline__ bool dead_samples_skippable(const BakeArgs& a) { return !a.tri_next && !a.src_next; }
+
 template <bool SPEC, bool COUNT, int LAYOUT, int LDS_DEPTH = kStackLds, bool GLOBAL_OVF = false>
 __device__ __forceinline__ RayOut shade_sample(const BakeArgs& a, int64_t p, int s, f3 x, f3 n, f3 w, f3 t, f3 b, uint64_t base,
                                                uint32_t* lds_stack, TraceStats* ts, uint32_t& n_rays, uint32_t* ovf = nullptr) {
     f3 wi; float g0, g1;
     sample_lobe<SPEC>(a, p, s, n, w, t, b, base, wi, g0, g1);
+    if (SPEC && !COUNT && dead_samples_skippable(a) && g0 == 0.f && g1 == 0.f) return RayOut{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // a zero-weight sample: not traced
     return trace_shade<SPEC, COUNT, LAYOUT, LDS_DEPTH, GLOBAL_OVF>(a, p, s, x, wi, g0, g1, lds_stack, ts, n_rays, ovf);
 }
 
@@ -227,6 +236,7 @@ __device__ __forceinline__ void tile_body(const BakeArgs& a, int64_t p0, int np,
     const float inv_spp = 1.0f / (float)spp;
     const int nr = np * spp;
     const bool resolve = !a.em.emit_ord && !a.tri_next;      // fused records, and nobody asks for the per-sample triangle ids
+    const bool skip_dead = dead_samples_skippable(a);
 
     // r / spp for a tile-local ray index without the 25-instruction integer division: exact for r * spp < 2^32 (r < kTileRays, spp <= kTileRays)
     const uint32_t spp_m = spp > 1 ? (uint32_t)(0x100000000ull / (uint64_t)(uint32_t)spp) + 1u : 0u;
@@ -249,7 +259,7 @@ __device__ __forceinline__ void tile_body(const BakeArgs& a, int64_t p0, int np,
     }
 
     // phases A-C (iris_tile.h): sample every ray (uniforms -> direction + GGX weights) and park it; sort by direction; trace
-    tile_sort_trace<LAYOUT, COUNT, kTileRays, TILE_STACK, true>(
+    tile_sort_trace<LAYOUT, COUNT, kTileRays, TILE_STACK, true, SPEC && !COUNT>(
         a.sc, nr, s_sorted, s_stack, s_chunk, ovf, ts,
         [&](int r) -> uint32_t {
             const int pl = div_spp(r), s = r - pl * spp;
@@ -261,9 +271,11 @@ __device__ __forceinline__ void tile_body(const BakeArgs& a, int64_t p0, int np,
             else normal_space(n, t, b);
             f3 wi; float g0, g1;
             sample_lobe<SPEC>(a, p, s, n, w, t, b, base, wi, g0, g1);
-            res[r] = make_float4(wi.x, wi.y, wi.z, 0.f);
             if (SPEC) res_g[r] = make_float2(g1, g0);
-            return dir_bin(wi);
+            // a zero-weight sample: park the record a miss would leave (no gather in phase D, which then adds Le * 0) and keep it out of the sort
+            const bool dead = SPEC && !COUNT && skip_dead && g0 == 0.f && g1 == 0.f;
+            res[r] = dead ? make_float4(0.f, 0.f, __int_as_float(resolve ? 0 : -1), __int_as_float(resolve ? -2 : 0)) : make_float4(wi.x, wi.y, wi.z, 0.f);
+            return dead ? kDeadRay : dir_bin(wi);
         },
         [&](int r, f3& o, f3& d) {
             const int64_t p = p0 + div_spp(r);

@@ -55,16 +55,24 @@ __device__ unsigned long long g_phase_cycles[8];
 // cursor storage: CAP bytes of keys, then 256 + 256 words -- the uses are separated by workgroup barriers), *s_chunk (cursor).
 // Before the call the caller has zeroed the histogram (s_stack + CAP/4, 256 words) and *s_chunk and passed a barrier.
 //   phase_a(r) -> direction bin : sample ray r of the tile and park whatever phase C / the caller's epilogue need
+//                                 (SKIP_DEAD: or kDeadRay -- the ray needs no trace and the caller has parked its final record itself)
 //   fetch_ray(r, o, d)          : ISSUE the loads of ray r's raw origin / direction (no dependent arithmetic)
 //   prepare(o, d)               : raw -> actual origin / direction (first use of the loaded values)
 //   retire(r, h)                : store the hit of ray r
+// SKIP_DEAD (the bake kernels' zero-weight specular samples, iris_bake.h): a ray phase_a reports as kDeadRay enters neither the histogram nor the
+// sorted list, and phase C runs over the nr_live entries the list then has.  All 256 values of the key are taken, so deadness travels in a per-thread
+// bit mask from phase A to phase B (the same thread handles the same rays, r = tid + k * 256, k < CAP / 256 <= 32).  nr_live is the total of the prefix
+// scan; the live rays are scattered to the LAST nr_live entries of the list and the cursor *s_chunk starts at nr - nr_live, so that phase C carries no
+// value it did not carry before (a tile without live rays falls straight through it).  Without SKIP_DEAD none of this is compiled.
 // Everything exchanged through global memory here stays inside ONE workgroup, so __syncthreads() orders it (the waves of a
 // workgroup share their CU's write-through L1; an agent-scope __threadfence() would flush that L1 -- including the hot upper BVH
 // levels -- once per tile and was measured 9 % slower per fence pair).  Ends with a barrier: hits are visible to the caller.
-template <int LAYOUT, bool COUNT, int CAP, int TILE_STACK, bool GLOBAL_OVF, class PhaseA, class FetchRay, class Prepare, class Retire>
+constexpr uint32_t kDeadRay = 256u;
+template <int LAYOUT, bool COUNT, int CAP, int TILE_STACK, bool GLOBAL_OVF, bool SKIP_DEAD = false, class PhaseA, class FetchRay, class Prepare, class Retire>
 __device__ __forceinline__ void tile_sort_trace(const SceneDev& sc, int nr, uint16_t* s_sorted, uint32_t* s_stack, int* s_chunk, uint32_t* ovf,
                                                 TraceStats& ts, PhaseA phase_a, FetchRay fetch_ray, Prepare prepare, Retire retire) {
     static_assert(TILE_STACK * kBlock * 4 >= CAP + 2 * 256 * 4, "stack region too small to alias the sort keys");
+    static_assert(!SKIP_DEAD || CAP <= 32 * kBlock, "one bit per ray of a thread");
     uint8_t* s_keys = reinterpret_cast<uint8_t*>(s_stack);
     uint32_t* s_hist = s_stack + CAP / 4;
     uint32_t* s_cur = s_hist + 256;
@@ -72,6 +80,15 @@ __device__ __forceinline__ void tile_sort_trace(const SceneDev& sc, int nr, uint
     IRIS_PHASE_BEGIN();
     __builtin_amdgcn_s_setprio(IRIS_PRIO_A);
     // ---- phase A: sample, park, histogram of the direction bins
+    uint32_t dead = 0;   // (SKIP_DEAD) bit k: ray tid + k * 256 needs no trace
+    if (SKIP_DEAD) {
+        uint32_t bit = 1u;
+        for (int r = tid; r < nr; r += kBlock, bit <<= 1) {
+            const uint32_t key = phase_a(r);
+            if (key == kDeadRay) dead |= bit;
+            else { s_keys[r] = (uint8_t)key; atomicAdd(&s_hist[key], 1u); }
+        }
+    } else
     for (int r = tid; r < nr; r += kBlock) {
         const uint32_t key = phase_a(r);
         s_keys[r] = (uint8_t)key;
@@ -85,10 +102,23 @@ __device__ __forceinline__ void tile_sort_trace(const SceneDev& sc, int nr, uint
         uint32_t tot = c0 + c1 + c2 + c3, inc = tot;
         for (int m = 1; m < 64; m <<= 1) { uint32_t v = __shfl_up(inc, m); if (lane >= m) inc += v; }
         uint32_t ex = inc - tot;
+        if (SKIP_DEAD) {
+            // the live rays take the END of the list and the cursor starts in front of them: phase C is the same code with or without dead rays
+            const uint32_t first = (uint32_t)nr - (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+            ex += first;
+            if (lane == 0) *s_chunk = (int)first;
+        }
         s_cur[lane * 4] = ex; s_cur[lane * 4 + 1] = ex + c0; s_cur[lane * 4 + 2] = ex + c0 + c1; s_cur[lane * 4 + 3] = ex + c0 + c1 + c2;
     }
     __syncthreads();
     // ---- phase B: scatter ray ids into bin order (order inside a bin is irrelevant: hits go to per-ray slots)
+    if (SKIP_DEAD) {
+        for (int r = tid; r < nr; r += kBlock, dead >>= 1) {
+            if (dead & 1u) continue;
+            const uint32_t pos = atomicAdd(&s_cur[s_keys[r]], 1u);
+            s_sorted[pos] = (uint16_t)r;
+        }
+    } else
     for (int r = tid; r < nr; r += kBlock) {
         const uint32_t pos = atomicAdd(&s_cur[s_keys[r]], 1u);
         s_sorted[pos] = (uint16_t)r;
