@@ -242,6 +242,19 @@ IRIS_API int iris_pt_accumulate_fwd(const float *radiance, const int32_t *e0, co
 /* dL/d radiance: g_radiance (n_rad,3), zero-initialised by the caller, += scatter of gL (B,3) */
 IRIS_API int iris_pt_accumulate_bwd(const float *gL, const int32_t *e0, const int32_t *path_of, const int32_t *e1, const float *coef1,
                            const int32_t *e2, const float *coef2, int64_t B, int spp, float *g_radiance, iris_stream_t);
+/* The reference's training step (train_emitter.py:181-189, initialize.py:172-180: n_calls = SPP // spp calls of path_tracing_single on the same rays, summed) as ONE
+ * accumulation.  Paths are pixel-major, path i = (b * n_calls + c) * spp + s; the arrays are iris_pt_accumulate_fwd's with n_calls * B * spp rows (< 2^31).
+ * SUMMATION ORDER (a contract: the result is the loop's `L = 0; L += L_c` bit for bit):
+ *   L[b] = (((m_0) + m_1) + ...) + m_{n_calls-1},   m_c = (sum over s = 0 .. spp-1, in that order, of term(b,c,s)) * (1.0f / spp)
+ * with iris_pt_accumulate_fwd's per-sample term -- every call's mean is rounded before the calls are added, in call order, in float32.
+ * n_calls = 1 gives iris_pt_accumulate_fwd's bits. */
+IRIS_API int iris_pt_step_accumulate_fwd(const float *radiance, const int32_t *e0, const int32_t *path_of, const int32_t *e1, const float *coef1,
+                                const int32_t *e2, const float *coef2, const float *const2, int64_t B, int spp, int n_calls, float *L,
+                                iris_stream_t);
+/* its dL/d radiance: the sum of the n_calls per-call gradients as one scatter (float atomics) over all paths, g = gL[b] * (1.0f / spp) for every call of pixel b;
+ * g_radiance (n_rad,3) zero-initialised by the caller */
+IRIS_API int iris_pt_step_accumulate_bwd(const float *gL, const int32_t *e0, const int32_t *path_of, const int32_t *e1, const float *coef1,
+                                const int32_t *e2, const float *coef2, int64_t B, int spp, int n_calls, float *g_radiance, iris_stream_t);
 
 /* ---- 8(f)-2: pooling builders of the stages that write vslf.npz / emitter.pth ------------------------------- */
 /* VoxelSLF.scatter_add (model/slf.py:56-61): radiance_acc (kv,3) f32 += rgb, count (kv) int64 += 1 at spatial_idx(x) */

@@ -80,6 +80,8 @@ PROTOTYPES = {
     "iris_pt_compact": [_P, _I64, _I32, _P, _P, C.c_uint32, _I32, _P, _P, _I32, _P, _P, _P, _P, C.c_uint64, _P],
     "iris_pt_accumulate_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P],
     "iris_pt_accumulate_bwd": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P],
+    "iris_pt_step_accumulate_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P],
+    "iris_pt_step_accumulate_bwd": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P],
     "iris_slf_scatter_add": [_P, _P, _P, _I64, _P, _P, _P],
     "iris_voxel_histogram": [_P, _I64, _D, _D, _I32, _P, _P],
     "iris_scatter_add_rows": [_P, _P, _I64, _I64, _P, _P, _P],

@@ -1272,6 +1272,26 @@ extern "C" IRIS_API int iris_pt_accumulate_bwd(const float* gL, const int32_t* e
     if (B == 0) return IRIS_OK;
     return launch1d(pt_accumulate_bwd_kernel, B * spp, 8192, stream, gL, e0, path_of, e1, coef1, e2, coef2, B, spp, g_radiance);
 }
+// The accumulation of a whole training step (n_calls calls on the same rays, paths pixel-major): see pt_step_accumulate_fwd_kernel for the summation order.
+static bool pt_step_sizes_ok(int64_t B, int spp, int n_calls) {
+    return B >= 0 && spp >= 1 && n_calls >= 1 && (int64_t)spp * n_calls < ((int64_t)1 << 31) && B * ((int64_t)spp * n_calls) < ((int64_t)1 << 31);   // (path_of is int32)
+}
+extern "C" IRIS_API int iris_pt_step_accumulate_fwd(const float* radiance, const int32_t* e0, const int32_t* path_of, const int32_t* e1, const float* coef1,
+                                           const int32_t* e2, const float* coef2, const float* const2, int64_t B, int spp, int n_calls, float* L,
+                                           iris_stream_t stream) {
+    if (!pt_step_sizes_ok(B, spp, n_calls) || (B > 0 && (!radiance || !e0 || !path_of || !L))) return fail(IRIS_ERR_ARG, "iris_pt_step_accumulate_fwd: bad arguments");
+    if (B == 0) return IRIS_OK;
+    int lpp = 1;
+    while (lpp < spp && lpp < 64) lpp <<= 1;                     // lanes per pixel, as iris_pt_accumulate_fwd
+    const int64_t n_groups = (B + 64 / lpp - 1) / (64 / lpp);
+    return launch1d(pt_step_accumulate_fwd_kernel, n_groups * 64, 8192, stream, radiance, e0, path_of, e1, coef1, e2, coef2, const2, B, spp, n_calls, lpp, L);
+}
+extern "C" IRIS_API int iris_pt_step_accumulate_bwd(const float* gL, const int32_t* e0, const int32_t* path_of, const int32_t* e1, const float* coef1,
+                                           const int32_t* e2, const float* coef2, int64_t B, int spp, int n_calls, float* g_radiance, iris_stream_t stream) {
+    if (!pt_step_sizes_ok(B, spp, n_calls) || (B > 0 && (!gL || !e0 || !path_of || !g_radiance))) return fail(IRIS_ERR_ARG, "iris_pt_step_accumulate_bwd: bad arguments");
+    if (B == 0) return IRIS_OK;
+    return launch1d(pt_step_accumulate_bwd_kernel, B * n_calls * spp, 8192, stream, gL, e0, path_of, e1, coef1, e2, coef2, B, spp, n_calls, g_radiance);
+}
 
 extern "C" IRIS_API int iris_pt_apply(float* L, const int32_t* rows, float* throughput, const float* radiance, const int32_t* e, const float* coef,
                              const float* cst, const float* weight, int64_t N, int nan_to_zero, iris_stream_t stream) {

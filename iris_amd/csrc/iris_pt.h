@@ -446,6 +446,76 @@ __global__ void pt_accumulate_bwd_kernel(const float* __restrict__ gL, const int
     }
 }
 
+// ---- the training step (train_emitter.py:181-189: n_calls calls of path_tracing_single on the same rays, summed) as ONE accumulation ----
+// Paths are pixel-major: path i = (b * n_calls + c) * spp + s.  SUMMATION ORDER (part of the contract, include/iris_hip.h):
+//   L[b] = (((m_0) + m_1) + ...) + m_{n_calls-1},   m_c = (sum over s = 0, 1, ..., spp-1 in that order of term(b,c,s)) * (1.0f / spp)
+// i.e. every call's mean is rounded before the calls are added in call order -- what `L = zeros; L += path_tracing_single(...)` computes.
+// term: pt_accumulate_fwd_kernel's per-sample term, in its internal order.
+__device__ __forceinline__ f3 pt_path_term(const float* __restrict__ radiance, const int32_t* __restrict__ e0, const int32_t* __restrict__ path_of,
+                                           const int32_t* __restrict__ e1, const float* __restrict__ coef1, const int32_t* __restrict__ e2,
+                                           const float* __restrict__ coef2, const float* __restrict__ const2, int64_t i) {
+    f3 l = mk3(0.f, 0.f, 0.f);
+    if (e0[i] >= 0) l = ld3(radiance + (int64_t)e0[i] * 3);
+    const int j = path_of[i];
+    if (j >= 0) {
+        if (e1[j] >= 0) { f3 r = ld3(radiance + (int64_t)e1[j] * 3), c = ld3(coef1 + (int64_t)j * 3); l.x += c.x * r.x; l.y += c.y * r.y; l.z += c.z * r.z; }
+        f3 t2 = ld3(const2 + (int64_t)j * 3);
+        if (e2[j] >= 0) { f3 r = ld3(radiance + (int64_t)e2[j] * 3), c = ld3(coef2 + (int64_t)j * 3); t2.x += c.x * r.x; t2.y += c.y * r.y; t2.z += c.z * r.z; }
+        l.x += t2.x; l.y += t2.y; l.z += t2.z;
+    }
+    return l;
+}
+// pt_accumulate_fwd_kernel's scheme -- one lane per (pixel, sample) of a call, the gathers in parallel, the sequential sum through lane reads, rounds of 64 when
+// spp > 64 -- with the calls of a pixel looped INSIDE its lane group: the n_calls * spp gathers of a pixel are issued by one wave.  n_calls = 1: that kernel's bits.
+__global__ __launch_bounds__(256) void pt_step_accumulate_fwd_kernel(const float* __restrict__ radiance, const int32_t* __restrict__ e0, const int32_t* __restrict__ path_of,
+                                         const int32_t* __restrict__ e1, const float* __restrict__ coef1, const int32_t* __restrict__ e2,
+                                         const float* __restrict__ coef2, const float* __restrict__ const2, int64_t B, int spp, int n_calls, int lpp,
+                                         float* __restrict__ L) {
+    const int lane = threadIdx.x & 63, sub = lane / lpp, sl = lane - sub * lpp, ppw = 64 / lpp;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t n_groups = (B + ppw - 1) / ppw;
+    const float inv = 1.0f / (float)spp;
+    for (int64_t g = wave; g < n_groups; g += n_waves) {
+        const int64_t b = g * ppw + sub;
+        float Lx = 0.f, Ly = 0.f, Lz = 0.f;
+        for (int c = 0; c < n_calls; ++c) {
+            const int64_t i0 = (b * n_calls + c) * spp;              // (b < B checked below: i0 < 2^31 there)
+            float ax = 0.f, ay = 0.f, az = 0.f;
+            for (int s0 = 0; s0 < spp; s0 += lpp) {                  // (spp > 64: rounds of 64 samples, still in order)
+                const int sidx = s0 + sl;
+                f3 l = mk3(0.f, 0.f, 0.f);
+                if (b < B && sidx < spp) l = pt_path_term(radiance, e0, path_of, e1, coef1, e2, coef2, const2, i0 + sidx);
+                const int n = min(lpp, spp - s0);                    // (wave-uniform)
+                for (int k = 0; k < n; ++k) {                        // the sequential sum, by every lane of the group (lane reads within the group)
+                    const int src = sub * lpp + k;
+                    ax += __shfl(l.x, src); ay += __shfl(l.y, src); az += __shfl(l.z, src);
+                }
+            }
+            const float mx = ax * inv, my = ay * inv, mz = az * inv; // the call's mean, rounded before it joins the sum over the calls
+            Lx = c ? Lx + mx : mx; Ly = c ? Ly + my : my; Lz = c ? Lz + mz : mz;
+        }
+        if (b < B && sl == 0) st3(L + b * 3, mk3(Lx, Ly, Lz));
+    }
+}
+// d radiance[e] += gL[b] * (1.0f / spp) * coef for EVERY call of pixel b: the sum of the per-call gradients as one scatter over all n_calls * B * spp paths
+// (float atomics, as pt_accumulate_bwd_kernel)
+__global__ void pt_step_accumulate_bwd_kernel(const float* __restrict__ gL, const int32_t* __restrict__ e0, const int32_t* __restrict__ path_of,
+                                              const int32_t* __restrict__ e1, const float* __restrict__ coef1, const int32_t* __restrict__ e2,
+                                              const float* __restrict__ coef2, int64_t B, int spp, int n_calls, float* __restrict__ g_radiance) {
+    const int64_t per_pixel = (int64_t)n_calls * spp, n = B * per_pixel;
+    const float inv = 1.0f / (float)spp;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = i / per_pixel;
+        const f3 g = mk3(gL[b * 3] * inv, gL[b * 3 + 1] * inv, gL[b * 3 + 2] * inv);
+        if (e0[i] >= 0) { float* q = g_radiance + (int64_t)e0[i] * 3; atomicAdd(q, g.x); atomicAdd(q + 1, g.y); atomicAdd(q + 2, g.z); }
+        const int j = path_of[i];
+        if (j >= 0) {
+            if (e1[j] >= 0) { float* q = g_radiance + (int64_t)e1[j] * 3; f3 c = ld3(coef1 + (int64_t)j * 3); atomicAdd(q, g.x * c.x); atomicAdd(q + 1, g.y * c.y); atomicAdd(q + 2, g.z * c.z); }
+            if (e2[j] >= 0) { float* q = g_radiance + (int64_t)e2[j] * 3; f3 c = ld3(coef2 + (int64_t)j * 3); atomicAdd(q, g.x * c.x); atomicAdd(q + 1, g.y * c.y); atomicAdd(q + 2, g.z * c.z); }
+        }
+    }
+}
+
 // L[rows[i]] += throughput[i] * (coef[i] * radiance[e[i]] + cst[i]), NaN -> 0 (trace_indirect's `dL[dL.isnan()] = 0`, :454-456,:484-486);
 // then optionally throughput[i] *= weight[i] (:462).  rows / throughput / cst / weight may be NULL.
 __global__ void pt_apply_kernel(float* __restrict__ Lacc, const int32_t* __restrict__ rows, float* __restrict__ throughput,

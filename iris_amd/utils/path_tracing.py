@@ -213,6 +213,117 @@ class _PtAccumulate(torch.autograd.Function):
         return (g.to(rad_dev),) + (None,) * 9
 
 
+class _PtStepAccumulate(torch.autograd.Function):
+    """_PtAccumulate for a whole training step (path_tracing_single_step): L = sum over the calls c, in call order, of mean_spp(call c's terms), paths pixel-major;
+    the backward pass is ONE scatter over all n_calls * B * spp paths (the sum of the per-call gradients)."""
+
+    @staticmethod
+    def forward(ctx, radiance, e0, path_of, e1, coef1, e2, coef2, const2, B, spp, n_calls):
+        rad = radiance.detach().to(device=e0.device, dtype=torch.float32).contiguous()
+        Lout = torch.empty(B, 3, device=rad.device, dtype=torch.float32)
+        with torch.cuda.device(rad.device):
+            L.check(L.lib().iris_pt_step_accumulate_fwd(L.ptr(rad), L.ptr(e0), L.ptr(path_of), L.ptr(e1), L.ptr(coef1), L.ptr(e2), L.ptr(coef2), L.ptr(const2),
+                                                        B, spp, n_calls, L.ptr(Lout), L.stream()))
+        ctx.save_for_backward(e0, path_of, e1, coef1, e2, coef2)
+        ctx.meta = (B, spp, n_calls, tuple(radiance.shape), radiance.device)
+        return Lout
+
+    @staticmethod
+    def backward(ctx, gL):
+        e0, path_of, e1, coef1, e2, coef2 = ctx.saved_tensors
+        B, spp, n_calls, shape, rad_dev = ctx.meta
+        g = torch.zeros(shape, device=gL.device, dtype=torch.float32)
+        gL = L.require_gpu(gL.contiguous().to(torch.float32), torch.float32, "grad of L")
+        with torch.cuda.device(gL.device):
+            L.check(L.lib().iris_pt_step_accumulate_bwd(L.ptr(gL), L.ptr(e0), L.ptr(path_of), L.ptr(e1), L.ptr(coef1), L.ptr(e2), L.ptr(coef2), B, spp, n_calls,
+                                                        L.ptr(g), L.stream()))
+        return (g.to(rad_dev),) + (None,) * 10
+
+
+def _roughness_bound(material_net):
+    """the lower bound of its roughness a material network declares, or None: taken from a network that is EXACTLY NGPBRDF (a subclass may map its roughness otherwise
+    and would inherit the class attribute silently) or that declares one on the INSTANCE (an explicit opt-in: tools/bench_refine.py's timing wrapper copies its network's)"""
+    from ..model.brdf import NGPBRDF
+    return NGPBRDF.roughness_min if type(material_net) is NGPBRDF else getattr(material_net, "__dict__", {}).get("roughness_min")
+
+
+def path_tracing_single_step(scene, emitter_net, material_net, rays_o, rays_d, dx_du, dy_dv, spp, n_calls, uniforms=None, skip_unused_material=True):
+    """The reference's training step (train_emitter.py:181-189, initialize.py:172-180) as one fused call: the SUM over c = 0 .. n_calls-1, added in that order in
+    float32, of what n_calls separate `path_tracing_single(..., spp, compact=False)` calls on the same rays return (each call's mean over its spp samples is rounded
+    before the sum); the caller keeps the reference's division by SPP // spp.
+
+    uniforms: None = the function's own draws, ONE generator launch for the whole step (8 * n_calls * B * spp floats); otherwise a list of n_calls entries, each the
+    five tensors of one call in the un-compacted shapes path_tracing_single(compact=False) takes ((2,B,spp), (B*spp), (B*spp,2), (B*spp), (B*spp,2)) -- the forward
+    result is then the loop's, bit for bit.
+    Paths are kept in place (un-compacted: the ones that do not continue are masked with path_of = -1) and ordered pixel-major, path i = (b * n_calls + c) * spp + s:
+    the n_calls * spp jittered rays of a pixel are neighbours, the head of the step is iris_pt_primary with spp' = n_calls * spp, and the material network sees ONE
+    evaluation of n_calls * B * spp points.  Every per-path stage is independent of its neighbours, so a path's bits do not depend on the order.  The visibility ray
+    and the BRDF ray of the paths share a launch (iris_pt_bounce): no side stream, no host synchronisation -- a linear chain on the caller's stream, capturable.
+    skip_unused_material: as in path_tracing_single.
+    Returns L Bx3, differentiable with respect to emitter_net.radiance (the sum of the per-call gradients, one backward scatter)."""
+    spp, n_calls = int(spp), int(n_calls)
+    if n_calls < 1 or spp < 1:
+        raise L.IrisError(f"path_tracing_single_step: n_calls ({n_calls}) and spp ({spp}) must be at least 1")
+    rays_o = L.require_gpu(rays_o, torch.float32, "rays_o").reshape(-1, 3)
+    rays_d = L.require_gpu(rays_d, torch.float32, "rays_d").reshape(-1, 3)
+    dx_du = L.require_gpu(dx_du, torch.float32, "dx_du").reshape(-1, 3)
+    dy_dv = L.require_gpu(dy_dv, torch.float32, "dy_dv").reshape(-1, 3)
+    B, dev = rays_o.shape[0], rays_o.device
+    S = n_calls * spp                      # samples of a pixel in the step
+    N = B * S
+    if N >= 1 << 31:
+        raise L.IrisError(f"path_tracing_single_step: n_calls * B * spp = {N} paths in one step, the limit is 2^31 - 1 (path_of is int32)")
+    if uniforms is not None:
+        # the recorded draws of the calls, moved to the pixel-major order (parity mode only: the function's own draws below are one tensor, cut)
+        calls = [list(u_c) for u_c in uniforms]
+        if len(calls) != n_calls:
+            raise L.IrisError(f"path_tracing_single_step: uniforms has {len(calls)} entries for n_calls = {n_calls}")
+        sizes = (2 * B * spp, B * spp, 2 * B * spp, B * spp, 2 * B * spp)
+        for c, u_c in enumerate(calls):
+            if len(u_c) != 5:
+                raise L.IrisError(f"path_tracing_single_step: uniforms[{c}] has {len(u_c)} tensors, a call draws five")
+            for k, (t, n) in enumerate(zip(u_c, sizes)):
+                if L.require_gpu(t, torch.float32, f"uniforms[{c}][{k}]").numel() != n:
+                    raise L.IrisError(f"path_tracing_single_step: uniforms[{c}][{k}] has shape {tuple(t.shape)}, expected {n} floats "
+                                      "((2,B,spp), (B*spp), (B*spp,2), (B*spp), (B*spp,2))")
+        dudv = torch.stack([u_c[0].reshape(2, B, spp) for u_c in calls], 2).reshape(2, B, S)
+        s1, s1b = (torch.stack([u_c[k].reshape(B, spp) for u_c in calls], 1).reshape(N) for k in (1, 3))
+        s2, s2b = (torch.stack([u_c[k].reshape(B, spp, 2) for u_c in calls], 1).reshape(N, 2) for k in (2, 4))
+    else:
+        pool = torch.rand(8 * N, device=dev)
+        dudv, s1, s2, s1b, s2b = pool[:2 * N].reshape(2, B, S), pool[2 * N:3 * N], pool[3 * N:5 * N].reshape(N, 2), pool[5 * N:6 * N], pool[6 * N:].reshape(N, 2)
+    rough_min = _roughness_bound(material_net)
+    skip_next = bool(skip_unused_material) and rough_min is not None and float(rough_min) > 0.0           # (see path_tracing_single's docstring)
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        L.mark()
+        eh, sh = emitter_net.handle(dev), emitter_net.slf.handle(dev)
+        wi = torch.empty(N, 3, device=dev); wo = torch.empty(N, 3, device=dev); position = torch.empty(N, 3, device=dev); normal = torch.empty(N, 3, device=dev)
+        e0 = torch.empty(N, device=dev, dtype=torch.int32); valid_next = torch.empty(N, device=dev, dtype=torch.bool); path_of = torch.empty(N, device=dev, dtype=torch.int32)
+        L.check(lib.iris_pt_primary(scene.handle, eh, L.ptr(rays_o), L.ptr(rays_d), L.ptr(dx_du), L.ptr(dy_dv), L.ptr(dudv), B, S, L.ptr(wi), L.ptr(wo), L.ptr(position),
+                                    L.ptr(normal), L.ptr(e0), L.ptr(valid_next), L.ptr(path_of), L.stream()))
+        L.mark("jitter + primary hit")
+        albedo, rough, metal = _mat_tensors(material_net(position))
+        L.mark("material (primary hits)")
+        # emitter sampling + visibility ray + MIS (:357-382) and BRDF sampling + next intersection (:384-391) behind one launch, with path_tracing_single's constants
+        coef1 = torch.empty(N, 3, device=dev); e1 = torch.empty(N, device=dev, dtype=torch.int32)
+        wi_b = torch.empty(N, 3, device=dev); pdf_b = torch.empty(N, device=dev); w_b = torch.empty(N, 3, device=dev)
+        pos_n = torch.empty(N, 3, device=dev); nrm_n = torch.empty(N, 3, device=dev)
+        tri_n = torch.empty(N, device=dev, dtype=torch.int64); hit_n = torch.empty(N, device=dev, dtype=torch.bool)
+        L.check(lib.iris_pt_bounce(scene.handle, eh, L.ptr(position), L.ptr(normal), L.ptr(wo), L.ptr(albedo), L.ptr(rough), L.ptr(metal), L.ptr(s1), L.ptr(s2), L.ptr(s1b), L.ptr(s2b), N,
+                                   L.ptr(coef1), L.ptr(e1), 1e-6, 1e-6, 1e-6, L.ptr(wi_b), L.ptr(pdf_b), L.ptr(w_b), L.ptr(pos_n), L.ptr(nrm_n), L.ptr(tri_n), L.ptr(hit_n), L.stream()))
+        L.mark("nee + brdf sample + trace (one launch)")
+        rough_n = None if skip_next else material_net(pos_n)["roughness"].detach().to(torch.float32).reshape(-1).contiguous()
+        L.mark("material (sampled hits)")
+        coef2 = torch.empty(N, 3, device=dev); const2 = torch.empty(N, 3, device=dev); e2 = torch.empty(N, device=dev, dtype=torch.int32)
+        L.check(lib.iris_pt_brdf_finish(eh, sh, L.ptr(position), L.ptr(pos_n), L.ptr(nrm_n), L.ptr(wi_b), L.ptr(tri_n), L.ptr(rough_n), L.ptr(pdf_b), L.ptr(w_b), N,
+                                        L.ptr(coef2), L.ptr(const2), L.ptr(e2), None, 0.0, 1e-6, L.stream()))
+        L.mark("finish")
+    out = _PtStepAccumulate.apply(emitter_net.radiance, e0, path_of, e1, coef1, e2, coef2, const2, B, spp, n_calls)
+    L.mark("accumulate")
+    return out
+
+
 def path_tracing_single(scene, emitter_net, material_net, rays_o, rays_d, dx_du, dy_dv, spp, uniforms=None, compact=None, skip_unused_material=True):
     """Path trace the scene with one bounce and power-2 MIS (utils/path_tracing.py:320-407).
 
@@ -256,11 +367,9 @@ def _path_tracing(scene, emitter_net, material_net, rays_o, rays_d, dx_du, dy_dv
         raise L.IrisError("path_tracing: the continuation (trace_indirect) compacts its paths; compact=False is for path_tracing_single")
     u = list(uniforms) if uniforms is not None else None
     trace_rough = 0.6 if full else 0.0
-    # the bound is taken from a network that is EXACTLY NGPBRDF (a subclass may map its roughness otherwise and would inherit the class attribute silently) or that
-    # declares one on the INSTANCE (an explicit opt-in: tools/bench_refine.py's timing wrapper copies its network's).  Caveat: with a non-finite network output the
-    # reference's test `NaN > 0` is False where the skipped path takes it for True: the "same bits" claim holds for finite outputs.
-    from ..model.brdf import NGPBRDF
-    rough_min = NGPBRDF.roughness_min if type(material_net) is NGPBRDF else getattr(material_net, "__dict__", {}).get("roughness_min")
+    # Caveat: with a non-finite network output the reference's test `NaN > 0` is False where the skipped path takes it for True: the "same bits" claim holds for
+    # finite outputs.
+    rough_min = _roughness_bound(material_net)
     skip_next = bool(skip_unused_material) and rough_min is not None and float(rough_min) > trace_rough     # (see path_tracing_single's docstring)
     if u is not None:
         nxt = lambda *shape: L.require_gpu(u.pop(0), torch.float32, "uniforms").reshape(*shape)             # noqa: E731

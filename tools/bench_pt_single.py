@@ -32,16 +32,9 @@ def ngp_material(slf, dev, seed=0):
 L2_PEAK_GBPS = 34500.0        # aggregate L2 bandwidth of the 8 XCDs (MI355X_MICROARCH.md: 4 MiB per XCD, about 34.5 TB/s)
 
 
-def run(room, slf, emi, scene, emitter0, dev, steps=10, warmup=2, rays=8192, spp=32, calls=4, graph=False, material="ngp", skip_unused_material=True, stages=True,
-        bake_mrays_per_s=None, streams=1):
-    """-> dict: Mpaths/s of `steps` training steps (each `calls` forward calls + one backward) on an existing bench workload.
-    material: "ngp" = NGPBRDF with random parameters (the reference's network), "stub" = the closed-form stand-in of rounds 1-3
-    skip_unused_material: path_tracing_single's default (True): the network's second evaluation per call, whose only use is a test its roughness bound decides,
-    is not launched (same outputs); False = evaluated as the reference does
-    stages: also time the stages of a call with HIP events (one extra instrumented step) and price the two leaders: the material network against the L2 line
-    roof, the BRDF-sampled rays against the bake kernel's ray rate on the same scene (bake_mrays_per_s)"""
+def _workload(slf, emi, emitter0, dev, rays, material):
+    """-> (learnable emitter, the `rays` camera rays of the bench view and their differentials, material network, target image rows)"""
     from iris_amd.model.emitter import SLFEmitterLearn
-    from iris_amd.utils.path_tracing import path_tracing_single
     from iris_amd.utils.dataset import real_ldr
     from tools import synth
     import tempfile
@@ -57,11 +50,78 @@ def run(room, slf, emi, scene, emitter0, dev, steps=10, warmup=2, rays=8192, spp
     o, d, dx, dy = real_ldr.to_world(real_ldr.get_direction(K, (H, W)), c2w, True, device=dev)
     g = torch.Generator(device="cpu").manual_seed(0)
     pick = torch.randint(0, H * W, (rays,), generator=g).to(dev)
-    o, d, dx, dy = o[pick], d[pick], dx[pick], dy[pick]
     mat = ngp_material(slf, dev) if material == "ngp" else GpuStub()
-    target = torch.rand(rays, 3, device=dev)
+    return em, (o[pick], d[pick], dx[pick], dy[pick]), mat, torch.rand(rays, 3, device=dev)
 
-    pool = [torch.cuda.Stream(device=dev) for _ in range(streams)] if streams > 1 else []
+
+def run_fused_step(room, slf, emi, scene, emitter0, dev, steps=10, warmup=2, rays=8192, spp=32, calls=4, material="ngp", skip_unused_material=True, repeats=5):
+    """-> dict: the training step (train_emitter.py:181-189: `calls` calls of `spp` samples on the same rays, summed, one backward) three ways in ONE process --
+    fused: one path_tracing_single_step(n_calls=calls); loop: the `calls` path_tracing_single calls (what run() times); one_call: one path_tracing_single of
+    spp * calls samples (another estimator: its mean is not the sum of the calls' rounded means, its draws are not the calls').  The three are timed in turn,
+    `repeats` windows of `steps` steps each (median, with the extremes), so that they share the box's state; then one instrumented fused step for the stage table."""
+    from iris_amd.utils.path_tracing import path_tracing_single, path_tracing_single_step
+    from iris_amd import _lib as L_
+    em, (o, d, dx, dy), mat, target = _workload(slf, emi, emitter0, dev, rays, material)
+
+    def fused():
+        em.radiance.grad = None
+        L = path_tracing_single_step(scene, em, mat, o, d, dx, dy, spp, calls, skip_unused_material=skip_unused_material)
+        ((L / calls - target) ** 2).mean().backward()
+        L_.mark("loss + backward")
+
+    def loop():
+        em.radiance.grad = None
+        loss = 0
+        for _ in range(calls):
+            loss = loss + ((path_tracing_single(scene, em, mat, o, d, dx, dy, spp, skip_unused_material=skip_unused_material) - target) ** 2).mean()
+        loss.backward()
+
+    def one_call():
+        em.radiance.grad = None
+        ((path_tracing_single(scene, em, mat, o, d, dx, dy, spp * calls, skip_unused_material=skip_unused_material) - target) ** 2).mean().backward()
+    modes = {"fused_step": fused, "loop_of_calls": loop, "one_call_of_spp_x_calls": one_call}
+    for fn in modes.values():
+        for _ in range(warmup):
+            fn()
+    paths = steps * calls * rays * spp
+    rates = {k: [] for k in modes}
+    for _ in range(repeats):
+        for k, fn in modes.items():
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(steps):
+                fn()
+            torch.cuda.synchronize()
+            rates[k].append(paths / (time.perf_counter() - t0) / 1e6)
+    rows = {k: {"mpaths_per_s": round(float(np.median(v)), 2), "min": round(min(v), 2), "max": round(max(v), 2), "ms_per_step": round(calls * rays * spp / float(np.median(v)) / 1e3, 3)}
+            for k, v in rates.items()}
+    with L_.StageTimer() as tm:
+        fused()
+    grad_rows = int((em.radiance.grad.abs().sum(-1) > 0).sum())
+    with L_.StageTimer() as tm1:           # the same path count with the two tracing stages as two launches side by side (main + side stream): what the merged launch replaces
+        one_call()
+    return {"metric": "path_tracing_single_step fwd+bwd (the training step of BASELINE configs[4] as one fused call)", "value": rows["fused_step"]["mpaths_per_s"], "unit": "Mpaths/s",
+            "rows": rows, "fused_over_loop": round(rows["fused_step"]["mpaths_per_s"] / rows["loop_of_calls"]["mpaths_per_s"], 3),
+            "fused_over_one_call": round(rows["fused_step"]["mpaths_per_s"] / rows["one_call_of_spp_x_calls"]["mpaths_per_s"], 3),
+            "stages_ms_per_fused_step": {k: round(v, 4) for k, v in tm.ms().items()},
+            "stages_ms_of_the_one_call": {k: round(v, 4) for k, v in tm1.ms().items()},
+            "config": {"rays": rays, "spp": spp, "calls_per_step": calls, "paths_per_step": calls * rays * spp, "steps_per_window": steps, "windows": repeats,
+                       "triangles": int(room["faces"].shape[0]), "material": material, "skip_unused_material": bool(skip_unused_material and material == "ngp")},
+            "note": "median of the windows, the three modes timed in turn in one process; host clock around work that ends in a device synchronise; stages: HIP events, one instrumented step",
+            "grad_nonzero_rows": grad_rows}
+
+
+def run(room, slf, emi, scene, emitter0, dev, steps=10, warmup=2, rays=8192, spp=32, calls=4, graph=False, material="ngp", skip_unused_material=True, stages=True,
+        bake_mrays_per_s=None, streams=1):
+    """-> dict: Mpaths/s of `steps` training steps (each `calls` forward calls + one backward) on an existing bench workload.
+    material: "ngp" = NGPBRDF with random parameters (the reference's network), "stub" = the closed-form stand-in of rounds 1-3
+    skip_unused_material: path_tracing_single's default (True): the network's second evaluation per call, whose only use is a test its roughness bound decides,
+    is not launched (same outputs); False = evaluated as the reference does
+    stages: also time the stages of a call with HIP events (one extra instrumented step) and price the two leaders: the material network against the L2 line
+    roof, the BRDF-sampled rays against the bake kernel's ray rate on the same scene (bake_mrays_per_s)"""
+    from iris_amd.utils.path_tracing import path_tracing_single
+    em, (o, d, dx, dy), mat, target = _workload(slf, emi, emitter0, dev, rays, material)
+
+    pool =[torch.cuda.Stream(device=dev) for _ in range(streams)] if streams > 1 else []
 
     def step():
         em.radiance.grad = None
@@ -168,6 +228,8 @@ def main():
     ap.add_argument("--tris", type=int, default=1_000_000)
     ap.add_argument("--streams", type=int, default=1, help="issue the independent forward calls of a step round-robin on this many HIP streams")
     ap.add_argument("--graph", action="store_true", help="capture the training step in a HIP graph (torch.cuda.CUDAGraph) and replay it")
+    ap.add_argument("--fused-step", action="store_true", help="time one path_tracing_single_step(n_calls=calls) + one backward per step, and in the same process the loop of "
+                                                                "`calls` calls and the one call of spp * calls samples")
     ap.add_argument("--material", choices=["ngp", "stub"], default="ngp")
     ap.add_argument("--no-skip", action="store_true", help="evaluate the material network at the sampled hits as the reference does (path_tracing_single skip_unused_material=False)")
     ap.add_argument("--debug-set", action="append", default=[], metavar="KEY=VALUE", help="iris_debug_set option (experiments), e.g. joint_max_rays=0")
@@ -182,6 +244,11 @@ def main():
         L.debug_set(kv.split("=")[0], int(kv.split("=")[1]))
     ns = argparse.Namespace(scene_seed=1, tris=args.tris, slf_res=256, layout=0)
     room, slf, emi, scene, emitter0 = bench.build_workload(ns, dev)
+    if args.fused_step:
+        if args.graph or args.streams > 1:
+            ap.error("--fused-step times the fused call against the plain loop: not with --graph / --streams")
+        print(json.dumps(run_fused_step(room, slf, emi, scene, emitter0, dev, args.steps, args.warmup, args.rays, args.spp, args.calls, material=args.material, skip_unused_material=not args.no_skip)))
+        return
     print(json.dumps(run(room, slf, emi, scene, emitter0, dev, args.steps, args.warmup, args.rays, args.spp, args.calls, graph=args.graph, material=args.material, skip_unused_material=not args.no_skip, streams=args.streams)))
 
 
