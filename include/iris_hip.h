@@ -292,12 +292,13 @@ IRIS_API int iris_denoise(const float *normal, const float *position, const uint
                  float *const *out, int iterations, float sigma_l, float sigma_n, float sigma_p, void *workspace, uint64_t workspace_bytes,
                  iris_stream_t);
 
-/* ---- the material network of the refine / emitter-training stages, inference only ----------------------- */
+/* ---- the material network of the refine / emitter-training / BRDF-training stages ------------------------ */
 /* NGPBRDF (model/brdf.py:213-260; loaded and frozen at refine_shading.py:83-92, train_emitter.py:67-77): tiny-cuda-nn
  * NetworkWithInputEncoding(3, 5, HashGrid{n_levels 32, 2 features, log2_hashmap_size 19, base 16, per_level_scale 1.3},
  * FullyFusedMLP{64 neurons, 2 hidden layers, ReLU}) + sigmoid.  params: HOST float32[n_params] = the `mlp.params` tensor of the reference's
  * state dict ([MLP weights 64x64, 64x64, 16x64 row-major | grid tables level by level, 2 features per entry]); n_params must equal
- * iris_ngp_n_params().  tiny-cuda-nn is third party: the published algorithm is implemented, parity unpinned (oracle/ngp_torch.py). */
+ * iris_ngp_n_params().  params may be NULL: an all-zero network whose parameters live on the device and arrive through iris_ngp_set_params_dev.
+ * tiny-cuda-nn is third party: the published algorithm is implemented, parity unpinned (oracle/ngp_torch.py). */
 IRIS_API int64_t iris_ngp_n_params(void);
 IRIS_API int iris_ngp_create(const float *params, int64_t n_params, double voxel_min, double voxel_max, int device, iris_ngp **out);
 /* forward(position): position (N,3) f32 world space -> albedo (N,3), roughness (N) in [0.02,1], metallic (N), all f32 device pointers.
@@ -305,6 +306,21 @@ IRIS_API int iris_ngp_create(const float *params, int64_t n_params, double voxel
  * in f32 afterwards).  The handle owns the feature buffer the two kernels of a call exchange (2^20 points x 128 B); calls on ONE handle from different
  * streams or host threads are serialised by the library (a device-side event wait, a host mutex); different handles are independent. */
 IRIS_API int iris_ngp_forward(const iris_ngp *, const float *position, int64_t N, float *albedo, float *roughness, float *metallic, iris_stream_t);
+/* Training (train_brdf_crf.py:163-207: material(positions) -> loss -> backward() -> Adam over mlp.params).
+ * set_params_dev: params_dev = DEVICE float32[n_params] (16-byte aligned), the master copy an optimizer updates -> the handle's half weights and tables,
+ * rounded to nearest even as iris_ngp_create rounds; one kernel on the stream, no host copy.
+ * backward: the gradient of the parameters given the cotangents of forward's three outputs; position has no gradient (the reference's comes from
+ * ray_intersect).  Straight-through: every rounding to half of the forward has derivative 1; d/dz of the output stage is g * s (1 - s) with s the forward's
+ * half-grid sigmoid (* 0.98 for roughness); ReLU masks from the recomputed pre-activations.  Nothing is saved by forward: backward re-encodes and recomputes.
+ * dz is multiplied by loss_scale before it is rounded to half (tiny-cuda-nn's default is 128) and the result divided by it again; a scaled gradient beyond
+ * the half range gives inf, as in the library.  grad_params: DEVICE float32[n_params], ADDED to.  Entries [0, 9216) (the three matrices) are summed in a
+ * fixed order: bitwise reproducible; the table entries receive f32 atomic adds: reproducible up to summation order.  Rows 5..15 of the padded output
+ * matrix receive exactly 0.  workspace: DEVICE, 16-byte aligned, at least iris_ngp_backward_workspace_bytes(N) bytes, free for reuse once the stream has
+ * passed the call.  N = 0 is a no-op.  Both calls are ordered against the other calls of the same handle as forwards are. */
+IRIS_API int iris_ngp_set_params_dev(iris_ngp *, const float *params_dev, int64_t n_params, iris_stream_t);
+IRIS_API uint64_t iris_ngp_backward_workspace_bytes(int64_t N);
+IRIS_API int iris_ngp_backward(const iris_ngp *, const float *position, int64_t N, const float *g_albedo, const float *g_roughness, const float *g_metallic,
+                      float loss_scale, float *grad_params, void *workspace, uint64_t workspace_bytes, iris_stream_t);
 IRIS_API void iris_ngp_destroy(iris_ngp *);
 
 /* ---- OpenEXR ZIP / ZIPS writer, device half ------------------------------------------------------------- */

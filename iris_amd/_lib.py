@@ -63,6 +63,9 @@ PROTOTYPES = {
     "iris_ngp_n_params": [],
     "iris_ngp_create": [_P, _I64, C.c_double, C.c_double, C.c_int, _P],
     "iris_ngp_forward": [_P, _P, _I64, _P, _P, _P, _P],
+    "iris_ngp_set_params_dev": [_P, _P, _I64, _P],
+    "iris_ngp_backward_workspace_bytes": [_I64],
+    "iris_ngp_backward": [_P, _P, _I64, _P, _P, _P, _F, _P, _P, C.c_uint64, _P],
     "iris_ngp_destroy": [_P],
     "iris_debug_ngp_encode": [_P, _P, _I64, _P, _P],
     "iris_sample_emitter": [_P, _P, _P, _P, _I64, _P, _P, _P, _P],
@@ -100,7 +103,7 @@ PROTOTYPES = {
 }
 _RESTYPE = {"iris_scene_destroy": None, "iris_slf_destroy": None, "iris_emitter_destroy": None,
             "iris_last_error": C.c_char_p, "iris_version": C.c_char_p, "iris_debug_build_flags": C.c_char_p, "iris_debug_source_hash": C.c_char_p, "iris_ngp_n_params": C.c_int64, "iris_ngp_destroy": None, "iris_bake_workspace_bytes": C.c_uint64, "iris_pt_compact_workspace_bytes": C.c_uint64, "iris_denoise_workspace_bytes": C.c_uint64,
-            "iris_exr_zip_workspace_bytes": C.c_uint64}
+            "iris_exr_zip_workspace_bytes": C.c_uint64, "iris_ngp_backward_workspace_bytes": C.c_uint64}
 
 _lib = None
 

@@ -306,7 +306,7 @@ extern "C" IRIS_API int iris_slf_create_dev(const int64_t* inds_dev, int H, cons
 extern "C" IRIS_API void iris_slf_destroy(iris_slf* s) { delete s; }
 
 // ======================================================================================================
-// NGPBRDF (model/brdf.py:213-260): hash-grid encoding + MLP, inference
+// NGPBRDF (model/brdf.py:213-260): hash-grid encoding + MLP, forward and parameter gradient
 // ======================================================================================================
 struct iris_ngp {
     int device = 0;
@@ -316,8 +316,9 @@ struct iris_ngp {
     DevBuf d_feat;              // [32 levels][kChunk] half2: the encoded features of one chunk of points
     float vmin = 0.f, den = 1.f;
     uint64_t n_entries = 0;
-    // d_feat is the handle's ONE scratch buffer: forwards of one handle are serialised on the device -- a call on another stream than the previous call's first
-    // waits (on the device, not the host) for the event that call recorded behind its last kernel.  Host threads are serialised by the mutex.
+    // d_feat is the handle's ONE scratch buffer: forwards and backwards of one handle are serialised on the device -- a call on another stream than the previous
+    // call's first waits (on the device, not the host) for the event that call recorded behind its last kernel; a parameter refresh (iris_ngp_set_params_dev
+    // rewrites d_w / d_grid) is ordered the same way.  Host threads are serialised by the mutex.
     mutable std::mutex mu;
     mutable DevEvent last_use;
     mutable hipStream_t last_stream = nullptr;
@@ -349,20 +350,23 @@ extern "C" IRIS_API int64_t iris_ngp_n_params(void) {
 }
 extern "C" IRIS_API int iris_ngp_create(const float* params, int64_t n_params, double voxel_min, double voxel_max, int device, iris_ngp** out) {
     API_BEGIN
-    if (!out || !params) return fail(IRIS_ERR_ARG, "iris_ngp_create: bad arguments");
+    if (!out) return fail(IRIS_ERR_ARG, "iris_ngp_create: bad arguments");
     HIP_TRY(hipSetDevice(device));              // (before anything is allocated: an invalid device leaves nothing behind)
     auto g = std::make_unique<iris_ngp>();
     g->device = device;
     g->n_entries = ngp_levels(g->lv);
     if (n_params != (int64_t)kNgpMlpParams + (int64_t)g->n_entries * 2)
         return fail(IRIS_ERR_ARG, "iris_ngp_create: mlp.params has " + std::to_string(n_params) + " entries, the NGPBRDF configuration has " + std::to_string(iris_ngp_n_params()));
-    std::vector<uint16_t> h((size_t)n_params);
-    for (int64_t i = 0; i < n_params; ++i) h[(size_t)i] = f32_to_f16_bits(params[i]);
+    std::vector<uint16_t> h(params ? (size_t)n_params : 0);
+    for (int64_t i = 0; params && i < n_params; ++i) h[(size_t)i] = f32_to_f16_bits(params[i]);
     if (g->d_w.alloc((size_t)kNgpMlpParams * 2) != hipSuccess || g->d_grid.alloc((size_t)g->n_entries * 4) != hipSuccess ||
         g->d_feat.alloc((size_t)kNgpLevels * kNgpChunk * 4) != hipSuccess)
         return fail(IRIS_ERR_HIP, "iris_ngp_create: out of device memory");
     if (g->last_use.create() != hipSuccess) return fail(IRIS_ERR_HIP, "iris_ngp_create: hipEventCreate failed");
-    if (g->d_w.upload(h.data(), (size_t)kNgpMlpParams * 2) != hipSuccess || g->d_grid.upload(h.data() + kNgpMlpParams, (size_t)g->n_entries * 4) != hipSuccess)
+    if (!params) {            // all-zero parameters: the caller's live on the device and arrive through iris_ngp_set_params_dev
+        if (hipMemset(g->d_w.p, 0, (size_t)kNgpMlpParams * 2) != hipSuccess || hipMemset(g->d_grid.p, 0, (size_t)g->n_entries * 4) != hipSuccess)
+            return fail(IRIS_ERR_HIP, "iris_ngp_create: hipMemset failed");
+    } else if (g->d_w.upload(h.data(), (size_t)kNgpMlpParams * 2) != hipSuccess || g->d_grid.upload(h.data() + kNgpMlpParams, (size_t)g->n_entries * 4) != hipSuccess)
         return fail(IRIS_ERR_HIP, "iris_ngp_create: upload failed");
     g->vmin = (float)voxel_min;
     g->den = (float)(voxel_max - voxel_min);           // (the difference of the two python floats, taken in double, enters the float32 tensor arithmetic as one scalar)
@@ -386,6 +390,66 @@ extern "C" IRIS_API int iris_ngp_forward(const iris_ngp* g, const float* positio
         hipLaunchKernelGGL(ngp_encode_kernel, dim3((a.n + 255) / 256, kNgpLevels), dim3(256), 0, st, a);
         const int tiles = (a.n + 31) / 32;
         hipLaunchKernelGGL(ngp_mlp_kernel, dim3(std::min(std::max((tiles + 3) / 4, 1), 2048)), dim3(256), 0, st, a);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->last_use.ev, st));
+    g->last_stream = st; g->used = true;
+    return IRIS_OK;
+    API_END
+}
+extern "C" IRIS_API int iris_ngp_set_params_dev(iris_ngp* g, const float* params_dev, int64_t n_params, iris_stream_t stream) {
+    API_BEGIN
+    if (!g || !params_dev) return fail(IRIS_ERR_ARG, "iris_ngp_set_params_dev: bad arguments");
+    if (n_params != (int64_t)kNgpMlpParams + (int64_t)g->n_entries * 2)
+        return fail(IRIS_ERR_ARG, "iris_ngp_set_params_dev: mlp.params has " + std::to_string(n_params) + " entries, the NGPBRDF configuration has " + std::to_string(iris_ngp_n_params()));
+    if ((uintptr_t)params_dev % 16) return fail(IRIS_ERR_ARG, "iris_ngp_set_params_dev: params_dev must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(g->device));
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(g->mu);
+    if (g->used && g->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, g->last_use.ev, 0));      // a forward in flight on another stream still reads the old parameters
+    const int64_t n8 = n_params / 8;
+    hipLaunchKernelGGL(ngp_params_cast_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, (const float4*)params_dev, n8, (_Float16*)g->d_w.p, (_Float16*)g->d_grid.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->last_use.ev, st));
+    g->last_stream = st; g->used = true;
+    return IRIS_OK;
+    API_END
+}
+static int64_t ngp_bwd_plane(int64_t N) { return std::min<int64_t>((std::max<int64_t>(N, 1) + 63) / 64 * 64, kNgpChunk); }
+extern "C" IRIS_API uint64_t iris_ngp_backward_workspace_bytes(int64_t N) {
+    // dX planes [32 levels][min(N, chunk)] float2 + one weight-gradient slab per workgroup of ngp_mlp_bwd_kernel
+    return (uint64_t)kNgpLevels * (uint64_t)ngp_bwd_plane(N) * 8 + (uint64_t)kNgpBwdMaxGroups * kNgpMlpParams * 4;
+}
+extern "C" IRIS_API int iris_ngp_backward(const iris_ngp* g, const float* position, int64_t N, const float* g_albedo, const float* g_roughness, const float* g_metallic,
+                                          float loss_scale, float* grad_params, void* workspace, uint64_t workspace_bytes, iris_stream_t stream) {
+    API_BEGIN
+    if (!g || N < 0 || (N > 0 && (!position || !g_albedo || !g_roughness || !g_metallic || !grad_params || !workspace))) return fail(IRIS_ERR_ARG, "iris_ngp_backward: bad arguments");
+    if (!(loss_scale > 0.f) || !std::isfinite(loss_scale)) return fail(IRIS_ERR_ARG, "iris_ngp_backward: loss_scale must be positive and finite");
+    if (N == 0) return IRIS_OK;
+    if (workspace_bytes < iris_ngp_backward_workspace_bytes(N))
+        return fail(IRIS_ERR_ARG, "iris_ngp_backward: workspace has " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(N) + " points need " + std::to_string(iris_ngp_backward_workspace_bytes(N)));
+    if ((uintptr_t)workspace % 16) return fail(IRIS_ERR_ARG, "iris_ngp_backward: workspace must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(g->device));
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(g->mu);
+    if (g->used && g->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, g->last_use.ev, 0));      // the previous call of this handle still owns d_feat
+    NgpBwdArgs b{};
+    NgpArgs& a = b.f;
+    a.lv = g->lv; a.grid = (const uint32_t*)g->d_grid.p; a.w = (const _Float16*)g->d_w.p; a.pos = position; a.feat = (uint32_t*)g->d_feat.p;
+    a.n_chunk = kNgpChunk; a.vmin = g->vmin; a.den = g->den;
+    b.g_albedo = g_albedo; b.g_rough = g_roughness; b.g_metal = g_metallic;
+    b.n_plane = (int)ngp_bwd_plane(N);
+    b.dx = (float2*)workspace;
+    b.slabs = (float*)((char*)workspace + (size_t)kNgpLevels * b.n_plane * 8);
+    b.grad = grad_params; b.loss_scale = loss_scale; b.inv_scale = 1.0f / loss_scale;
+    for (int64_t n0 = 0; n0 < N; n0 += kNgpChunk) {          // (stream-ordered, as the forward: a chunk's planes and slabs are consumed before the next chunk overwrites them)
+        a.n0 = n0; a.n = (int)std::min<int64_t>(kNgpChunk, N - n0);
+        const int tiles = (a.n + 31) / 32;
+        b.n_slabs = std::min(std::max((tiles + 3) / 4, 1), kNgpBwdMaxGroups);
+        hipLaunchKernelGGL(ngp_encode_kernel, dim3((a.n + 255) / 256, kNgpLevels), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(ngp_mlp_bwd_kernel, dim3(b.n_slabs), dim3(256), 0, st, b);
+        hipLaunchKernelGGL(ngp_wgrad_reduce_kernel, dim3(kNgpMlpParams / 256), dim3(256), 0, st, b);
+        hipLaunchKernelGGL(ngp_grid_bwd_kernel, dim3((a.n + 255) / 256, kNgpLevels), dim3(256), 0, st, b);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(g->last_use.ev, st));

@@ -146,16 +146,55 @@ class _TcnnParams(nn.Module):
         self.params = nn.Parameter(torch.zeros(n, dtype=torch.float32), requires_grad=False)
 
 
+class _NGPForward(torch.autograd.Function):
+    """`mlp.params` -> (albedo, roughness, metallic) for fixed positions: the forward is the inference path's iris_ngp_forward (the same bits), the backward
+    iris_ngp_backward, which recomputes the forward from the positions (nothing is saved but the positions themselves)."""
+
+    @staticmethod
+    def forward(ctx, params, net, pos):
+        ctx.net, ctx.pos = net, pos
+        return net._run(pos)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_albedo, g_rough, g_metal):
+        net, pos = ctx.net, ctx.pos
+        N, dev = pos.shape[0], pos.device
+        p = net.mlp.params
+        grad = torch.zeros(p.numel(), device=dev, dtype=torch.float32)
+        if N > 0:
+            def cot(g, shape):
+                return torch.zeros(shape, device=dev) if g is None else g.to(torch.float32).contiguous()
+            g_albedo, g_rough, g_metal = cot(g_albedo, (N, 3)), cot(g_rough, (N,)), cot(g_metal, (N,))
+            with torch.cuda.device(dev):
+                nbytes = int(L.lib().iris_ngp_backward_workspace_bytes(N))
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                L.check(L.lib().iris_ngp_backward(net._handle(dev), L.ptr(pos), N, L.ptr(g_albedo), L.ptr(g_rough), L.ptr(g_metal), float(net.loss_scale),
+                                                  L.ptr(grad), L.ptr(ws), nbytes, L.stream()))
+        return grad, None, None
+
+
 class NGPBRDF(BaseBRDF):
-    """Hash-grid material network, INFERENCE ONLY (model/brdf.py:213-260; the reference loads it from a checkpoint and freezes it in refine_shading.py:83-92
-    and train_emitter.py:67-77): HashGrid{32 levels x 2 features, 2^19 entries, base 16, x1.3} -> FullyFusedMLP{64 x 2, ReLU} -> sigmoid, as two HIP
-    kernels (level-major gathers; the perceptron on the matrix cores, iris_amd/csrc/iris_ngp.h).  tiny-cuda-nn is third party and CUDA only: its published
-    algorithm is implemented, parity unpinned (oracle/ngp_torch.py).  No backward pass: training the material network is train_brdf_crf's job (out of scope)."""
+    """Hash-grid material network (model/brdf.py:213-260; the reference trains it in train_brdf_crf.py:163-207 and loads it frozen in refine_shading.py:83-92
+    and train_emitter.py:67-77): HashGrid{32 levels x 2 features, 2^19 entries, base 16, x1.3} -> FullyFusedMLP{64 x 2, ReLU} -> sigmoid, as HIP kernels
+    (level-major gathers; the perceptron on the matrix cores, iris_amd/csrc/iris_ngp.h).  tiny-cuda-nn is third party and CUDA only: its published
+    algorithm is implemented, parity unpinned (oracle/ngp_torch.py).
+
+    Training: with `mlp.params` on the GPU and requiring grad, forward runs under autograd and `backward()` fills `mlp.params.grad` (iris_ngp_backward:
+    straight-through over every rounding to half, the forward recomputed from the positions, the matrices' gradient bitwise reproducible, the tables' gradient
+    accumulated with float atomics).  `position` never gets a gradient -- the reference's positions come from `ray_intersect` and need none -- and a
+    position that requires grad raises.  A frozen network (the constructor's state, and what load_ngpbrdf returns) takes the inference path unchanged.
+    The constructor leaves the parameters all-zero and frozen, since existing callers load a checkpoint; a trainer calls init_parameters(), .to(device) and
+    mlp.params.requires_grad_(True)."""
 
     # roughness = sigmoid(.) * 0.98 + 0.02 (model/brdf.py:258): never below 0.02 for finite network outputs.  path_tracing_single uses its SECOND evaluation of the
     # network (mat_next, utils/path_tracing.py:392) only for the test roughness > trace_roughness = 0.0 (model/emitter.py:209), whose outcome this bound decides:
     # iris_amd.utils.path_tracing skips that evaluation when the network declares a bound above trace_roughness (same outputs, bit for bit).
     roughness_min = 0.02
+    # The backward multiplies the output-stage gradient by this before rounding it to half and divides the result by it again (tiny-cuda-nn's default): small
+    # loss gradients do not flush to zero.  A scaled gradient beyond the half range (65504) becomes inf, and so does the parameter gradient, as in the library:
+    # lower the value if the loss gradients are large.
+    loss_scale = 128.0
 
     def __init__(self, voxel_min, voxel_max):
         super().__init__()
@@ -163,14 +202,50 @@ class NGPBRDF(BaseBRDF):
         self.mlp = _TcnnParams(int(L.lib().iris_ngp_n_params()))
         self._h, self._h_key = None, None
 
+    def init_parameters(self, seed=1337):
+        """tiny-cuda-nn's initial distributions, drawn from a torch generator on the CPU: tables U(-1e-4, 1e-4), the three matrices Xavier-uniform
+        (+-sqrt(6 / (fan_in + fan_out)), the padded output matrix as 16 x 64).  The bits do not equal the library's RNG: parity unpinned.
+        The constructor's all-zero network cannot be trained: with zero weights every gradient is zero, for ever."""
+        import math
+        g = torch.Generator().manual_seed(int(seed))
+        p = self.mlp.params
+        new = torch.empty(p.numel(), dtype=torch.float32)
+        o = 0
+        for rows, cols in ((64, 64), (64, 64), (16, 64)):
+            a = math.sqrt(6.0 / (rows + cols))
+            new[o:o + rows * cols] = (torch.rand(rows * cols, generator=g) * 2 - 1) * a
+            o += rows * cols
+        new[o:] = (torch.rand(p.numel() - o, generator=g) * 2 - 1) * 1e-4
+        with torch.no_grad():
+            p.copy_(new.to(p.device))
+        return self
+
     def _handle(self, device):
         import ctypes as C
         p = self.mlp.params
+        idx = L.device_index(device)
+        if p.is_cuda:
+            # parameters that live on the GPU (a network being trained): ONE handle, refreshed on the device whenever the tensor has been written to
+            # (every optimizer step bumps _version) -- no 112 MB round trip through the host
+            if p.device.index != idx:
+                raise L.IrisError(f"NGPBRDF: mlp.params is on {p.device}, position on cuda:{idx}")
+            key = ("dev", idx, p.data_ptr(), p._version)
+            if self._h is None or self._h_key is None or self._h_key[:3] != key[:3]:
+                self._free()
+                h = C.c_void_p()
+                L.check(L.lib().iris_ngp_create(None, p.numel(), self.voxel_min, self.voxel_max, idx, C.byref(h)))
+                self._h, self._h_key = h, None
+            if self._h_key != key:
+                src = p.detach()
+                src = src if src.is_contiguous() and src.dtype == torch.float32 else src.to(torch.float32).contiguous()
+                with torch.cuda.device(p.device):
+                    L.check(L.lib().iris_ngp_set_params_dev(self._h, L.ptr(src), src.numel(), L.stream()))
+                self._h_key = key
+            return self._h
         key = (str(device), p.data_ptr(), p._version)
         if self._h is None or self._h_key != key:
             self._free()
             host = p.detach().to("cpu", torch.float32).contiguous()
-            idx = L.device_index(device)
             h = C.c_void_p()
             L.check(L.lib().iris_ngp_create(C.c_void_p(host.data_ptr()), host.numel(), self.voxel_min, self.voxel_max, idx, C.byref(h)))
             self._h, self._h_key = h, key
@@ -194,16 +269,29 @@ class NGPBRDF(BaseBRDF):
         state["_h"], state["_h_key"] = None, None
         return state
 
-    def forward(self, position):
-        """position Bx3 (world space) -> {'albedo': Bx3, 'roughness': Bx1 in [0.02, 1], 'metallic': Bx1}  (model/brdf.py:243-260)"""
-        L.no_autograd("NGPBRDF.forward", position)
-        position = L.require_gpu(position, torch.float32, "position")
-        shape = position.shape[:-1]
-        pos = position.reshape(-1, 3)
+    def _run(self, pos):
         N, dev = pos.shape[0], pos.device
         albedo = torch.empty(N, 3, device=dev); rough = torch.empty(N, device=dev); metal = torch.empty(N, device=dev)
         with torch.cuda.device(dev):
             L.check(L.lib().iris_ngp_forward(self._handle(dev), L.ptr(pos), N, L.ptr(albedo), L.ptr(rough), L.ptr(metal), L.stream()))
+        return albedo, rough, metal
+
+    def forward(self, position):
+        """position Bx3 (world space) -> {'albedo': Bx3, 'roughness': Bx1 in [0.02, 1], 'metallic': Bx1}  (model/brdf.py:243-260).
+        Differentiable with respect to mlp.params when they require grad (and grad mode is on); never with respect to position, which raises if it
+        requires grad: the reference's positions are ray_intersect's hit points."""
+        L.no_autograd("NGPBRDF.forward", position)
+        position = L.require_gpu(position, torch.float32, "position")
+        shape = position.shape[:-1]
+        pos = position.reshape(-1, 3)
+        p = self.mlp.params
+        if torch.is_grad_enabled() and p.requires_grad:
+            if not p.is_cuda:
+                raise L.IrisError("NGPBRDF.forward: mlp.params requires grad but lives on the CPU; move the network to the GPU first (net.to(device)): "
+                                  "the backward pass and the parameter refresh run on the device")
+            albedo, rough, metal = _NGPForward.apply(p, self, pos.detach())
+        else:
+            albedo, rough, metal = self._run(pos)
         return {"albedo": albedo.reshape(*shape, 3), "roughness": rough.reshape(*shape, 1), "metallic": metal.reshape(*shape, 1)}
 
 

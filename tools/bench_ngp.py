@@ -3,6 +3,7 @@
 one MI355X, random-initialised parameters of the reference's configuration (model/brdf.py:222-241).
 
     python tools/bench_ngp.py [--points 4194304] [--steps 10]
+    python tools/bench_ngp.py --backward [--steps 10]      # forward + backward (training), written to profiles/ngp_backward.json
 
 Two input distributions: positions drawn uniformly in the scene box (incoherent: every level's gathers scatter over its whole table) and the
 primary hits of a 1080p view of the bench room in pixel-block order (what refine_shading feeds: neighbouring pixels share cells on the coarse levels).
@@ -20,11 +21,74 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 
+def backward(args):
+    """forward + backward of a trainable network at the reference's trainer batch (8192 points) and at 262 144: median time per call (HIP events), the
+    per-kernel split (torch.profiler's device-side kernel durations, averaged over the timed calls: encode counts twice, the forward's and the backward's
+    re-encode), the device-side parameter refresh, and the grid backward's added bytes per second (32 levels x 8 corners x 2 features x 4 B per point) next to
+    the guide's float-atomic rate."""
+    from iris_amd.model.brdf import NGPBRDF
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    net = NGPBRDF(-3.0, 3.0)
+    net.load_state_dict({"mlp.params": (torch.rand(net.mlp.params.numel(), generator=g) * 2 - 1) * 0.3})
+    net.to(dev)
+    net.mlp.params.requires_grad_(True)
+    out = {"what": "NGPBRDF forward + backward (iris_ngp_forward, iris_ngp_backward, iris_ngp_set_params_dev)", "box": torch.cuda.get_device_name(0),
+           "loss_scale": net.loss_scale, "atomic_floor_GBps_guide": 1300.0}
+
+    def step(pos, cot):
+        net.mlp.params.grad = None
+        with torch.no_grad():
+            net.mlp.params.mul_(1.0)                     # what an optimizer step does to the handle: the next forward refreshes it on the device
+        o = net(pos)
+        torch.autograd.backward([o["albedo"], o["roughness"], o["metallic"]], cot)
+
+    for n in (8192, 262144):
+        pos = (torch.rand(n, 3, generator=g) * 6 - 3).to(dev)
+        cot = [torch.randn(n, k, generator=g).to(dev) for k in (3, 1, 1)]
+        for _ in range(3):
+            step(pos, cot)
+        torch.cuda.synchronize()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        ev[0].record()
+        for i in range(args.steps):
+            step(pos, cot); ev[i + 1].record()
+        torch.cuda.synchronize()
+        ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps))
+        row = {"points": n, "ms_per_step_median": round(ms[len(ms) // 2], 3), "step": "parameter refresh + forward + backward (incl. zeroing the 112 MB gradient)"}
+        try:
+            from torch.profiler import ProfilerActivity, profile
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                for _ in range(args.steps):
+                    step(pos, cot)
+                torch.cuda.synchronize()
+            split = {}
+            for e in prof.key_averages():
+                m = [k for k in ("ngp_encode_kernel", "ngp_mlp_bwd_kernel", "ngp_mlp_kernel", "ngp_wgrad_reduce_kernel", "ngp_grid_bwd_kernel", "ngp_params_cast_kernel") if k in e.key]
+                if m:
+                    t = getattr(e, "device_time_total", None) or getattr(e, "cuda_time_total", 0.0)
+                    split[m[0]] = round(split.get(m[0], 0.0) + t / args.steps / 1e3, 4)
+            row["kernel_ms_per_step"] = split
+            if split.get("ngp_grid_bwd_kernel"):
+                row["grid_bwd_added_GBps"] = round(32 * 8 * 2 * 4 * n / (split["ngp_grid_bwd_kernel"] * 1e-3) / 1e9, 1)
+        except Exception as e:     # noqa
+            row["kernel_ms_per_step"] = {"unavailable": repr(e)}
+        out["n%d" % n] = row
+    line = json.dumps(out)
+    print(line)
+    with open(args.out or os.path.join(REPO, "profiles", "ngp_backward.json"), "w") as f:
+        f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=1 << 22)
     ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--backward", action="store_true", help="time forward + backward of a trainable network instead")
+    ap.add_argument("--out", default=None, help="--backward: where the JSON line goes (default profiles/ngp_backward.json)")
     args = ap.parse_args()
+    if args.backward:
+        return backward(args)
     from iris_amd.model.brdf import NGPBRDF
     from iris_amd import _lib as L
     dev = torch.device("cuda:0")
