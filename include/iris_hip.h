@@ -323,6 +323,44 @@ IRIS_API int iris_ngp_backward(const iris_ngp *, const float *position, int64_t 
                       float loss_scale, float *grad_params, void *workspace, uint64_t workspace_bytes, iris_stream_t);
 IRIS_API void iris_ngp_destroy(iris_ngp *);
 
+/* ---- the BRDF trainer's roughness-metallic propagation regulariser (train_brdf_crf.py:212-290) ------------------------ */
+/* All six calls work on the batch SORTED by segment id: sorted_seg, order = torch.sort(segmentation, stable=True) (N int64 each; a stable sort keeps a
+ * segment's pixels in ascending index, the order of the reference's torch.where).  Position q of the sorted batch holds pixel order[q].  N < 2^31 - 64.
+ * runs: (N, 2) int32, per position the (start, count) of its segment's run, from two binary searches in sorted_seg; no segment count is ever needed
+ * (sum over segments of a mean = sum over pixels of term / count).  Nothing here synchronises or depends on data in the size of an output. */
+IRIS_API int iris_prop_runs(const int64_t *sorted_seg, int64_t N, int32_t *runs, iris_stream_t);
+/* The local ranks the Philox mode of the semantic branch draws: draws (N, K) int64 indexed by PIXEL, draws[i][k] in [0, count of i's segment) =
+ * word (k / 64) % 4 of the Philox4x32-10 block with counter (64 (k / 256) + k % 64, i, 0x50524F50, 0) and key seed, modulo the count (every row is
+ * filled, also those of segments with fewer than K members, which the loss does not use). */
+IRIS_API int iris_prop_draws(const int32_t *runs, const int64_t *order, int64_t N, int K, uint64_t seed, int64_t *draws, iris_stream_t);
+/* Semantic branch (:243-290).  roughness, metallic (N), albedo, positions (N, 3) by pixel.  normalise != 0: positions = (positions - voxel_min) /
+ * (voxel_max - voxel_min) * 2 - 1 first (:244).  Pixel i of a segment with c members mem[0..c) has, when c < K, the c partners mem[0..c), else K partners
+ * mem[d]: d = draws[i][k] (clamped into [0, c)) when draws is given, the ranks of iris_prop_draws(seed) when it is NULL.  Per partner j
+ * w = exp(-(|a_i - a_j|^2 / sigma_albedo^2) / 2) exp(-(|p_i - p_j|^2 / sigma_pos^2) / 2);  W_i = 1e-4 + sum w;  l_i = |sum w r_j / W_i - r_i| + |sum w m_j / W_i - m_i|;
+ * loss[0] = ls * sum_i l_i / c_i.  One wave per pixel, lane l sums draws k = l, l + 64, ... in that order, fixed-order reductions: bitwise reproducible.
+ * Kept for the backward: records (N, 8) f32 (per position a.xyz p.xyz r m), saved (N, 4) f32 (W, sign(rbar - r), sign(mbar - m), 0), both 16-byte aligned;
+ * terms (N) f32 scratch.  N = 0 writes loss[0] = 0. */
+IRIS_API int iris_prop_semantic_fwd(const int32_t *runs, const int64_t *order, const float *roughness, const float *metallic, const float *albedo,
+                           const float *positions, int64_t N, int K, const int64_t *draws, uint64_t seed, double sigma_albedo, double sigma_pos,
+                           int normalise, double voxel_min, double voxel_max, float ls, float *records, float *saved, float *terms, float *loss,
+                           iris_stream_t);
+/* Its gradient for the cotangent g_loss[0] (device), with the forward's runs, order, records, saved, draws / seed, K, sigmas and ls:
+ * g_roughness[k] = -sign_r(k) g_k + sum over the draws (i, j = k) of sign_r(i) g_i w_ij / W_i, g_i = ls g_loss / c_i (the partners' r_j are not detached in the
+ * reference); g_metallic likewise; albedo and positions get none.  The draws and weights are regenerated.  The propagated part is summed per segment in LDS
+ * (segments up to 8192 members; larger ones add straight to memory) and flushed with f32 atomics into g_sorted (2 N f32 scratch, zeroed by the call), so
+ * the gradient is reproducible up to summation order, not bitwise.  g_roughness, g_metallic (N) are overwritten. */
+IRIS_API int iris_prop_semantic_bwd(const int32_t *runs, const int64_t *order, const float *records, const float *saved, int64_t N, int K, const int64_t *draws,
+                           uint64_t seed, double sigma_albedo, double sigma_pos, float ls, const float *g_loss, float *g_sorted, float *g_roughness,
+                           float *g_metallic, iris_stream_t);
+/* Part branch (:216-238): w_i = (1 - r_i) + 1e-4 (detached), S_s = sum w, M_s = sum w m / S_s, R_s = sum w r / S_s over segment s,
+ * loss[0] = lp / N * sum_i (|m_i - M_s(i)| + |r_i - R_s(i)|).  No atomics: bitwise reproducible.  Kept for the backward: seg_means (N, 4) f32, row `start`
+ * of a run = (S, M, R, 0), 16-byte aligned; signs (N, 2) f32 (sign(m - M), sign(r - R)) per position, 8-byte aligned; terms (N) scratch. */
+IRIS_API int iris_prop_part_fwd(const int32_t *runs, const int64_t *order, const float *roughness, const float *metallic, int64_t N, float lp, float *seg_means,
+                       float *signs, float *terms, float *loss, iris_stream_t);
+/* g_metallic[k] = lp g_loss / N (sign_m(k) - w_k / S_s sum_{i in s} sign_m(i)), g_roughness likewise with the r signs (no gradient through w); overwritten. */
+IRIS_API int iris_prop_part_bwd(const int32_t *runs, const int64_t *order, const float *roughness, const float *seg_means, const float *signs, int64_t N, float lp,
+                       const float *g_loss, float *g_roughness, float *g_metallic, iris_stream_t);
+
 /* ---- OpenEXR ZIP / ZIPS writer, device half ------------------------------------------------------------- */
 /* Deflate of the scanline blocks of n_maps maps (utils/exr.py scanline_blocks_torch): full (n_maps, n_full, block_bytes) and tail (n_maps, tail_bytes)
  * hold the PREDICTED bytes (reordered, delta-coded) of every block, device uint8, contiguous.  records receives, map by map, every chunk record as the

@@ -45,6 +45,8 @@ IRIS_API int iris_debug_bake_specular(const iris_scene *, const iris_emitter *, 
  *                       clipped boxes (80; 0 = off)
  *   "phase_min" lanes (12)      "tile_target_rays" (4096)      "tiles_per_block" (4)
  *   "pt_tile_min": smallest batch the path-tracing stages route through the tile-sorted kernel
+ *   "prop_bwd_targets" (32): pixels per workgroup of the propagation regulariser's backward      "prop_lds_members" 0..8192 (8192): largest segment it sums in
+ *                       LDS, 0 = global atomics only (these two change the ORDER of the gradient's float sums: its last bits, nothing else)
  * NOT thread-safe: plain process-wide globals that iris_scene_create / the launches read.  Set them before creating handles, from one thread. */
 IRIS_API int iris_debug_set(const char *key, long long value);
 /* NGPBRDF: the hash-grid encoding alone (tests compare it bit for bit with the restatement; the perceptron behind it only to a tolerance):

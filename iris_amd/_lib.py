@@ -93,6 +93,12 @@ PROTOTYPES = {
     "iris_cache_gather": [_P, _P, _I64, _I32, _P, _P],
     "iris_shade_cached_fwd": [_P, _P, _P, _P, _P, _I64, _I32, _P, _P],
     "iris_shade_cached_bwd": [_P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P],
+    "iris_prop_runs": [_P, _I64, _P, _P],
+    "iris_prop_draws": [_P, _P, _I64, _I32, _U64, _P, _P],
+    "iris_prop_semantic_fwd": [_P, _P, _P, _P, _P, _P, _I64, _I32, _P, _U64, _D, _D, _I32, _D, _D, _F, _P, _P, _P, _P, _P],
+    "iris_prop_semantic_bwd": [_P, _P, _P, _P, _I64, _I32, _P, _U64, _D, _D, _F, _P, _P, _P, _P, _P],
+    "iris_prop_part_fwd": [_P, _P, _P, _P, _I64, _F, _P, _P, _P, _P, _P],
+    "iris_prop_part_bwd": [_P, _P, _P, _P, _P, _I64, _F, _P, _P, _P, _P],
     "iris_denoise_workspace_bytes": [_I32, _I32],
     "iris_denoise": [_P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _F, _F, _F, _P, _U64, _P],
     "iris_exr_zip_workspace_bytes": [_I32, _I64, _I64, _I64],

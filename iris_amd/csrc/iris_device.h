@@ -200,6 +200,21 @@ __device__ __forceinline__ void philox_u2(uint64_t seed, uint64_t idx, uint32_t 
     u1 = (float)(c1 >> 8) * 5.9604644775390625e-08f;
 }
 
+// The same block with all four output words (the propagation regulariser's draws, iris_prop.h).  Kept beside philox_u2 rather than under it: routing
+// philox_u2 through this function reorders the bake kernels' instruction schedule, and those kernels are measured to the per cent.
+__device__ __forceinline__ void philox4x32(uint64_t seed, uint64_t idx, uint32_t stream, uint32_t& o0, uint32_t& o1, uint32_t& o2, uint32_t& o3) {
+    uint32_t c0 = (uint32_t)idx, c1 = (uint32_t)(idx >> 32), c2 = stream, c3 = 0u;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        const uint64_t m0 = (uint64_t)0xD2511F53u * (uint64_t)c0, m1 = (uint64_t)0xCD9E8D57u * (uint64_t)c2;
+        const uint32_t n0 = (uint32_t)(m1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(m0 >> 32) ^ c3 ^ k1;
+        c0 = n0; c1 = (uint32_t)m1; c2 = n2; c3 = (uint32_t)m0;
+    }
+    o0 = c0; o1 = c1; o2 = c2; o3 = c3;
+}
+
 // ---- VoxelSLF (model/slf.py) and SLFEmitter tables (model/emitter.py) as laid out in HBM ----
 struct SlfDev {
     const int32_t* inds;     // H^3 int32 [z][y][x], -1 empty (the reference keeps int64: 128 MiB -> 64 MiB at H=256)

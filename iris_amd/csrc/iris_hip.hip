@@ -22,6 +22,7 @@
 #include "iris_cache.h"
 #include "iris_denoise.h"
 #include "iris_ngp.h"
+#include "iris_prop.h"
 #include "iris_deflate.h"
 
 using namespace iris;
@@ -64,7 +65,7 @@ struct DevEvent {
 };
 
 // ---- diagnostics options (iris_hip_debug.h): process-wide, set by tests / experiments only; -1 = the built-in default
-static long long g_opt_bvh_tri_cost_x100 = -1, g_opt_bvh_max_leaf = -1, g_opt_phase_min = -1, g_opt_tile_target_rays = -1, g_opt_tiles_per_block = -1, g_opt_pt_tile_min = -1, g_opt_bvh_presplit_x10 = -1, g_opt_joint_max_rays = -1;
+static long long g_opt_bvh_tri_cost_x100 = -1, g_opt_bvh_max_leaf = -1, g_opt_phase_min = -1, g_opt_tile_target_rays = -1, g_opt_tiles_per_block = -1, g_opt_pt_tile_min = -1, g_opt_bvh_presplit_x10 = -1, g_opt_joint_max_rays = -1, g_opt_prop_bwd_targets = -1, g_opt_prop_lds_members = -1;
 extern "C" IRIS_API int iris_debug_set(const char* key, long long value) {
     if (!key) return fail(IRIS_ERR_ARG, "iris_debug_set: null key");
     const std::string k(key);
@@ -76,6 +77,8 @@ extern "C" IRIS_API int iris_debug_set(const char* key, long long value) {
     else if (k == "tiles_per_block") g_opt_tiles_per_block = value;
     else if (k == "pt_tile_min") g_opt_pt_tile_min = value;
     else if (k == "joint_max_rays") g_opt_joint_max_rays = value;
+    else if (k == "prop_bwd_targets") g_opt_prop_bwd_targets = value;
+    else if (k == "prop_lds_members") g_opt_prop_lds_members = value;
     else return fail(IRIS_ERR_ARG, "iris_debug_set: unknown option " + k);
     return IRIS_OK;
 }
@@ -852,6 +855,89 @@ extern "C" IRIS_API int iris_shade_cached_bwd(const float* rows, const int64_t* 
     if (B == 0) return IRIS_OK;
     return launch1d(shade_cached_bwd_kernel, B, 16384, stream, rows, idx, albedo, metallic,
                        roughness, gL, B, R, g_albedo, g_metallic, g_roughness);
+}
+
+// ---- the BRDF trainer's propagation regulariser (iris_prop.h; train_brdf_crf.py:212-290)
+static bool prop_n_ok(int64_t N) { return N >= 0 && N < (int64_t(1) << 31) - 64; }       // positions and counts are 32-bit in the kernels
+extern "C" IRIS_API int iris_prop_runs(const int64_t* sorted_seg, int64_t N, int32_t* runs, iris_stream_t stream) {
+    if (!prop_n_ok(N) || (N > 0 && (!sorted_seg || !runs))) return fail(IRIS_ERR_ARG, "iris_prop_runs: bad arguments");
+    if (N == 0) return IRIS_OK;
+    return launch1d(prop_runs_kernel, N, 4096, stream, sorted_seg, (int)N, (int2*)runs);
+}
+extern "C" IRIS_API int iris_prop_draws(const int32_t* runs, const int64_t* order, int64_t N, int K, uint64_t seed, int64_t* draws, iris_stream_t stream) {
+    if (!prop_n_ok(N) || K < 1 || (N > 0 && (!runs || !order || !draws))) return fail(IRIS_ERR_ARG, "iris_prop_draws: bad arguments");
+    if (N == 0) return IRIS_OK;
+    return launch1d(prop_draws_kernel, N * K, 16384, stream, (const int2*)runs, order, (int)N, K, seed, draws);
+}
+static bool prop_sigmas(double sigma_albedo, double sigma_pos, PropArgs& a) {
+    a.sa2 = (float)(sigma_albedo * sigma_albedo);
+    a.sp2 = (float)(sigma_pos * sigma_pos);
+    return a.sa2 > 0.f && a.sp2 > 0.f && std::isfinite(a.sa2) && std::isfinite(a.sp2);
+}
+extern "C" IRIS_API int iris_prop_semantic_fwd(const int32_t* runs, const int64_t* order, const float* roughness, const float* metallic, const float* albedo,
+                                               const float* positions, int64_t N, int K, const int64_t* draws, uint64_t seed, double sigma_albedo,
+                                               double sigma_pos, int normalise, double voxel_min, double voxel_max, float ls, float* records, float* saved,
+                                               float* terms, float* loss, iris_stream_t stream) {
+    PropArgs a;
+    if (!prop_n_ok(N) || K < 1 || !loss || !prop_sigmas(sigma_albedo, sigma_pos, a) ||
+        (N > 0 && (!runs || !order || !roughness || !metallic || !albedo || !positions || !records || !saved || !terms)))
+        return fail(IRIS_ERR_ARG, "iris_prop_semantic_fwd: bad arguments");
+    if (((uintptr_t)records | (uintptr_t)saved) % 16) return fail(IRIS_ERR_ARG, "iris_prop_semantic_fwd: records and saved must be 16-byte aligned");
+    if (N > 0) {
+        int rc = launch1d(prop_pack_kernel, N, 4096, stream, order, albedo, positions, roughness, metallic, (int)N, normalise, (float)voxel_min,
+                          (float)(voxel_max - voxel_min), (PropRec*)records);
+        if (rc) return rc;
+        a.runs = (const int2*)runs; a.order = order; a.rec = (const PropRec*)records; a.draws = draws; a.seed = seed; a.n = (int)N; a.K = K;
+        rc = launch1d(prop_semantic_fwd_kernel, N * 64, 1 << 16, stream, a, (float4*)saved, terms);     // one wave per pixel
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(prop_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)terms, (int)N, ls, loss);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_prop_semantic_bwd(const int32_t* runs, const int64_t* order, const float* records, const float* saved, int64_t N, int K,
+                                               const int64_t* draws, uint64_t seed, double sigma_albedo, double sigma_pos, float ls, const float* g_loss,
+                                               float* g_sorted, float* g_roughness, float* g_metallic, iris_stream_t stream) {
+    PropArgs a;
+    if (!prop_n_ok(N) || K < 1 || !prop_sigmas(sigma_albedo, sigma_pos, a) ||
+        (N > 0 && (!runs || !order || !records || !saved || !g_loss || !g_sorted || !g_roughness || !g_metallic)))
+        return fail(IRIS_ERR_ARG, "iris_prop_semantic_bwd: bad arguments");
+    if (((uintptr_t)records | (uintptr_t)saved) % 16) return fail(IRIS_ERR_ARG, "iris_prop_semantic_bwd: records and saved must be 16-byte aligned");
+    if (N == 0) return IRIS_OK;
+    a.runs = (const int2*)runs; a.order = order; a.rec = (const PropRec*)records; a.draws = draws; a.seed = seed; a.n = (int)N; a.K = K;
+    const int targets = g_opt_prop_bwd_targets > 0 ? (int)std::min<long long>(g_opt_prop_bwd_targets, 1 << 20) : kPropBwdTargets;
+    const int members = g_opt_prop_lds_members >= 0 ? (int)std::min<long long>(g_opt_prop_lds_members, kPropLdsMembers) : kPropLdsMembers;   // 64 KB at most
+    HIP_TRY(hipMemsetAsync(g_sorted, 0, (size_t)N * 2 * sizeof(float), (hipStream_t)stream));
+    const int64_t chunks = (N + targets - 1) / targets;
+    hipLaunchKernelGGL(prop_semantic_bwd_kernel, dim3(grid_for(chunks, 1, 1 << 16)), dim3(kPropBwdThreads), (size_t)members * 2 * sizeof(float), (hipStream_t)stream,
+                       a, (const float4*)saved, g_loss, ls, targets, members, g_sorted);
+    HIP_TRY(hipGetLastError());
+    return launch1d(prop_semantic_bwd_finish_kernel, N, 4096, stream, (const int2*)runs, order, (const float4*)saved, g_loss, ls, (const float*)g_sorted, (int)N,
+                    g_roughness, g_metallic);
+}
+extern "C" IRIS_API int iris_prop_part_fwd(const int32_t* runs, const int64_t* order, const float* roughness, const float* metallic, int64_t N, float lp,
+                                           float* seg_means, float* signs, float* terms, float* loss, iris_stream_t stream) {
+    if (!prop_n_ok(N) || !loss || (N > 0 && (!runs || !order || !roughness || !metallic || !seg_means || !signs || !terms)))
+        return fail(IRIS_ERR_ARG, "iris_prop_part_fwd: bad arguments");
+    if ((uintptr_t)seg_means % 16 || (uintptr_t)signs % 8) return fail(IRIS_ERR_ARG, "iris_prop_part_fwd: seg_means must be 16-byte, signs 8-byte aligned");
+    if (N > 0) {
+        int rc = launch1d(prop_part_means_kernel, N * 64, 1 << 16, stream, (const int2*)runs, order, roughness, metallic, (int)N, (float4*)seg_means);
+        if (rc) return rc;
+        rc = launch1d(prop_part_terms_kernel, N, 4096, stream, (const int2*)runs, order, roughness, metallic, (const float4*)seg_means, (int)N, (float2*)signs, terms);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(prop_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)terms, (int)N, N > 0 ? lp / (float)N : 0.f, loss);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_prop_part_bwd(const int32_t* runs, const int64_t* order, const float* roughness, const float* seg_means, const float* signs,
+                                           int64_t N, float lp, const float* g_loss, float* g_roughness, float* g_metallic, iris_stream_t stream) {
+    if (!prop_n_ok(N) || (N > 0 && (!runs || !order || !roughness || !seg_means || !signs || !g_loss || !g_roughness || !g_metallic)))
+        return fail(IRIS_ERR_ARG, "iris_prop_part_bwd: bad arguments");
+    if ((uintptr_t)seg_means % 16 || (uintptr_t)signs % 8) return fail(IRIS_ERR_ARG, "iris_prop_part_bwd: seg_means must be 16-byte, signs 8-byte aligned");
+    if (N == 0) return IRIS_OK;
+    return launch1d(prop_part_bwd_kernel, N * 64, 1 << 16, stream, (const int2*)runs, order, roughness, (const float4*)seg_means, (const float2*)signs, g_loss, lp,
+                    (int)N, g_roughness, g_metallic);
 }
 
 // ---- 8(f)-4: denoiser substitute (iris_denoise.h)
