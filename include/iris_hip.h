@@ -361,6 +361,34 @@ IRIS_API int iris_prop_part_fwd(const int32_t *runs, const int64_t *order, const
 IRIS_API int iris_prop_part_bwd(const int32_t *runs, const int64_t *order, const float *roughness, const float *seg_means, const float *signs, int64_t N, float lp,
                        const float *g_loss, float *g_roughness, float *g_metallic, iris_stream_t);
 
+/* ---- the camera response model EmorCRF (crf/model_crf.py:32-122) ---------------------------------------------------------------------- */
+/* The interpolator is this project's contract (the reference's torch_interpolations is third-party and has no ROCm build: parity unpinned).  Knots p[0..n)
+ * non-decreasing, values v[0..n), query q:  r = first index with p[r] >= q, clamped to n - 1 (torch.bucketize);  l = max(r - 1, 0);  dl = max(q - p[l], 0);
+ * dr = max(p[r] - q, 0);  both zero -> both 1;  out = (v[l] dr + v[r] dl) / (dl + dr), each operation rounded once, in this order.
+ * d out / d q = (v[r] - v[l]) / (dl + dr), 0 where both were zero;  d out / d v[l] = dr / (dl + dr), d out / d v[r] = dl / (dl + dr).
+ * grid: (n) f32 knots shared by the three channels.  PRECONDITION: grid is torch.linspace(0, 1, n) in float32 (uniform up to rounding).  The segment
+ * is guessed as ceil(q (n - 1)) and corrected by a walk against these values, so it is bucketize's for every q; on the uniform grid the walk takes at
+ * most one step.  Any other non-decreasing grid still gives bucketize's segment and in-range reads, but the walk is then O(n) per lookup.  2 <= n <= 1024 (the tables live in LDS).  A NaN or infinite input gives an unspecified value
+ * and no out-of-range access.  exposure: device pointer to n_exposure = 1 or B values, or NULL: the host value exposure_value.  B = 0 is a no-op. */
+/* model_crf.py:68-86: ldr[i][c] = interp(grid, table[c], clip(hdr[i][c] * e_i, 0, 1)); table (3, n), hdr and ldr (B, 3) */
+IRIS_API int iris_crf_fwd(const float *grid, const float *table, int n, const float *hdr, const float *exposure, int64_t n_exposure, float exposure_value,
+                 int64_t B, float *ldr, iris_stream_t);
+/* model_crf.py:88-106 after get_inv_crf: hdr[i][c] = interp(grid, inv_table[c], clip(ldr[i][c], 0, 1)) / e_i.  No gradient. */
+IRIS_API int iris_crf_lookup_inv(const float *grid, const float *inv_table, int n, const float *ldr, const float *exposure, int64_t n_exposure,
+                        float exposure_value, int64_t B, float *hdr, iris_stream_t);
+/* Gradient of iris_crf_fwd for the cotangent g_ldr (B, 3); either output may be NULL.
+ * g_hdr (B, 3) = g_ldr * slope * e_i where 0 <= hdr * e_i <= 1 (torch.clip's gradient: 1 on the closed interval), else 0.
+ * g_table (3, n): sum over the pixels of the two weights above times g_ldr (no clip mask: the lookup reads the table at the clipped value too).  Summed
+ * per workgroup in LDS, one partial slab per workgroup stored to workspace (iris_crf_bwd_workspace_bytes(B, n) bytes, at most 3 MiB), the slabs added in
+ * slab order: no global atomics; reproducible up to the order of the LDS adds inside a workgroup.  The slab count depends on B only. */
+IRIS_API uint64_t iris_crf_bwd_workspace_bytes(int64_t B, int n);
+IRIS_API int iris_crf_bwd(const float *grid, const float *table, int n, const float *hdr, const float *exposure, int64_t n_exposure, float exposure_value,
+                 int64_t B, const float *g_ldr, float *g_hdr, float *g_table, void *workspace, uint64_t workspace_bytes, iris_stream_t);
+/* get_inv_crf (model_crf.py:22-30, 45-55) for the three channels in one launch: d = neighbouring differences of table[c]; d += -min(d) if that is negative;
+ * d /= sum(d); knots = (0, prefix sums of d); inv_table[c] = interp(knots, values grid, at grid).  A tree sum and a parallel scan: agrees with torch's
+ * sequential cumsum up to summation order. */
+IRIS_API int iris_crf_inv_table(const float *grid, const float *table, int n, float *inv_table, iris_stream_t);
+
 /* ---- OpenEXR ZIP / ZIPS writer, device half ------------------------------------------------------------- */
 /* Deflate of the scanline blocks of n_maps maps (utils/exr.py scanline_blocks_torch): full (n_maps, n_full, block_bytes) and tail (n_maps, tail_bytes)
  * hold the PREDICTED bytes (reordered, delta-coded) of every block, device uint8, contiguous.  records receives, map by map, every chunk record as the

@@ -23,6 +23,7 @@
 #include "iris_denoise.h"
 #include "iris_ngp.h"
 #include "iris_prop.h"
+#include "iris_crf.h"
 #include "iris_deflate.h"
 
 using namespace iris;
@@ -938,6 +939,63 @@ extern "C" IRIS_API int iris_prop_part_bwd(const int32_t* runs, const int64_t* o
     if (N == 0) return IRIS_OK;
     return launch1d(prop_part_bwd_kernel, N * 64, 1 << 16, stream, (const int2*)runs, order, roughness, (const float4*)seg_means, (const float2*)signs, g_loss, lp,
                     (int)N, g_roughness, g_metallic);
+}
+
+// ---- the camera response model (iris_crf.h; crf/model_crf.py:32-122)
+static bool crf_args(const float* grid, const float* table, int n, const float* exposure, int64_t n_exposure, float exposure_value, int64_t B, CrfArgs& a) {
+    a.grid = grid; a.table = table; a.n = n; a.exposure = exposure; a.n_exposure = n_exposure; a.exposure_value = exposure_value; a.B = B;
+    return n >= 2 && n <= kCrfMaxKnots && B >= 0 && grid && table && (!exposure || n_exposure == 1 || n_exposure == B);
+}
+static int crf_slabs(int64_t B) { return grid_for(B, kCrfThreads, kCrfSlabs); }       // a function of B alone: the sum's grouping does not depend on the device
+template <bool INV>
+static int crf_lookup(const char* who, const float* grid, const float* table, int n, const float* in, const float* exposure, int64_t n_exposure,
+                      float exposure_value, int64_t B, float* out, iris_stream_t stream) {
+    CrfArgs a;
+    if (!crf_args(grid, table, n, exposure, n_exposure, exposure_value, B, a) || (B > 0 && (!in || !out)))
+        return fail(IRIS_ERR_ARG, std::string(who) + ": bad arguments (2 <= n <= 1024, exposure holds 1 or B values)");
+    if (B == 0) return IRIS_OK;
+    hipLaunchKernelGGL(crf_lookup_kernel<INV>, dim3(grid_for(B, kCrfThreads, kCrfLookupBlocks)), dim3(kCrfThreads), (size_t)n * 4 * sizeof(float), (hipStream_t)stream,
+                       a, in, out);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_crf_fwd(const float* grid, const float* table, int n, const float* hdr, const float* exposure, int64_t n_exposure, float exposure_value,
+                                     int64_t B, float* ldr, iris_stream_t stream) {
+    return crf_lookup<false>("iris_crf_fwd", grid, table, n, hdr, exposure, n_exposure, exposure_value, B, ldr, stream);
+}
+extern "C" IRIS_API int iris_crf_lookup_inv(const float* grid, const float* inv_table, int n, const float* ldr, const float* exposure, int64_t n_exposure,
+                                            float exposure_value, int64_t B, float* hdr, iris_stream_t stream) {
+    return crf_lookup<true>("iris_crf_lookup_inv", grid, inv_table, n, ldr, exposure, n_exposure, exposure_value, B, hdr, stream);
+}
+extern "C" IRIS_API uint64_t iris_crf_bwd_workspace_bytes(int64_t B, int n) {
+    if (B < 0 || n < 2 || n > kCrfMaxKnots) return 0;
+    return (uint64_t)crf_slabs(B) * 3 * (uint64_t)n * sizeof(float);
+}
+extern "C" IRIS_API int iris_crf_bwd(const float* grid, const float* table, int n, const float* hdr, const float* exposure, int64_t n_exposure, float exposure_value,
+                                     int64_t B, const float* g_ldr, float* g_hdr, float* g_table, void* workspace, uint64_t workspace_bytes,
+                                     iris_stream_t stream) {
+    CrfArgs a;
+    if (!crf_args(grid, table, n, exposure, n_exposure, exposure_value, B, a) || (B > 0 && (!hdr || !g_ldr)))
+        return fail(IRIS_ERR_ARG, "iris_crf_bwd: bad arguments (2 <= n <= 1024, exposure holds 1 or B values)");
+    if (g_table && (!workspace || workspace_bytes < iris_crf_bwd_workspace_bytes(B, n) || (uintptr_t)workspace % 4))
+        return fail(IRIS_ERR_ARG, "iris_crf_bwd: g_table needs a workspace of " + std::to_string(iris_crf_bwd_workspace_bytes(B, n)) + " bytes");
+    if (B == 0) {
+        if (g_table) HIP_TRY(hipMemsetAsync(g_table, 0, (size_t)3 * n * sizeof(float), (hipStream_t)stream));
+        return IRIS_OK;
+    }
+    if (!g_hdr && !g_table) return IRIS_OK;
+    const int slabs = crf_slabs(B);
+    hipLaunchKernelGGL(crf_bwd_kernel, dim3(slabs), dim3(kCrfThreads), (size_t)n * (g_table ? 7 : 4) * sizeof(float), (hipStream_t)stream, a, hdr, g_ldr, g_hdr,
+                       g_table ? (float*)workspace : (float*)nullptr);
+    HIP_TRY(hipGetLastError());
+    if (!g_table) return IRIS_OK;
+    return launch1d(crf_slab_sum_kernel, 3 * n, 16, stream, (const float*)workspace, slabs, 3 * n, g_table);
+}
+extern "C" IRIS_API int iris_crf_inv_table(const float* grid, const float* table, int n, float* inv_table, iris_stream_t stream) {
+    if (n < 2 || n > kCrfMaxKnots || !grid || !table || !inv_table) return fail(IRIS_ERR_ARG, "iris_crf_inv_table: bad arguments (2 <= n <= 1024)");
+    hipLaunchKernelGGL(crf_inv_table_kernel, dim3(3), dim3(kCrfMaxKnots), 0, (hipStream_t)stream, grid, table, n, inv_table);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
 }
 
 // ---- 8(f)-4: denoiser substitute (iris_denoise.h)

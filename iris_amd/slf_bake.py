@@ -4,9 +4,10 @@
   refine_slf       slf_refine.py:85-108        re-pool an existing grid with new radiance
   extract_emitters extract_emitter_ldr.py:72-115  per-triangle mean radiance -> threshold -> emitter.pth
 
-`views` is any iterable of dicts with 'rays' (N,6) [origin, direction] and, where radiance is pooled, 'rgbs' (N,3) LINEAR radiance:
-the reference obtains it with ``model_crf.inverse(rgbs, exposure)`` (slf_bake.py:128-129) -- the learned camera response model and
-the image datasets are outside this path, the caller applies them.  Primary rays are traced with the HIP intersector; pooling is
+`views` is any iterable of dicts with 'rays' (N,6) [origin, direction] and, where radiance is pooled, 'rgbs' (N,3).  Without `crf=` the 'rgbs' are
+LINEAR radiance and pooled as given.  With `crf=model` (an iris_amd.model.crf.EmorCRF on the device) they are the LDR photographs and every batch also
+carries 'exposure': the functions pool ``model.inverse(rgbs, exposure)`` as the reference does (slf_bake.py:128-129, slf_refine.py:96-97,
+extract_emitter_ldr.py).  Primary rays are traced with the HIP intersector; pooling is
 atomic accumulation in HBM (utils/gbuffer.py, VoxelSLF.scatter_add), so float sums agree with the reference's sequential CPU
 scatter up to summation order, integer results exactly.  Everything stays on the device; only the final state dict goes to the
 host, in the reference's file format (so SLFEmitter(emitter_path, slf_path) loads either side's files).
@@ -77,18 +78,24 @@ def visible_voxels(scene, views, voxel_min, voxel_max, res_spatial, device, cach
     return hist
 
 
-def pool_radiance(scene, views, vslf, device, cache=False):
+def _radiance(batch, device, crf):
+    """the batch's linear radiance on the device: 'rgbs' as given, or through the response model's inverse with the batch's 'exposure'"""
+    rgbs = batch["rgbs"].to(device=device, dtype=torch.float32)
+    return rgbs if crf is None else crf.inverse(rgbs, batch["exposure"])
+
+
+def pool_radiance(scene, views, vslf, device, cache=False, crf=None):
     """slf_bake.py:120-138 / slf_refine.py:90-106: scatter every valid primary hit's radiance into its voxel, then average."""
     vslf = vslf.to(device)
     for batch in views:
         positions, _, valid = _hits(scene, batch, device, cache)
-        vslf.scatter_add(positions[valid], batch["rgbs"].to(device=device, dtype=torch.float32)[valid])
+        vslf.scatter_add(positions[valid], _radiance(batch, device, crf)[valid])
     vslf.radiance = vslf.radiance / vslf.count[..., None].float().clamp_min(1)
     vslf.refresh()                                    # the buffer was rebound: the device tables are rebuilt at the next lookup
     return vslf
 
 
-def bake_slf(scene, views, res_spatial=256, dataset="scannetpp", device="cuda"):
+def bake_slf(scene, views, res_spatial=256, dataset="scannetpp", device="cuda", crf=None):
     """-> the dict slf_bake.py:140-145 saves as vslf.npz: {'mask', 'voxel_min', 'voxel_max', 'weight'}  (tensors on the host)."""
     views = list(views)
     device = torch.device(device)
@@ -97,23 +104,23 @@ def bake_slf(scene, views, res_spatial=256, dataset="scannetpp", device="cuda"):
         hist = visible_voxels(scene, views, voxel_min, voxel_max, res_spatial, device, cache=True)
         mask = hist > 0
         vslf = VoxelSLF(mask, voxel_min.item(), voxel_max.item())            # index grid and buffers built on the device the mask was counted on
-        vslf = pool_radiance(scene, views, vslf, device, cache=True)
+        vslf = pool_radiance(scene, views, vslf, device, cache=True, crf=crf)
     finally:
         drop_hits(views)
     return {"mask": mask.cpu(), "voxel_min": voxel_min.item(), "voxel_max": voxel_max.item(),
             "weight": {k: v.cpu() for k, v in vslf.state_dict().items()}}
 
 
-def refine_slf(state_dict, scene, views, device="cuda"):
+def refine_slf(state_dict, scene, views, device="cuda", crf=None):
     """slf_refine.py:85-108: same grid, radiance pooled anew; returns the updated dict."""
     vslf = VoxelSLF(state_dict["mask"], state_dict["voxel_min"], state_dict["voxel_max"])
-    vslf = pool_radiance(scene, list(views), vslf, torch.device(device))
+    vslf = pool_radiance(scene, list(views), vslf, torch.device(device), crf=crf)
     out = dict(state_dict)
     out["weight"] = {k: v.cpu() for k, v in vslf.state_dict().items()}
     return out
 
 
-def extract_emitters(scene, vertices, faces, views, threshold, device="cuda"):
+def extract_emitters(scene, vertices, faces, views, threshold, device="cuda", crf=None):
     """extract_emitter_ldr.py:77-115 (mode 'export'): per-triangle mean of the radiance of the primary hits that landed on it, max over
     the channels, > threshold -> emitter; returns the dict saved as emitter.pth."""
     device = torch.device(device)
@@ -123,7 +130,7 @@ def extract_emitters(scene, vertices, faces, views, threshold, device="cuda"):
     triangle_count = torch.zeros(n_face, device=device)
     for batch in views:
         _, idx, valid = _hits(scene, batch, device)
-        scatter_add_rows(batch["rgbs"].to(device=device, dtype=torch.float32)[valid], idx[valid], triangle_radiance, triangle_count)
+        scatter_add_rows(_radiance(batch, device, crf)[valid], idx[valid], triangle_radiance, triangle_count)
     mean = triangle_radiance / triangle_count.unsqueeze(-1).clamp_min(1)
     is_emitter = (torch.max(mean, dim=-1)[0] > threshold).cpu()
     ev = vertices[faces[is_emitter]]
