@@ -199,6 +199,26 @@ IRIS_API int iris_pt_nee(const iris_scene *, const iris_emitter *, const float *
 IRIS_API int iris_pt_primary(const iris_scene *, const iris_emitter *, const float *rays_o, const float *rays_d, const float *dxdu, const float *dydv,
                     const float *dudv, int64_t B, int spp, float *wi, float *wo, float *pos, float *nrm, int32_t *e0, uint8_t *valid_next, int32_t *path_of,
                     iris_stream_t);
+/* render.py:179-184 as ONE launch, the head of the render stage's intrinsics pass: ds = normalize(rays_d + dx_du*u + dy_dv*v) with u, v in [0,1) -- render.py:180
+ * does NOT subtract 0.5, unlike :338-339 --, closest hit of rays_o[b] + t * ds, the primary hit's emitter ordinal.  iris_pt_primary's kernel and outputs (the jitter is
+ * one device function with the offset as a parameter), without path_of.  From them: vis = valid_next | (e0 >= 0); emission = e0 >= 0 ? radiance[e0] : 0. */
+IRIS_API int iris_render_primary(const iris_scene *, const iris_emitter *, const float *rays_o, const float *rays_d, const float *dxdu, const float *dydv,
+                        const float *dudv, int64_t B, int spp, float *wi, float *wo, float *pos, float *nrm, int32_t *e0, uint8_t *valid_next, iris_stream_t);
+/* render.py:189-220 after the material network, ONE launch.  Per sample i = b*spp + s (N = B*spp rows, pixel-major): pos, nrm, wo, e0, valid_next as
+ * iris_render_primary gives them; albedo (N,3), roughness (N), metallic (N) = material_net(pos); u2 (N,2) the draw of :197; radiance: the emitter's (n_rad,3) tensor
+ * itself, as iris_pt_accumulate_fwd takes it (rows beyond the emitter handle's count are never read).
+ *   kd_ = albedo*(1-m); ks_ = 0.04*(1-m) + albedo*m; g0, g1 = sample_specular(u2, wo, nrm, roughness)[2:] (iris_sample_specular_v's arithmetic; the direction is
+ *   neither traced nor stored); a_prime_ = g0*ks_ + g1 + kd_; emission_ = e0 >= 0 ? radiance[e0] : 0;
+ *   keep = (valid_next | e0 >= 0) & ((emission_.r + emission_.g) + emission_.b == 0)  -- an emitter triangle whose radiance row sums to zero stays a surface (:202);
+ *   where !keep: kd_ = a_prime_ = 1, roughness_ = 1, metallic_ = 0 (:209-212), selected: a miss's non-finite GGX terms never reach a map;
+ *   slf_ = VoxelSLF lookup at pos for EVERY sample (:205 does not mask it): 0 in an empty voxel; a miss is looked up at the position the intersector gives a miss, (0,0,0).
+ * SUMMATION ORDER (a contract):  map[b] += (x_0 + x_1 + ... + x_{spp-1}) * (1.0f / spp), samples added in increasing s, in float32 -- `map += x.reshape(-1,spp,C).mean(1)`
+ * with a sequential sum.  The six maps are the caller's: kd (B,3), a_prime (B,3), roughness (B), metallic (B), emission (B,3), slf (B,3).  No atomics, every element
+ * written by one thread: bitwise reproducible.  spp: any positive int. */
+IRIS_API int iris_render_intrinsics(const iris_emitter *, const iris_slf *, const float *radiance, const float *pos, const float *nrm, const float *wo,
+                           const int32_t *e0, const uint8_t *valid_next, const float *albedo, const float *roughness, const float *metallic, const float *u2,
+                           int64_t B, int spp, float *kd, float *a_prime, float *roughness_map, float *metallic_map, float *emission, float *slf_map,
+                           iris_stream_t);
 /* :384-391  lobe sampling + next intersection.  lobe 0: sample_brdf(s1,s2,wo,normal,mat); lobe 1: sample_diffuse(s2,normal)
  * (path_tracing_det_diff :93-97, weight 1); lobe 2: sample_specular(s2,wo,normal,lobe_roughness) (path_tracing_det_spec :174-178),
  * weight = (g0,g1,0). */

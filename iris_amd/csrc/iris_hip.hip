@@ -24,6 +24,7 @@
 #include "iris_ngp.h"
 #include "iris_prop.h"
 #include "iris_crf.h"
+#include "iris_render.h"
 #include "iris_deflate.h"
 
 using namespace iris;
@@ -1327,16 +1328,14 @@ extern "C" IRIS_API int iris_pt_primary_emit(const iris_emitter* e, const int64_
 // (repeat_interleave, where, neg): six launches of a 0.5 ms call.
 template <int LAYOUT, bool JOINT>
 __global__ __launch_bounds__(kBlock) void pt_primary_kernel(SceneDev sc, EmitDev em, const float* __restrict__ rays_o, const float* __restrict__ rays_d, const float* __restrict__ dxdu,
-                                                            const float* __restrict__ dydv, const float* __restrict__ dudv, int64_t B, int spp, float* __restrict__ wi_out,
+                                                            const float* __restrict__ dydv, const float* __restrict__ dudv, float jitter_offset, int64_t B, int spp, float* __restrict__ wi_out,
                                                             float* __restrict__ wo_out, float* __restrict__ pos, float* __restrict__ nrm, int32_t* __restrict__ e0,
                                                             uint8_t* __restrict__ valid_next, int32_t* __restrict__ path_of) {
     __shared__ uint32_t s_stack[kStackLds * kBlock];
     const int64_t n = B * spp;
     for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
         const int64_t b = i / spp;
-        const float du = dudv[i] - 0.5f, dv = dudv[n + i] - 0.5f;
-        const f3 d0 = ld3(rays_d + b * 3), dx = ld3(dxdu + b * 3), dy = ld3(dydv + b * 3);
-        const f3 d = t_normalize(mk3((d0.x + dx.x * du) + dy.x * dv, (d0.y + dx.y * du) + dy.y * dv, (d0.z + dx.z * du) + dy.z * dv));   // pt_jitter_kernel
+        const f3 d = pt_jitter_dir(ld3(rays_d + b * 3), ld3(dxdu + b * 3), ld3(dydv + b * 3), dudv[i], dudv[n + i], jitter_offset);   // pt_jitter_kernel (0.5), render.py:180 (0)
         const f3 o = ld3(rays_o + b * 3);
         st3(wi_out + i * 3, d); st3(wo_out + i * 3, mk3(-d.x, -d.y, -d.z));
         const Hit h = trace_bvh4<LAYOUT, false, kStackLds, false, JOINT>(sc, o, d, s_stack + threadIdx.x);
@@ -1353,8 +1352,21 @@ __global__ __launch_bounds__(kBlock) void pt_primary_kernel(SceneDev sc, EmitDev
             st3(pos + i * 3, mk3(0.f, 0.f, 0.f)); st3(nrm + i * 3, mk3(0.f, 0.f, 0.f));
         }
         const bool cont = h.slot >= 0 && ord < 0;
-        e0[i] = ord; valid_next[i] = cont ? 1 : 0; path_of[i] = cont ? (int32_t)i : -1;
+        e0[i] = ord; valid_next[i] = cont ? 1 : 0;
+        if (path_of) path_of[i] = cont ? (int32_t)i : -1;                          // (iris_render_primary has no use for it)
     }
+}
+static int pt_primary_launch(const iris_scene* sc, const iris_emitter* e, const float* rays_o, const float* rays_d, const float* dxdu, const float* dydv, const float* dudv,
+                             float jitter_offset, int64_t B, int spp, float* wi, float* wo, float* pos, float* nrm, int32_t* e0, uint8_t* valid_next, int32_t* path_of,
+                             iris_stream_t stream) {
+    const int64_t N = B * spp;
+    const dim3 grid(grid_for(N, kBlock, num_cus() * 6));
+    with_trace(sc->dev, N, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pt_primary_kernel<T::layout, T::joint>), grid, dim3(kBlock), 0, (hipStream_t)stream, sc->dev, e->dev, rays_o, rays_d, dxdu, dydv, dudv, jitter_offset, B, spp, wi, wo, pos, nrm, e0, valid_next, path_of);
+    });
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
 }
 extern "C" IRIS_API int iris_pt_primary(const iris_scene* sc, const iris_emitter* e, const float* rays_o, const float* rays_d, const float* dxdu, const float* dydv,
                                const float* dudv, int64_t B, int spp, float* wi, float* wo, float* pos, float* nrm, int32_t* e0, uint8_t* valid_next, int32_t* path_of,
@@ -1364,14 +1376,39 @@ extern "C" IRIS_API int iris_pt_primary(const iris_scene* sc, const iris_emitter
     if (B == 0) return IRIS_OK;
     if (B * spp >= ((int64_t)1 << 31)) return fail(IRIS_ERR_ARG, "iris_pt_primary: more than 2^31 paths in one call (path_of is int32)");
     if (e->dev.nf != sc->info.n_triangles) return fail(IRIS_ERR_ARG, "iris_pt_primary: the emitter tables are for a mesh of another size than the scene's");
-    const int64_t N = B * spp;
-    const dim3 grid(grid_for(N, kBlock, num_cus() * 6));
-    with_trace(sc->dev, N, [&](auto t) {
-        using T = decltype(t);
-        hipLaunchKernelGGL((pt_primary_kernel<T::layout, T::joint>), grid, dim3(kBlock), 0, (hipStream_t)stream, sc->dev, e->dev, rays_o, rays_d, dxdu, dydv, dudv, B, spp, wi, wo, pos, nrm, e0, valid_next, path_of);
-    });
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
+    return pt_primary_launch(sc, e, rays_o, rays_d, dxdu, dydv, dudv, 0.5f, B, spp, wi, wo, pos, nrm, e0, valid_next, path_of, stream);
+}
+// render.py:179-184 + the primary hit's emitter ordinal: iris_pt_primary's kernel with render.py's jitter (du, dv in [0,1), no -0.5) and without path_of
+extern "C" IRIS_API int iris_render_primary(const iris_scene* sc, const iris_emitter* e, const float* rays_o, const float* rays_d, const float* dxdu, const float* dydv,
+                                   const float* dudv, int64_t B, int spp, float* wi, float* wo, float* pos, float* nrm, int32_t* e0, uint8_t* valid_next,
+                                   iris_stream_t stream) {
+    if (!sc || !e || B < 0 || spp < 1 || (B > 0 && (!rays_o || !rays_d || !dxdu || !dydv || !dudv || !wi || !wo || !pos || !nrm || !e0 || !valid_next)))
+        return fail(IRIS_ERR_ARG, "iris_render_primary: bad arguments");
+    if (B == 0) return IRIS_OK;
+    if (B > (((int64_t)1 << 40) / spp)) return fail(IRIS_ERR_ARG, "iris_render_primary: more than 2^40 samples in one call");
+    if (e->dev.nf != sc->info.n_triangles) return fail(IRIS_ERR_ARG, "iris_render_primary: the emitter tables are for a mesh of another size than the scene's");
+    return pt_primary_launch(sc, e, rays_o, rays_d, dxdu, dydv, dudv, 0.0f, B, spp, wi, wo, pos, nrm, e0, valid_next, nullptr, stream);
+}
+// render.py:189-220 after the material network (iris_render.h)
+extern "C" IRIS_API int iris_render_intrinsics(const iris_emitter* e, const iris_slf* slf, const float* radiance, const float* pos, const float* nrm, const float* wo,
+                                      const int32_t* e0, const uint8_t* valid_next, const float* albedo, const float* roughness, const float* metallic,
+                                      const float* u2, int64_t B, int spp, float* kd, float* a_prime, float* roughness_map, float* metallic_map, float* emission,
+                                      float* slf_map, iris_stream_t stream) {
+    if (!e || !slf || B < 0 || spp < 1 ||
+        (B > 0 && (!radiance || !pos || !nrm || !wo || !e0 || !valid_next || !albedo || !roughness || !metallic || !u2 || !kd || !a_prime || !roughness_map ||
+                   !metallic_map || !emission || !slf_map)))
+        return fail(IRIS_ERR_ARG, "iris_render_intrinsics: bad arguments");
+    if (B == 0) return IRIS_OK;
+    if (B > (((int64_t)1 << 40) / spp)) return fail(IRIS_ERR_ARG, "iris_render_intrinsics: more than 2^40 samples in one call");
+    RenderArgs a{};
+    a.slf = slf->dev; a.radiance = radiance; a.n_rad = e->n_rad; a.B = B; a.spp = spp;
+    a.pos = pos; a.nrm = nrm; a.wo = wo; a.albedo = albedo; a.rough = roughness; a.metal = metallic; a.u2 = u2; a.e0 = e0; a.valid_next = valid_next;
+    a.kd = kd; a.a_prime = a_prime; a.roughness = roughness_map; a.metallic = metallic_map; a.emission = emission; a.slf_out = slf_map;
+    int lpp = 1;
+    while (lpp < spp && lpp < 64) lpp <<= 1;                     // lanes per pixel: min(64, next power of two >= spp), as iris_pt_accumulate_fwd
+    a.lpp = lpp;
+    const int64_t n_groups = (B + 64 / lpp - 1) / (64 / lpp);    // one wave per group of 64 / lpp pixels
+    return launch1d(render_intrinsics_kernel, n_groups * 64, 16384, stream, a);
 }
 extern "C" IRIS_API int iris_pt_nee(const iris_scene* sc, const iris_emitter* e, const float* pos, const float* nrm, const float* wo, const float* albedo,
                            const float* roughness, const float* metallic, const float* s1, const float* s2, int64_t N, float* coef1, int32_t* e1,

@@ -76,15 +76,20 @@ __device__ __forceinline__ void sample_emitter1(const EmitSampleDev& e, float s1
     tri = e.ord2tri[ei];
 }
 
+// render.py:179-181 and utils/path_tracing.py:338-340: normalize(rays_d + dx_du * (u - offset) + dy_dv * (v - offset)); offset 0.5 in path_tracing_single, 0 in render.py
+// (u - 0.0f == u for every u >= 0: the unshifted jitter exactly)
+__device__ __forceinline__ f3 pt_jitter_dir(f3 d0, f3 dx, f3 dy, float u, float v, float offset) {
+    const float du = u - offset, dv = v - offset;
+    return t_normalize(mk3((d0.x + dx.x * du) + dy.x * dv, (d0.y + dx.y * du) + dy.y * dv, (d0.z + dx.z * du) + dy.z * dv));
+}
+
 // utils/path_tracing.py:338-340: wi = normalize(rays_d + dx_du*du + dy_dv*dv), du,dv = rand - 0.5
 __global__ void pt_jitter_kernel(const float* __restrict__ rays_d, const float* __restrict__ dxdu, const float* __restrict__ dydv,
                                  const float* __restrict__ dudv /* (2,B,spp) */, int64_t B, int spp, float* __restrict__ wi) {
     const int64_t n = B * spp;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = i / spp;
-        const float du = dudv[i] - 0.5f, dv = dudv[n + i] - 0.5f;
-        f3 d = ld3(rays_d + b * 3), dx = ld3(dxdu + b * 3), dy = ld3(dydv + b * 3);
-        st3(wi + i * 3, t_normalize(mk3((d.x + dx.x * du) + dy.x * dv, (d.y + dx.y * du) + dy.y * dv, (d.z + dx.z * du) + dy.z * dv)));
+        st3(wi + i * 3, pt_jitter_dir(ld3(rays_d + b * 3), ld3(dxdu + b * 3), ld3(dydv + b * 3), dudv[i], dudv[n + i], 0.5f));
     }
 }
 

@@ -1,0 +1,299 @@
+"""The render stage (reference: render.py:57-298) on MI355X: for every view of a split the path-traced image (`path_tracing`, the full integrator) and, in the
+same SPP // spp rounds, the scene intrinsics averaged over jittered primary rays (kd, a_prime, roughness, metallic, emission, surface light field); then the
+denoiser, the camera response model, the maps on disk and PSNR against the photograph.
+
+Every ingredient is a HIP stage of this package: `utils.path_tracing.path_tracing`, `utils.render.render_intrinsics` (iris_render_primary + the material network +
+iris_render_intrinsics), `utils.denoise.Denoiser` (the a-trous filter that stands where OptixDenoiser stands), `model.crf.EmorCRF`, `utils.exr.write_exr`.
+
+Not here: --light_type area (AreaEmitter), SSIM (metrics.txt carries PSNR only), the magma colour maps (*_color.png), merge.png, crfs.png,
+render_video.py / render_relight.py, and the trainers' validation(), which masks differently.
+"""
+import math
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .utils.path_tracing import path_tracing, ray_intersect
+from .utils.render import MAPS, new_maps, render_intrinsics
+
+INDIR_DEPTH = 5            # render.py:176
+OUT_DIRS = ("rgb", "diffuse", "a_prime", "roughness", "metallic", "emission", "slf", "merge")      # render.py:145
+
+
+def psnr(gt, img, data_range=1.0):
+    """skimage.metrics.peak_signal_noise_ratio in closed form: 10 log10(data_range^2 / mean((gt - img)^2)), in float64 (render.py:236)"""
+    gt, img = np.asarray(gt, np.float64), np.asarray(img, np.float64)
+    mse = float(np.mean((gt - img) ** 2))
+    return float("inf") if mse == 0.0 else 10.0 * math.log10(data_range * data_range / mse)
+
+
+@torch.no_grad()
+def render_view(scene, emitter_net, material_net, model_crf, rays, img_hw, SPP, spp, indir_depth=INDIR_DEPTH, exposure=1.0, gt=None, denoise=True, denoiser=None,
+                chunk=None):
+    """One iteration of the reference's per-view loop (render.py:157-279).
+
+    rays: (H*W, 12) float32 on the GPU -- origin, direction, dxdu, dydv as the datasets give them with ray_diff=True -- or the tuple of the four (H*W,3) tensors.
+    SPP // spp rounds of `path_tracing(..., spp, indir_depth)` and `render_intrinsics(..., spp)`, every sum divided by the round count (:222,:241-271);
+    L_full denoised (denoise=True, as the reference does; the guides are the pixel-centre primary hits) and mapped to LDR by model_crf(L, exposure) (None: no LDR);
+    gt: optional (H,W,3) / (H*W,3) LDR photograph in [0,1] -> 'psnr' (data_range 1).
+    Returns {'rgb_full' (H,W,3) HDR, 'rgb_ldr' (H,W,3) or None, 'kd', 'a_prime', 'emission', 'slf' (H,W,3), 'roughness', 'metallic' (H,W), 'psnr' or None, 'rounds'},
+    device tensors."""
+    H, W = int(img_hw[0]), int(img_hw[1])
+    if isinstance(rays, (tuple, list)):
+        rays_x, rays_d, dxdu, dydv = rays
+    else:
+        rays = L.require_gpu(rays, torch.float32, "rays").reshape(-1, 12)
+        rays_x, rays_d, dxdu, dydv = (rays[:, 3 * k:3 * k + 3].contiguous() for k in range(4))
+    rays_x = L.require_gpu(rays_x, torch.float32, "rays_x").reshape(-1, 3)
+    B, dev = rays_x.shape[0], rays_x.device
+    if B != H * W:
+        raise L.IrisError(f"render_view: {B} rays for an image of {H} x {W}")
+    rounds = int(SPP) // int(spp)
+    if rounds < 1:
+        raise L.IrisError(f"render_view: SPP ({SPP}) // spp ({spp}) is zero: nothing would be rendered")
+    L_full = torch.zeros(B, 3, device=dev)
+    maps = new_maps(B, dev)
+    for _ in range(rounds):
+        L_round = path_tracing(scene, emitter_net, material_net, rays_x, rays_d, dxdu, dydv, spp, indir_depth).detach()
+        if L_round.shape[0] != B:          # (no path continues after the primary hit: the integrator returns the un-reduced samples, as the reference's does)
+            L_round = L_round.reshape(B, int(spp), 3).mean(1)
+        L_full += L_round
+        render_intrinsics(scene, emitter_net, material_net, rays_x, rays_d, dxdu, dydv, spp, out=maps, chunk=chunk)
+    L_full = L_full / rounds
+    out = {k: (maps[k] / rounds).reshape((H, W, 3) if c == 3 else (H, W)) for k, c in MAPS}
+    if denoise:
+        if denoiser is None:
+            from .utils.denoise import Denoiser
+            denoiser = Denoiser((W, H), dev)
+        pos, nrm, _, _, valid = ray_intersect(scene, rays_x, torch.nn.functional.normalize(L.require_gpu(rays_d, torch.float32, "rays_d").reshape(-1, 3), dim=-1))
+        denoiser.set_guides(nrm, pos, valid)
+        L_full = denoiser(L_full.reshape(H, W, 3)).reshape(B, 3)
+    out["rgb_full"] = L_full.reshape(H, W, 3)
+    out["rgb_ldr"] = None if model_crf is None else model_crf(L_full.contiguous(), exposure).detach().reshape(H, W, 3)
+    out["psnr"] = None
+    if gt is not None and out["rgb_ldr"] is not None:
+        g = gt.detach().cpu().numpy() if torch.is_tensor(gt) else np.asarray(gt)
+        out["psnr"] = psnr(g.reshape(H, W, 3), out["rgb_ldr"].cpu().numpy(), 1.0)
+    out["rounds"] = rounds
+    return out
+
+
+def save_png(image, path):
+    """render.py:37-46 save_image without the colour map: clip to [0,1], * 255, uint8.  Written only when PIL imports; returns whether it was."""
+    try:
+        from PIL import Image
+    except ImportError:
+        return False
+    a = image.detach().cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
+    a = (np.clip(a, 0.0, 1.0) * 255).astype(np.uint8)
+    Image.fromarray(a).save(path)
+    return True
+
+
+def write_view(output_path, split, i, out, compression="zip"):
+    """The files of view i under the reference's tree (render.py:224-275): <output>/<split>/{rgb,diffuse,a_prime,roughness,metallic,emission}/{i:05d}_*.exr (+ .png).
+    EXR through the project's three-channel writer, R,G,B meaning as imageio writes them; roughness / metallic replicated to three equal channels.  slf/ also gets
+    {i:05d}_slf.exr: the reference accumulates that map and never writes it.  Returns the list of files written."""
+    from .utils.exr import write_exr
+    root = os.path.join(output_path, split)
+    dirs = {n: os.path.join(root, n) for n in OUT_DIRS}
+    for d in dirs.values():
+        os.makedirs(d, exist_ok=True)
+    files = []
+
+    def exr(folder, name, img):
+        a = img.detach().cpu().numpy()
+        if a.ndim == 2:
+            a = np.repeat(a[..., None], 3, -1)
+        p = os.path.join(dirs[folder], "{:0>5d}_{}.exr".format(i, name))
+        write_exr(p, a, compression)
+        files.append(p)
+
+    def png(folder, name, img):
+        a = img
+        if a.ndim == 2:
+            a = a[..., None].expand(-1, -1, 3)
+        p = os.path.join(dirs[folder], "{:0>5d}_{}.png".format(i, name))
+        if save_png(a, p):
+            files.append(p)
+    exr("rgb", "rgb_full", out["rgb_full"])
+    if out.get("rgb_ldr") is not None:
+        png("rgb", "rgb_full", out["rgb_ldr"])
+    for folder, name, key in (("diffuse", "kd", "kd"), ("a_prime", "a_prime", "a_prime"), ("roughness", "roughness", "roughness"), ("metallic", "metallic", "metallic"),
+                              ("emission", "emission", "emission")):
+        exr(folder, name, out[key])
+        png(folder, name, out[key])
+    exr("slf", "slf", out["slf"])
+    return files
+
+
+def write_metrics(path, psnr_list):
+    """rgb/metrics.txt (render.py:283-290) with the PSNR column only; views without a photograph are left out of the list and of the mean"""
+    with open(path, "w") as fh:
+        fh.write("Name, PSNR\n")
+        for i, p in psnr_list:
+            fh.write("{:0>5d}, {:.5f}\n".format(i, p))
+        fh.write("{:<5}, {:.5f}\n".format("mean", float(np.mean([p for _, p in psnr_list])) if psnr_list else float("nan")))
+
+
+def build_parser():
+    """The reference's render.py arguments (render.py:57-71 + configs/config.py) that matter here; the trainers' options it also registers are accepted and ignored."""
+    import argparse
+    parser = argparse.ArgumentParser(description="python -m iris_amd.render: the reference's render.py on MI355X")
+    parser.add_argument("--experiment_name", type=str, required=True)
+    parser.add_argument("--checkpoint_path", type=str, default="./checkpoints")
+    parser.add_argument("--output_path", type=str, default="outputs/kitchen_output")
+    parser.add_argument("--device", type=int, default=0)
+    parser.add_argument("--split", type=str, default="val")
+    parser.add_argument("--ckpt", type=str, default="last.ckpt")
+    parser.add_argument("--light_type", type=str, default="slf", choices=["slf", "area"])
+    parser.add_argument("--dataset", type=str, nargs=2, default=["synthetic", "../data/indoor_synthetic/kitchen"], help="dataset type (synthetic | real | scannetpp | generic) and its path")
+    parser.add_argument("--scene", type=str, default="")
+    parser.add_argument("--emitter_path", type=str, required=True, help="folder holding vslf.npz, emitter.pth and vslf_0.npz (render.py:109-124)")
+    parser.add_argument("--SPP", type=int, default=512)
+    parser.add_argument("--spp", type=int, default=8)
+    parser.add_argument("--indir_depth", type=int, default=INDIR_DEPTH)
+    parser.add_argument("--crf_basis", type=int, default=3)
+    parser.add_argument("--res_scale", type=float, default=1.0)
+    parser.add_argument("--ldr_img_dir", type=str, default=None)
+    parser.add_argument("--log_path", type=str, default="./logs")
+    for name, typ in (("batch_size", int), ("voxel_path", str), ("num_workers", int), ("dir_val", str), ("val_step", int), ("has_part", int), ("load_crf", int)):
+        parser.add_argument("--" + name, type=typ, default=None, help="(a trainer option of configs/config.py: accepted, unused)")
+    # additions (defaults reproduce the reference)
+    parser.add_argument("--material", type=str, default=None, help="pkg.module:factory returning material_net(position) -> {'albedo','roughness','metallic'} "
+                        "(default: the reference's NGPBRDF, loaded from the checkpoint's 'material.' entries)")
+    parser.add_argument("--cameras", type=str, default=None, help="generic camera JSON instead of the dataset's own camera files; a view may carry \"image\" (an EXR "
+                        "or, with PIL, PNG photograph in [0,1]) and \"exposure\"")
+    parser.add_argument("--emor_path", type=str, default=None, help="the EMoR basis file (default: crf/emor.txt under the working directory, as the reference)")
+    parser.add_argument("--denoise", type=str, default="atrous", choices=["atrous", "none"])
+    parser.add_argument("--compression", type=str, default="zip", choices=["none", "zips", "zip"])
+    parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--max_views", type=int, default=None)
+    return parser
+
+
+def _load_state(path):
+    try:
+        return torch.load(path, map_location="cpu")["state_dict"]
+    except Exception:     # noqa  (a Lightning checkpoint: see model.brdf.load_ngpbrdf)
+        return torch.load(path, map_location="cpu", weights_only=False)["state_dict"]
+
+
+def _views(args):
+    """(img_hw, views) of the split; every view: camera + optional 'image' / 'exposure'"""
+    from .utils import cameras
+    name, path = args.dataset
+    if args.cameras:
+        import json
+        img_hw, views = cameras.load_generic(args.cameras, args.res_scale)
+        with open(args.cameras) as fh:
+            meta = json.load(fh)["views"]
+        for v, m in zip(views, meta):
+            v["image"], v["exposure"] = m.get("image"), float(m.get("exposure", 1.0))
+            if v["image"] and not os.path.isabs(v["image"]):
+                v["image"] = os.path.join(os.path.dirname(os.path.abspath(args.cameras)), v["image"])
+        return img_hw, views
+    if name == "real":
+        return cameras.load_real(path, args.res_scale, split=args.split)
+    if name == "scannetpp":
+        return cameras.load_scannetpp(path, args.scene, args.res_scale, split=args.split)
+    if name == "synthetic":
+        import json
+        with open(os.path.join(path, args.split, "transforms.json")) as fh:
+            meta = json.load(fh)
+        img_hw = cameras._img_hw_from_exr(os.path.join(path, args.split, "Image", "000_0001.exr"), args.res_scale)
+        focal = float(0.5 * img_hw[1] / np.tan(0.5 * meta["camera_angle_x"]))
+        return img_hw, [{"kind": "synthetic", "focal": focal, "c2w": np.asarray(f["transform_matrix"], np.float32)[:3, :4]} for f in meta["frames"]]
+    raise L.IrisError("--dataset {!r}: synthetic | real | scannetpp, or --cameras cameras.json".format(name))
+
+
+def _view_rays(view, img_hw, device):
+    """rays with differentials, as the reference's datasets give them with ray_diff=True"""
+    from .utils.dataset import real_ldr, synthetic_ldr
+    if view["kind"] == "synthetic":
+        return synthetic_ldr.get_rays(synthetic_ldr.get_ray_directions(img_hw[0], img_hw[1], view["focal"]), view["c2w"], focal=view["focal"], device=device)
+    return real_ldr.to_world(real_ldr.get_direction(view["K"], img_hw), view["c2w"], True, view["K"], device=device)
+
+
+def _read_image(path, img_hw):
+    if path.lower().endswith(".exr"):
+        from .utils.exr import read_exr
+        a = read_exr(path)
+    else:
+        from PIL import Image
+        a = np.asarray(Image.open(path).convert("RGB"), np.float32) / 255.0
+    if a.shape[:2] != tuple(img_hw):
+        raise L.IrisError(f"{path}: {a.shape[:2]} pixels, the view has {tuple(img_hw)}")
+    return a
+
+
+def main(argv=None):
+    from .model.crf import EmorCRF
+    from .model.emitter import SLFEmitter
+    from .refine_shading import _load_material
+    from .utils.path_tracing import load_scene
+    args = build_parser().parse_args(argv)
+    if args.light_type != "slf":
+        raise L.IrisError("--light_type area (AreaEmitter, relighting) is not part of this stage: only slf")
+    if not torch.cuda.is_available():
+        raise L.IrisError("render needs a HIP device; there is no CPU path")
+    torch.cuda.set_device(args.device)
+    device = torch.device("cuda", args.device)
+    print("==========================\nExp: {}\nOutput: {}\nSplit: {}\n==========================".format(args.experiment_name, args.output_path, args.split))
+    name, path = args.dataset
+    if name == "scannetpp":
+        mesh_path = os.path.join(path, "data", args.scene, "scans", "scene.ply")
+    else:
+        mesh_path = os.path.join(path, "scene.obj")
+        if not os.path.exists(mesh_path) and os.path.exists(os.path.join(path, "scene.ply")):
+            mesh_path = os.path.join(path, "scene.ply")
+    assert os.path.exists(mesh_path), "mesh not found: " + mesh_path
+    scene = load_scene(mesh_path, device=device)
+    img_hw, views = _views(args)
+    if args.max_views is not None:
+        views = views[:args.max_views]
+
+    ckpt = os.path.join(args.checkpoint_path, args.experiment_name, args.ckpt)
+    material_net = _load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), ckpt)        # NGPBRDF(mask['voxel_min'], mask['voxel_max']) + 'material.' (:110-119)
+    if isinstance(material_net, torch.nn.Module):
+        material_net.to(device)
+    emitter_net = SLFEmitter(os.path.join(args.emitter_path, "emitter.pth"), os.path.join(args.emitter_path, "vslf_0.npz")).to(device)      # :123-124
+    crf_state = {k.replace("model_crf.", ""): v for k, v in _load_state(ckpt).items() if "model_crf." in k}                            # :130-135
+    if args.emor_path is None and not os.path.isfile(os.path.join(os.getcwd(), "crf", "emor.txt")) and "f0" in crf_state and "basis" in crf_state:
+        model_crf = EmorCRF.from_arrays(crf_state["f0"][0], crf_state["basis"])      # no EMoR file at hand: the curves are buffers of the module, so the checkpoint carries them
+    else:
+        model_crf = EmorCRF(args.crf_basis, emor_path=args.emor_path)
+    model_crf.load_state_dict(crf_state)
+    model_crf.to(device)
+    for m in (material_net, emitter_net, model_crf):
+        if isinstance(m, torch.nn.Module):
+            for p in m.parameters():
+                p.requires_grad = False
+    denoiser = None
+    if args.denoise == "atrous":
+        from .utils.denoise import Denoiser
+        denoiser = Denoiser(img_hw[::-1], device)
+    psnr_list = []
+    t0 = time.time()
+    for i, view in enumerate(views):
+        torch.manual_seed(args.seed * 1000003 + i); torch.cuda.manual_seed(args.seed * 1000003 + i)
+        rays = _view_rays(view, img_hw, device)
+        gt = _read_image(view["image"], img_hw) if view.get("image") else None
+        out = render_view(scene, emitter_net, material_net, model_crf, rays, img_hw, args.SPP, args.spp, args.indir_depth, exposure=float(view.get("exposure", 1.0)),
+                          gt=gt, denoise=denoiser is not None, denoiser=denoiser)
+        write_view(args.output_path, args.split, i, out, args.compression)
+        if out["psnr"] is not None:
+            psnr_list.append((i, out["psnr"]))
+    if psnr_list:
+        print("Mean PSNR: {:.5f}".format(float(np.mean([p for _, p in psnr_list]))))
+    os.makedirs(os.path.join(args.output_path, args.split, "rgb"), exist_ok=True)
+    write_metrics(os.path.join(args.output_path, args.split, "rgb", "metrics.txt"), psnr_list)
+    torch.cuda.synchronize()
+    print("[render] {} views: {:.2f} s".format(len(views), time.time() - t0))
+
+
+if __name__ == "__main__":
+    main()
