@@ -4,7 +4,9 @@
 // with; the substitute is a variance-guided edge-avoiding a-trous wavelet filter (Dammertz et al. 2010; the spatial part of SVGF,
 // Schied et al. 2017) that uses what this pipeline has and OptiX is not given: the primary-hit normal and position of every pixel.
 //   1. guides   : g0 = (n.xyz, valid), g1 = (x.xyz, 0)  packed once per view (shared by all maps of the view)
-//   2. variance : per map, luminance mean / variance in a 7x7 window weighted by the geometric weights  -> (rgb, var) float4
+//   2. variance : per map, luminance variance in a 7x7 window weighted by the geometric weights (centre 1)  -> (rgb, var) float4
+//        var = sum w (l_q - mean)^2 / sum w, evaluated as E[d^2] - E[d]^2 of d = l_q - l_p (shift invariant; the unshifted form loses the
+//        variance of a map with luminance 60 and 0.1 % noise to float32 cancellation)
 //   3. a-trous  : `iterations` passes, 5x5 B3-spline taps at stride 2^i, weight = h * w_n * w_p * w_l
 //        w_n = max(0, n_p.n_q)^sigma_n                     w_p = exp(-|n_p.(x_q-x_p)| / (sigma_p*|x_q-x_p| + 1e-12))   (scale free)
 //        w_l = exp(-|l_p-l_q| / (sigma_l*sqrt(gauss3x3(var)_p) + 1e-6));  colour' = sum w c / sum w;  var' = sum w^2 var / (sum w)^2
@@ -62,9 +64,10 @@ __global__ __launch_bounds__(256) void dn_variance_kernel(DnParams P, DnMaps mp,
         for (int m = 0; m < M; ++m) mp.a[m][p] = make_float4(0.f, 0.f, 0.f, 0.f);
         return;
     }
-    float ws = 0.f, m1[M], m2[M];
+    // moments of l_q - l_p: the variance is shift invariant, and E[d^2] - E[d]^2 of the shifted values does not cancel on a bright, quiet map
+    float ws = 0.f, m1[M], m2[M], lp[M];
 #pragma unroll
-    for (int m = 0; m < M; ++m) { m1[m] = 0.f; m2[m] = 0.f; }
+    for (int m = 0; m < M; ++m) { m1[m] = 0.f; m2[m] = 0.f; lp[m] = dn_lum(mp.in[m][p * 3], mp.in[m][p * 3 + 1], mp.in[m][p * 3 + 2]); }
     for (int dy = -3; dy <= 3; ++dy) {
         const int yy = y + dy;
         if (yy < 0 || yy >= P.H) continue;
@@ -77,8 +80,8 @@ __global__ __launch_bounds__(256) void dn_variance_kernel(DnParams P, DnMaps mp,
             ws += w;
 #pragma unroll
             for (int m = 0; m < M; ++m) {
-                const float l = dn_lum(mp.in[m][q * 3], mp.in[m][q * 3 + 1], mp.in[m][q * 3 + 2]);
-                m1[m] += w * l; m2[m] += w * l * l;
+                const float d = dn_lum(mp.in[m][q * 3], mp.in[m][q * 3 + 1], mp.in[m][q * 3 + 2]) - lp[m];
+                m1[m] += w * d; m2[m] += w * d * d;
             }
         }
     }

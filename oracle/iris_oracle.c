@@ -434,7 +434,8 @@ ORC_API void orc_shade_cached_bwd(const float *rows, const int64_t *idx, const f
  * 8(f)-4  denoiser substitute.  NO reference counterpart can be restated: bake_shading.py:81,129,198-200 call the closed OptiX AI
  * denoiser.  This is the CPU restatement of the BUILD'S OWN filter (iris_amd/csrc/iris_denoise.h: variance-guided edge-avoiding
  * a-trous), used to check the HIP kernels tap for tap (tolerance: expf / log2f differ in the last ulp between libm and the device);
- * quality is judged separately on PSNR against a high-spp bake.  "parity unpinned" by construction.
+ * quality is judged separately on PSNR against a high-spp bake.  "parity unpinned" by construction.  A float32 copy of the kernel's
+ * expressions cannot disagree with them; tests/denoise_ref64.py (float64, from the header's definition) is what both are held to.
  * ------------------------------------------------------------------------------------------ */
 static float dn_lum(const float *c) { return 0.2126f * c[0] + 0.7152f * c[1] + 0.0722f * c[2]; }
 typedef struct { int H, W; float sigma_l, sigma_n, sigma_p; const float *normal, *position; const uint8_t *valid; } dn_ctx;
@@ -465,7 +466,8 @@ ORC_API void orc_denoise(const float *normal, const float *position, const uint8
         for (int x = 0; x < W; ++x) {
             int64_t p = (int64_t)y * W + x;
             if (!dn_valid(&d, p)) continue;
-            float ws = 0.f, m1 = 0.f, m2 = 0.f;
+            float ws = 0.f, m1 = 0.f, m2 = 0.f;   /* moments of l_q - l_p, as the kernel (shift invariant, no cancellation on a bright quiet map) */
+            const float lp = dn_lum(in + p * 3);
             for (int dy = -3; dy <= 3; ++dy) {
                 int yy = y + dy;
                 if (yy < 0 || yy >= H) continue;
@@ -475,7 +477,7 @@ ORC_API void orc_denoise(const float *normal, const float *position, const uint8
                     int64_t q = (int64_t)yy * W + xx;
                     float w = (dx == 0 && dy == 0) ? 1.f : dn_geo(&d, p, q);
                     if (w == 0.f) continue;
-                    float l = dn_lum(in + q * 3);
+                    float l = dn_lum(in + q * 3) - lp;
                     ws += w; m1 += w * l; m2 += w * l * l;
                 }
             }
