@@ -157,11 +157,56 @@ def source_hash():
 def device_index(device):
     """The HIP device ordinal a torch device names: `torch.device('cuda')` (no index) is torch's CURRENT device on this rank, not device 0 -- one process per
     GPU sets it once (torch.cuda.set_device(LOCAL_RANK)) and then passes index-less devices around."""
-    import torch
     device = torch.device(device)
     if device.type != "cuda":
         raise IrisError(f"{device}: the HIP path needs a GPU device (there is no CPU fallback)")
     return device.index if device.index is not None else torch.cuda.current_device()
+
+
+class Native:
+    """The ONE owner of a native object (iris_scene / iris_slf / iris_emitter / iris_ngp): its pointer, the entry point that destroys it and the device
+    ordinal (device_index) it was created for, with the tensor_keys of the tensors it was filled from (`keys`, a list: they describe this object and leave with
+    it).  The pointer is destroyed exactly once, by free() or when the owner is collected.  copy.copy, copy.deepcopy and pickle never duplicate it: the copy
+    is an EMPTY owner (ptr None, no keys), so a deep copy or unpickle of a module builds its own native object on first use.  (A SHALLOW copy of a module
+    shares the module's tensors and, with them, this one owner: nothing is destroyed before both are gone.)"""
+
+    def __init__(self, ptr=None, destroy=None, device=None, keys=()):
+        self.ptr, self.destroy, self.device, self.keys = ptr, destroy, device, list(keys)
+
+    def free(self):
+        d = self.__dict__               # (plain dict access: at interpreter shutdown little else can be relied on)
+        p, d["ptr"] = d.get("ptr"), None
+        if p:
+            d["destroy"](p)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:     # noqa  (interpreter shutdown: the library, or the helpers the call needs, may be gone already)
+            pass
+
+    def __reduce__(self):
+        return (Native, ())
+
+
+class tensor_key:
+    """What a device-side copy of tensor `t` was made from: the tensor OBJECT, its _version, its data_ptr() and its device.  A change in any of the four means the
+    copy is stale: an in-place write bumps _version; a rebound buffer (`vslf.radiance = vslf.radiance / n`) is a new object even when the caching allocator hands it
+    the address -- and _version 0 -- of the tensor that was uploaded before; `p.data = other` and Module.to() keep the object and its _version and change only
+    data_ptr().  The tensor object itself is kept (not only its data_ptr): holding the reference keeps that address from being reused while the key is alive.
+    tensor_key() matches nothing, and that is what a copy or unpickle of a key is: the key is dropped with the native object it describes."""
+    __slots__ = ("t", "version", "ptr", "device")
+
+    def __init__(self, t=None):
+        self.t = t
+        if t is not None:
+            self.version, self.ptr, self.device = t._version, t.data_ptr(), t.device
+
+    def fresh(self, t):
+        return self.t is t and self.version == t._version and self.ptr == t.data_ptr() and self.device == t.device
+
+    def __reduce__(self):
+        return (tensor_key, ())
 
 
 def build_id():

@@ -200,7 +200,7 @@ class NGPBRDF(BaseBRDF):
         super().__init__()
         self.voxel_min, self.voxel_max = float(voxel_min), float(voxel_max)
         self.mlp = _TcnnParams(int(L.lib().iris_ngp_n_params()))
-        self._h, self._h_key = None, None
+        self._native = L.Native()
 
     def init_parameters(self, seed=1337):
         """tiny-cuda-nn's initial distributions, drawn from a torch generator on the CPU: tables U(-1e-4, 1e-4), the three matrices Xavier-uniform
@@ -224,50 +224,33 @@ class NGPBRDF(BaseBRDF):
         import ctypes as C
         p = self.mlp.params
         idx = L.device_index(device)
+        n = self._native
+        if n.ptr is not None and n.device == idx and n.keys[0].fresh(p):
+            return n.ptr
         if p.is_cuda:
-            # parameters that live on the GPU (a network being trained): ONE handle, refreshed on the device whenever the tensor has been written to
-            # (every optimizer step bumps _version) -- no 112 MB round trip through the host
+            # parameters that live on the GPU (a network being trained): ONE native object, refreshed on the device whenever the tensor has been written to
+            # or swapped (L.tensor_key: every optimizer step bumps _version) -- no 112 MB round trip through the host
             if p.device.index != idx:
                 raise L.IrisError(f"NGPBRDF: mlp.params is on {p.device}, position on cuda:{idx}")
-            key = ("dev", idx, p.data_ptr(), p._version)
-            if self._h is None or self._h_key is None or self._h_key[:3] != key[:3]:
-                self._free()
-                h = C.c_void_p()
-                L.check(L.lib().iris_ngp_create(None, p.numel(), self.voxel_min, self.voxel_max, idx, C.byref(h)))
-                self._h, self._h_key = h, None
-            if self._h_key != key:
-                src = p.detach()
-                src = src if src.is_contiguous() and src.dtype == torch.float32 else src.to(torch.float32).contiguous()
-                with torch.cuda.device(p.device):
-                    L.check(L.lib().iris_ngp_set_params_dev(self._h, L.ptr(src), src.numel(), L.stream()))
-                self._h_key = key
-            return self._h
-        key = (str(device), p.data_ptr(), p._version)
-        if self._h is None or self._h_key != key:
-            self._free()
+            if n.ptr is None or n.device != idx:
+                n = self._create(None, p.numel(), idx)
+            src = p.detach()
+            src = src if src.is_contiguous() and src.dtype == torch.float32 else src.to(torch.float32).contiguous()
+            with torch.cuda.device(idx):
+                L.check(L.lib().iris_ngp_set_params_dev(n.ptr, L.ptr(src), src.numel(), L.stream()))
+        else:
             host = p.detach().to("cpu", torch.float32).contiguous()
-            h = C.c_void_p()
-            L.check(L.lib().iris_ngp_create(C.c_void_p(host.data_ptr()), host.numel(), self.voxel_min, self.voxel_max, idx, C.byref(h)))
-            self._h, self._h_key = h, key
-        return self._h
+            n = self._create(C.c_void_p(host.data_ptr()), host.numel(), idx)
+        n.keys[0] = L.tensor_key(p)
+        return n.ptr
 
-    def _free(self):
-        h = self.__dict__.get("_h")
-        if h is not None:
-            self.__dict__["_h"] = None              # (not through nn.Module.__setattr__: at interpreter shutdown its helpers may be gone)
-            try:
-                L.lib().iris_ngp_destroy(h)
-            except Exception:     # noqa  (interpreter shutdown)
-                pass
-
-    def __del__(self):
-        self._free()
-
-    def __getstate__(self):
-        """copy.deepcopy / pickle: the native handle belongs to THIS object (a raw pointer: a copy would free it twice); the copy builds its own on first use"""
-        state = self.__dict__.copy()
-        state["_h"], state["_h_key"] = None, None
-        return state
+    def _create(self, host_params, n_params, idx):
+        import ctypes as C
+        self._native.free()
+        h = C.c_void_p()
+        L.check(L.lib().iris_ngp_create(host_params, n_params, self.voxel_min, self.voxel_max, idx, C.byref(h)))
+        self._native = L.Native(h, L.lib().iris_ngp_destroy, idx, (L.tensor_key(),))      # (the empty key: the parameters are not in yet)
+        return self._native
 
     def _run(self, pos):
         N, dev = pos.shape[0], pos.device

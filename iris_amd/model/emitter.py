@@ -32,28 +32,20 @@ class SLFEmitter(nn.Module):
         emitter_pdf = NF.normalize(torch.ones_like(weight["emitter_area"]), dim=-1, p=1)
         self.register_buffer("emitter_pdf", emitter_pdf)
         self.register_buffer("emitter_cdf", emitter_pdf.cumsum(-1).contiguous())
-        self._h = None
-        self._h_device = None
-        self._struct_ver = None
-        self._rad_version = None
+        self._native = L.Native()
 
     def refresh(self):
-        h, self._h = self._h, None
-        if h:
-            L.lib().iris_emitter_destroy(h)
-
-    @staticmethod
-    def _ver(t):
-        return (t._version, t.data_ptr(), str(t.device), tuple(t.shape))
+        self._native.free()
 
     def handle(self, device):
-        """Device-side tables of this emitter.  They follow the module: the tables are rebuilt when is_emitter / emitter_area /
-        emitter_vertices change (load_state_dict, in-place edits, .to()) and the radiance table is re-uploaded when `radiance`
+        """Device-side tables of this emitter.  They follow the module (L.tensor_key): the tables are rebuilt when is_emitter / emitter_area /
+        emitter_vertices change (load_state_dict, in-place edits, rebinding, .to()) and the radiance table is re-uploaded when `radiance`
         does (SLFEmitterLearn's optimiser steps, model/emitter.py:268), so a cached handle never goes stale."""
-        device = torch.device(device)
-        struct = (self._ver(self.is_emitter), self._ver(self.emitter_area), self._ver(self.emitter_vertices))
-        if self._h is None or self._h_device != device or self._struct_ver != struct:
-            self.refresh()
+        idx = L.device_index(device)
+        n = self._native
+        k = n.keys
+        if n.ptr is None or n.device != idx or not (k[0].fresh(self.is_emitter) and k[1].fresh(self.emitter_area) and k[2].fresh(self.emitter_vertices)):
+            n.free()
             ie = np.ascontiguousarray(self.is_emitter.detach().cpu().numpy(), dtype=np.uint8)
             rad = L.host_f32(self.radiance).reshape(-1, 3)
             area = L.host_f32(self.emitter_area).reshape(-1)
@@ -64,25 +56,19 @@ class SLFEmitter(nn.Module):
             L.check(L.lib().iris_emitter_create(ie.ctypes.data_as(C.c_void_p), ie.shape[0], rad.ctypes.data_as(C.c_void_p), rad.shape[0],
                                                 area.ctypes.data_as(C.c_void_p), area.shape[0],
                                                 verts.ctypes.data_as(C.c_void_p) if has_v else None, cdf.ctypes.data_as(C.c_void_p) if has_v else None,
-                                                L.device_index(device), C.byref(h)))
-            self._h, self._h_device, self._struct_ver = h, device, struct
-            self._rad_version = self._ver(self.radiance)
-        elif self._rad_version != self._ver(self.radiance):
-            rr = self.radiance_on(device)
-            with torch.cuda.device(device):
-                L.check(L.lib().iris_emitter_set_radiance(self._h, L.ptr(rr), rr.shape[0], L.stream()))
-            self._rad_version = self._ver(self.radiance)
-        return self._h
+                                                idx, C.byref(h)))
+            n = self._native = L.Native(h, L.lib().iris_emitter_destroy, idx, (L.tensor_key(self.is_emitter), L.tensor_key(self.emitter_area),
+                                                                               L.tensor_key(self.emitter_vertices), L.tensor_key(self.radiance)))
+        elif not k[3].fresh(self.radiance):
+            rr = self.radiance_on(torch.device("cuda", idx))
+            with torch.cuda.device(idx):
+                L.check(L.lib().iris_emitter_set_radiance(n.ptr, L.ptr(rr), rr.shape[0], L.stream()))
+            k[3] = L.tensor_key(self.radiance)
+        return n.ptr
 
     def radiance_on(self, device):
         """`radiance` as a detached, contiguous float32 tensor on `device` (the files are loaded with map_location='cpu')."""
         return self.radiance.detach().to(device=device, dtype=torch.float32).contiguous()
-
-    def __del__(self):
-        try:
-            self.refresh()
-        except Exception:
-            pass
 
     def forward(self, position):
         """surface light field from queried location (model/emitter.py:175-178)"""

@@ -26,43 +26,26 @@ class VoxelSLF(nn.Module):
         self.register_buffer("inds", inds)
         self.register_buffer("radiance", torch.zeros(len(ii), 3, device=dev))
         self.register_buffer("count", torch.zeros(len(ii), dtype=torch.long, device=dev))
-        self._h = None
-        self._h_device = None
-        self._ver = None
-        self._rver = None
+        self._native = L.Native()
 
     # -- device handle ---------------------------------------------------------------------------------
     def refresh(self):
         """Drop the device-side tables; they are rebuilt from the buffers at the next lookup."""
-        h, self._h = self._h, None
-        if h:
-            L.lib().iris_slf_destroy(h)
-
-    @staticmethod
-    def _tver(t):
-        # identity + version of the uploaded tensor.  The tensor object itself is kept (not its data_ptr): a rebound buffer
-        # (`vslf.radiance = vslf.radiance / n`) is a new object even when the caching allocator hands it the address -- and _version 0 -- of
-        # the tensor that was uploaded before, and holding the reference keeps that address from being reused while the key is alive.
-        return (t, t._version)
-
-    @staticmethod
-    def _same(a, b):
-        return a is not None and b is not None and a[0] is b[0] and a[1] == b[1]
+        self._native.free()
 
     def handle(self, device, need_radiance=True):
-        """Device-side tables (int32 index grid + padded radiance rows).  They follow the module: the tables are rebuilt when `inds`
-        changed since the upload (load_state_dict through a parent module, in-place edits, .to()), and the radiance rows alone are
-        re-uploaded when only `radiance` did (scatter_add, mean pooling) -- lazily, the next time a lookup needs them."""
-        device = torch.device(device)
-        iv = self._tver(self.inds)
-        if self._h is None or self._h_device != device or not self._same(self._ver, iv):
-            self.refresh()
+        """Device-side tables (int32 index grid + padded radiance rows).  They follow the module (L.tensor_key): the tables are rebuilt when `inds`
+        changed since the upload (load_state_dict, in-place edits, rebinding, .to()), and the radiance rows alone are re-uploaded when only
+        `radiance` did (scatter_add, mean pooling) -- lazily, the next time a lookup needs them."""
+        # the device ordinal resolved ONCE ('cuda' without an index = torch's current device): the same ordinal decides whether the handle is for this device,
+        # whether the tensors are already there, which device torch makes current around the call, and which device the C side creates the tables on
+        idx = L.device_index(device)
+        n = self._native
+        if n.ptr is None or n.device != idx or not n.keys[0].fresh(self.inds):
+            n.free()
             h = C.c_void_p()
-            # the device index resolved ONCE ('cuda' without an index = torch's current device): the same index decides whether the tensors are already
-            # there, which device torch makes current around the call, and which device the C side creates the tables on
-            idx = device.index if device.index is not None else (torch.cuda.current_device() if device.type == "cuda" else 0)
             on_dev = lambda t: t.is_cuda and t.device.index == idx
-            if device.type == "cuda" and on_dev(self.inds) and on_dev(self.radiance):
+            if on_dev(self.inds) and on_dev(self.radiance):
                 inds = self.inds.detach().to(torch.int64).contiguous()
                 rad = self.radiance.detach().to(torch.float32).contiguous().reshape(-1, 3)
                 with torch.cuda.device(idx):
@@ -72,24 +55,13 @@ class VoxelSLF(nn.Module):
                 rad = L.host_f32(self.radiance).reshape(-1, 3)
                 L.check(L.lib().iris_slf_create(inds.ctypes.data_as(C.c_void_p), self.H, rad.ctypes.data_as(C.c_void_p), rad.shape[0],
                                                 self.voxel_min, self.voxel_max, idx, C.byref(h)))
-            self._h, self._h_device, self._ver, self._rver = h, device, iv, self._tver(self.radiance)
-        elif need_radiance and not self._same(self._rver, self._tver(self.radiance)):
-            rr = self.radiance.detach().to(device=device, dtype=torch.float32).contiguous()
-            with torch.cuda.device(device):
-                L.check(L.lib().iris_slf_set_radiance(self._h, L.ptr(rr), rr.shape[0], L.stream()))
-            self._rver = self._tver(self.radiance)
-        return self._h
-
-    def load_state_dict(self, *a, **k):
-        r = super().load_state_dict(*a, **k)
-        self.refresh()
-        return r
-
-    def __del__(self):
-        try:
-            self.refresh()
-        except Exception:
-            pass
+            n = self._native = L.Native(h, L.lib().iris_slf_destroy, idx, (L.tensor_key(self.inds), L.tensor_key(self.radiance)))
+        elif need_radiance and not n.keys[1].fresh(self.radiance):
+            rr = self.radiance.detach().to(device=torch.device("cuda", idx), dtype=torch.float32).contiguous()
+            with torch.cuda.device(idx):
+                L.check(L.lib().iris_slf_set_radiance(n.ptr, L.ptr(rr), rr.shape[0], L.stream()))
+            n.keys[1] = L.tensor_key(self.radiance)
+        return n.ptr
 
     # -- reference API ---------------------------------------------------------------------------------
     def _lookup(self, x, want_idx, want_rgb):

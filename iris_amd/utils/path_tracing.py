@@ -33,24 +33,19 @@ class Scene:
         else:   # explicit node layout: diagnostics entry point (A/B baseline)
             L.check(L.lib().iris_debug_scene_create(v.ctypes.data_as(C.c_void_p), v.shape[0], f.ctypes.data_as(C.c_void_p), f.shape[0],
                                                     L.device_index(self.device), int(layout), C.byref(h)))
-        self._h = h
+        self._native = L.Native(h, L.lib().iris_scene_destroy, L.device_index(self.device))
 
     @property
     def handle(self):
-        return self._h
+        return self._native.ptr
 
     def info(self):
         i = L.SceneInfo()
-        L.check(L.lib().iris_scene_get_info(self._h, C.byref(i)))
+        L.check(L.lib().iris_scene_get_info(self.handle, C.byref(i)))
         return {k: getattr(i, k) for k, _ in L.SceneInfo._fields_}
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                L.lib().iris_scene_destroy(h)
-            except Exception:
-                pass
+    def __reduce__(self):
+        raise L.IrisError("Scene cannot be copied or pickled: it keeps no mesh to rebuild its native BVH from (build another Scene from the vertices and faces)")
 
 
 def load_mesh(path):

@@ -1,11 +1,17 @@
-"""Device-side tables follow the modules: SLFEmitter / VoxelSLF cache their handles keyed on the tensors' version counters,
-so in-place edits, load_state_dict through the parent module and optimiser steps are picked up without an explicit refresh(); the modules may
-live on the CPU (the reference loads them with map_location='cpu'); a mesh / emitter mismatch is an error, not an out-of-bounds read."""
+"""Device-side tables follow the modules: SLFEmitter / VoxelSLF / NGPBRDF keep their native object in ONE owner (iris_amd._lib.Native) keyed on the
+tensors it was filled from (iris_amd._lib.tensor_key: object, _version, data_ptr, device), so in-place edits, load_state_dict through the parent module,
+rebound buffers, `.data` swaps and optimiser steps are picked up without an explicit refresh(); a handle is for a device ORDINAL, however the device was
+spelt; copies of a module build their own native object and a Scene refuses to be copied; the modules may live on the CPU (the reference loads them
+with map_location='cpu'); a mesh / emitter mismatch is an error, not an out-of-bounds read."""
+import copy
+import pickle
+
 import numpy as np
 import pytest
 import torch
 
-from test_hip_parity import dev, room_setup, T  # noqa: F401  (fixtures)
+from conftest import golden
+from test_hip_parity import dev, room_setup, T, _emitter_files  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -172,3 +178,114 @@ def test_resolved_and_plain_hit_slots_give_the_same_maps(dev, room_setup):
     for l, sid in ((1, 1), (2, 4)):
         c0, c1, _ = bs.bake_specular(s["sc"], s["em"], pos, nrm, wo, lobes[l], 64, seed=4, stream_id=sid, want_tri=True)
         assert torch.equal(view[l][0], c0) and torch.equal(view[l][1], c1)
+
+
+def test_index_less_device_does_not_thrash(dev, room_setup):
+    """A handle is for a device ORDINAL: `cuda` and `cuda:<current>` alternating keep the one native object (a rebuild would come from the host every time and drop
+    the emitter's cached fused leaf records)."""
+    em = room_setup["em"]
+    for m in (em, em.slf):
+        a = m.handle(torch.device("cuda")).value
+        owner = m._native
+        b = m.handle(torch.device("cuda", torch.cuda.current_device())).value
+        c = m.handle(torch.device("cuda")).value
+        assert a == b == c and a is not None
+        assert m._native is owner                   # (a rebuild could be handed the freed address again: it would still make a new owner)
+
+
+def _emitter_probe(vertices, faces, tri, dev):
+    """eval_emitter inputs: the centroids of triangles `tri`, rough enough (1 > trace_roughness) for the radiance cache to answer where no emitter does"""
+    pos = T(vertices[faces[tri]].mean(1).astype(np.float32), dev)
+    return pos, T(tri, dev, torch.int64), torch.ones(len(tri), device=dev)
+
+
+def test_copies_of_modules_that_have_run(dev, room_setup):
+    """deepcopy / pickle of an emitter (and its VoxelSLF) that has run: the copy owns no native pointer, builds its own on first use, answers with the same bits, and its
+    death leaves the original's tables alone; a shallow copy shares the original's tensors and its one owner"""
+    s = room_setup
+    em, r = s["em"], s["room"]
+    is_em = r["is_emitter"].astype(bool)
+    tri = np.concatenate([np.resize(np.flatnonzero(is_em), 128), np.flatnonzero(~is_em)[:128 * 500:500]])
+    pos, tri_t, rough = _emitter_probe(r["vertices"], r["faces"], tri, dev)
+
+    def run(m):
+        return m.eval_emitter(pos, None, tri_t, roughness=rough) + (m.slf(pos)["rgb"], m.slf.spatial_idx(pos))
+
+    def same(a, b):
+        return all(torch.equal(x, y) for x, y in zip(a, b))
+    ref = run(em)
+    assert float(ref[0][:128].min()) > 0 and float(ref[0][128:].sum()) > 0 and int((ref[4] >= 0).sum()) > 0     # emitters, and the cache behind the other triangles
+    assert em._native.ptr is not None and em.slf._native.ptr is not None
+    for other in (copy.deepcopy(em), pickle.loads(pickle.dumps(em))):
+        assert other._native.ptr is None and other.slf._native.ptr is None
+        assert same(run(other), ref)
+        assert other._native.ptr.value != em._native.ptr.value and other.slf._native.ptr.value != em.slf._native.ptr.value
+        del other
+        assert same(run(em), ref)
+    shallow = copy.copy(em)
+    assert same(run(shallow), ref)
+    del shallow
+    assert same(run(em), ref)
+
+
+def test_scene_is_not_copyable(dev):
+    from iris_amd import _lib as L
+    from iris_amd.utils.path_tracing import Scene, ray_intersect
+    v = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0]], np.float32)
+    f = np.array([[0, 1, 2], [1, 3, 2]], np.int32)
+    sc = Scene(v, f, device=dev)
+    for fn in (copy.copy, copy.deepcopy, pickle.dumps):
+        with pytest.raises(L.IrisError, match="cannot be copied"):
+            fn(sc)
+    o = torch.tensor([[0.2, 0.2, 1.0], [0.8, 0.8, 1.0], [2.0, 2.0, 1.0]], device=dev)
+    d = torch.tensor([[0.0, 0.0, -1.0]], device=dev).repeat(3, 1)
+    pos, _, _, idx, valid = ray_intersect(sc, o, d)
+    assert idx.tolist()[:2] == [0, 1] and valid.tolist() == [True, True, False]
+    assert torch.allclose(pos[:2], torch.tensor([[0.2, 0.2, 0.0], [0.8, 0.8, 0.0]], device=dev), atol=1e-6)
+
+
+def test_rebound_and_swapped_radiance_reaches_the_emitter_tables(dev, tmp_path):
+    """`em.radiance = em.radiance / 2` in a loop (fresh tensors start at _version 0 and may reuse a freed address) and `radiance.data = new` on SLFEmitterLearn's
+    parameter (same object, same _version) both reach the device table: each Le is the previous one halved, bit for bit (powers of two are exact)."""
+    from iris_amd.model.emitter import SLFEmitter, SLFEmitterLearn
+    g = golden("bake_box.npz")
+    ep, sp = _emitter_files(tmp_path, g["is_emitter"], g["emitter_area"], g["emitter_radiance"], g["slf_mask"], g["slf_inds"], g["slf_radiance"],
+                            float(g["voxel_min"]), float(g["voxel_max"]))
+    tri = np.resize(np.flatnonzero(g["is_emitter"]), 256)
+    pos, tri_t, _ = _emitter_probe(g["verts"], g["faces"], tri, dev)
+    em = SLFEmitter(ep, sp)
+    prev = em.eval_emitter(pos, None, tri_t)[0]
+    assert float(prev.max(1).values.min()) > 0
+    owner = em._native
+    for _ in range(6):
+        em.radiance = em.radiance / 2.0
+        Le = em.eval_emitter(pos, None, tri_t)[0]
+        assert torch.equal(Le, prev / 2.0)
+        prev = Le
+    assert em._native is owner                      # the radiance rows alone were re-uploaded
+    learn = SLFEmitterLearn(ep, sp)
+    prev = learn.eval_emitter(pos, None, tri_t)[0]
+    p, version = learn.radiance, learn.radiance._version
+    learn.radiance.data = learn.radiance.data / 2.0
+    assert learn.radiance is p and p._version == version
+    assert torch.equal(learn.eval_emitter(pos, None, tri_t)[0], prev / 2.0)
+
+
+def test_data_swap_on_device_parameters_refreshes_the_network_in_place(dev):
+    from iris_amd import _lib as L
+    from iris_amd.model.brdf import NGPBRDF
+    n = int(L.lib().iris_ngp_n_params())
+    params, other = ((torch.rand(n, generator=torch.Generator().manual_seed(sd)) * 2 - 1) * 0.3 for sd in (6, 7))
+    pos = (torch.rand(300, 3, generator=torch.Generator().manual_seed(3)) * 4.5 - 2.0).to(dev)
+    net = NGPBRDF(-2.0, 2.5)
+    net.load_state_dict({"mlp.params": params})
+    net.to(dev)
+    first = net(pos)
+    owner, ptr = net._native, net._native.ptr.value
+    net.mlp.params.data = other.to(dev)
+    out = net(pos)
+    assert net._native is owner and net._native.ptr.value == ptr          # refreshed in place, not re-created
+    fresh = NGPBRDF(-2.0, 2.5)
+    fresh.load_state_dict({"mlp.params": other})
+    ref = fresh(pos)
+    assert all(torch.equal(out[k], ref[k]) for k in ref) and not torch.equal(out["albedo"], first["albedo"])

@@ -116,7 +116,7 @@ def test_copies_and_streams_of_one_network():
     ref, ref2 = net(pos), net(pos2)
     torch.cuda.synchronize()
     for other in (copy.deepcopy(net), pickle.loads(pickle.dumps(net))):
-        assert other._h is None
+        assert other._native.ptr is None
         out = other(pos)
         assert all(torch.equal(out[k], ref[k]) for k in ref)
         del other

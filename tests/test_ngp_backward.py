@@ -303,13 +303,13 @@ def test_device_refresh_after_an_optimizer_step():
     pos, cot = pos.to(dev), tuple(c.to(dev) for c in cot)
     opt = torch.optim.Adam(net.parameters(), lr=1e-2)
     _hip_gradient(net, pos, cot)
-    handle = net._h.value
+    handle = net._native.ptr.value
     before = net.mlp.params.detach().clone()
     opt.step()
     assert not torch.equal(before, net.mlp.params.detach())
     with torch.no_grad():
         out = net(pos)
-    assert net._h.value == handle                                                   # refreshed in place, not re-created
+    assert net._native.ptr.value == handle                                                   # refreshed in place, not re-created
     fresh = NGPBRDF(VMIN, VMAX)
     fresh.load_state_dict({"mlp.params": net.mlp.params.detach().cpu()})            # CPU-resident, frozen: the host path
     ref = fresh(pos)
