@@ -409,6 +409,19 @@ IRIS_API int iris_crf_bwd(const float *grid, const float *table, int n, const fl
  * sequential cumsum up to summation order. */
 IRIS_API int iris_crf_inv_table(const float *grid, const float *table, int n, float *inv_table, iris_stream_t);
 
+/* ---- image-quality metrics: SSIM and the squared error behind PSNR (render.py:236-239) ------------------------ */
+/* a, b: image stacks (N, H, W, C) float32, interleaved, C 1 or 3, H and W >= 7; data_range R > 0.  The contract is skimage's
+ * structural_similarity defaults restated (uniform 7 x 7 window, K1 0.01, K2 0.03, sample covariance, only the windows that lie fully inside the
+ * image), with the window moments taken of the window shifted by its own centre pixel -- arithmetic and operation order: iris_amd/csrc/iris_metrics.h.
+ * sums (N, C, 2) float64, per image and channel: [0] sum of ((double)a - (double)b)^2 over the H W pixels, [1] sum of S over the (H - 6)(W - 6) windows;
+ * PSNR = 10 log10(R^2 C H W / sum_c sums[c][0]), SSIM = mean_c sums[c][1] / ((H - 6)(W - 6)).  ssim_map (N, H - 6, W - 6, C) float32 receives S of
+ * every window, or NULL: not written; the sums are the same bits either way.  Partial sums go through workspace
+ * (iris_image_metrics_workspace_bytes() bytes, 8-byte aligned; 0: the shape is not supported) with plain stores and are added in a fixed order: no
+ * atomics, bitwise reproducible for a given shape.  A non-finite pixel makes its image's sums NaN.  Two launches on the stream. */
+IRIS_API uint64_t iris_image_metrics_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C);
+IRIS_API int iris_image_metrics(const float *a, const float *b, int32_t N, int32_t H, int32_t W, int32_t C, float data_range, double *sums,
+                       float *ssim_map, void *workspace, uint64_t workspace_bytes, iris_stream_t);
+
 /* ---- OpenEXR ZIP / ZIPS writer, device half ------------------------------------------------------------- */
 /* Deflate of the scanline blocks of n_maps maps (utils/exr.py scanline_blocks_torch): full (n_maps, n_full, block_bytes) and tail (n_maps, tail_bytes)
  * hold the PREDICTED bytes (reordered, delta-coded) of every block, device uint8, contiguous.  records receives, map by map, every chunk record as the

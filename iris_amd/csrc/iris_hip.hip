@@ -21,6 +21,7 @@
 #include "iris_pt.h"
 #include "iris_cache.h"
 #include "iris_denoise.h"
+#include "iris_metrics.h"
 #include "iris_ngp.h"
 #include "iris_prop.h"
 #include "iris_crf.h"
@@ -1042,6 +1043,46 @@ extern "C" IRIS_API int iris_denoise(const float* normal, const float* position,
             case 3: denoise_group<3>(P, mp, g0, g1, iterations, st); break;
             default: denoise_group<4>(P, mp, g0, g1, iterations, st); break;
         }
+    }
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
+// ---- SSIM and the squared error behind PSNR (iris_metrics.h; render.py:236-239)
+static bool metrics_shape(int N, int H, int W, int C, int& tiles_x, int& tiles_y) {
+    if (N < 1 || H < 7 || W < 7 || (C != 1 && C != 3)) return false;
+    tiles_x = (W + kMetTileX - 1) / kMetTileX;
+    tiles_y = (H + kMetTileY - 1) / kMetTileY;
+    return (int64_t)N * tiles_x * tiles_y <= INT32_MAX && (int64_t)W * C <= INT32_MAX - 4 * kMetTileX;       // the grid, and a row's element index, are ints
+}
+extern "C" IRIS_API uint64_t iris_image_metrics_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C) {
+    int tx, ty;
+    if (!metrics_shape(N, H, W, C, tx, ty)) return 0;
+    return (uint64_t)N * tx * ty * C * 2 * sizeof(double);
+}
+extern "C" IRIS_API int iris_image_metrics(const float* a, const float* b, int32_t N, int32_t H, int32_t W, int32_t C, float data_range, double* sums,
+                                           float* ssim_map, void* workspace, uint64_t workspace_bytes, iris_stream_t stream) {
+    int tx, ty;
+    if (!metrics_shape(N, H, W, C, tx, ty))
+        return fail(IRIS_ERR_ARG, "iris_image_metrics: bad shape (N, H, W, C) = (" + std::to_string(N) + ", " + std::to_string(H) + ", " + std::to_string(W) + ", " +
+                                      std::to_string(C) + "): N >= 1, H >= 7, W >= 7, C 1 or 3");
+    if (!(data_range > 0.f) || !std::isfinite(data_range)) return fail(IRIS_ERR_ARG, "iris_image_metrics: data_range must be positive and finite");
+    if (!a || !b || !sums || (uintptr_t)a % 4 || (uintptr_t)b % 4 || (uintptr_t)sums % 8 || (uintptr_t)ssim_map % 4)
+        return fail(IRIS_ERR_ARG, "iris_image_metrics: null or misaligned a / b / sums / ssim_map");
+    const uint64_t need = iris_image_metrics_workspace_bytes(N, H, W, C);
+    if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 8)
+        return fail(IRIS_ERR_ARG, "iris_image_metrics: an 8-byte aligned workspace of " + std::to_string(need) + " bytes is required (got " +
+                                      std::to_string(workspace_bytes) + ")");
+    const float k1r = 0.01f * data_range, k2r = 0.03f * data_range;
+    MetArgs g{a, b, (double*)workspace, ssim_map, H, W, tx, ty, k1r * k1r, k2r * k2r};
+    const hipStream_t st = (hipStream_t)stream;
+    const int tiles = tx * ty;
+    if (C == 1) {
+        hipLaunchKernelGGL(metrics_tile_kernel<1>, dim3(N * tiles), dim3(kMetThreads), 0, st, g);
+        hipLaunchKernelGGL(metrics_slab_sum_kernel<1>, dim3(N), dim3(kMetThreads), 0, st, (const double*)workspace, tiles, sums);
+    } else {
+        hipLaunchKernelGGL(metrics_tile_kernel<3>, dim3(N * tiles), dim3(kMetThreads), 0, st, g);
+        hipLaunchKernelGGL(metrics_slab_sum_kernel<3>, dim3(N), dim3(kMetThreads), 0, st, (const double*)workspace, tiles, sums);
     }
     HIP_TRY(hipGetLastError());
     return IRIS_OK;

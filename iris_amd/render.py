@@ -1,11 +1,12 @@
 """The render stage (reference: render.py:57-298) on MI355X: for every view of a split the path-traced image (`path_tracing`, the full integrator) and, in the
 same SPP // spp rounds, the scene intrinsics averaged over jittered primary rays (kd, a_prime, roughness, metallic, emission, surface light field); then the
-denoiser, the camera response model, the maps on disk and PSNR against the photograph.
+denoiser, the camera response model, the maps on disk and PSNR -- with --metrics psnr,ssim also SSIM -- against the photograph.
 
 Every ingredient is a HIP stage of this package: `utils.path_tracing.path_tracing`, `utils.render.render_intrinsics` (iris_render_primary + the material network +
-iris_render_intrinsics), `utils.denoise.Denoiser` (the a-trous filter that stands where OptixDenoiser stands), `model.crf.EmorCRF`, `utils.exr.write_exr`.
+iris_render_intrinsics), `utils.denoise.Denoiser` (the a-trous filter that stands where OptixDenoiser stands), `model.crf.EmorCRF`, `utils.exr.write_exr`, `utils.metrics.image_metrics` (SSIM on the
+device: skimage's defaults restated).
 
-Not here: --light_type area (AreaEmitter), SSIM (metrics.txt carries PSNR only), the magma colour maps (*_color.png), merge.png, crfs.png,
+Not here: --light_type area (AreaEmitter), the magma colour maps (*_color.png), merge.png, crfs.png,
 render_video.py / render_relight.py, and the trainers' validation(), which masks differently.
 """
 import math
@@ -32,15 +33,19 @@ def psnr(gt, img, data_range=1.0):
 
 @torch.no_grad()
 def render_view(scene, emitter_net, material_net, model_crf, rays, img_hw, SPP, spp, indir_depth=INDIR_DEPTH, exposure=1.0, gt=None, denoise=True, denoiser=None,
-                chunk=None):
+                chunk=None, metrics=("psnr",)):
     """One iteration of the reference's per-view loop (render.py:157-279).
 
     rays: (H*W, 12) float32 on the GPU -- origin, direction, dxdu, dydv as the datasets give them with ray_diff=True -- or the tuple of the four (H*W,3) tensors.
     SPP // spp rounds of `path_tracing(..., spp, indir_depth)` and `render_intrinsics(..., spp)`, every sum divided by the round count (:222,:241-271);
     L_full denoised (denoise=True, as the reference does; the guides are the pixel-centre primary hits) and mapped to LDR by model_crf(L, exposure) (None: no LDR);
-    gt: optional (H,W,3) / (H*W,3) LDR photograph in [0,1] -> 'psnr' (data_range 1).
-    Returns {'rgb_full' (H,W,3) HDR, 'rgb_ldr' (H,W,3) or None, 'kd', 'a_prime', 'emission', 'slf' (H,W,3), 'roughness', 'metallic' (H,W), 'psnr' or None, 'rounds'},
-    device tensors."""
+    gt: optional (H,W,3) / (H*W,3) LDR photograph in [0,1] -> 'psnr' (data_range 1) and, with "ssim" in `metrics`, 'ssim' (render.py:238: skimage's defaults at
+    data_range 1, evaluated on the device by utils.metrics.image_metrics).
+    Returns {'rgb_full' (H,W,3) HDR, 'rgb_ldr' (H,W,3) or None, 'kd', 'a_prime', 'emission', 'slf' (H,W,3), 'roughness', 'metallic' (H,W), 'psnr' or None,
+    'ssim' or None, 'rounds'}, device tensors; psnr and ssim Python floats."""
+    unknown = set(metrics) - {"psnr", "ssim"}
+    if unknown:
+        raise L.IrisError(f"render_view: unknown metrics {sorted(unknown)} (psnr, ssim)")
     H, W = int(img_hw[0]), int(img_hw[1])
     if isinstance(rays, (tuple, list)):
         rays_x, rays_d, dxdu, dydv = rays
@@ -73,10 +78,14 @@ def render_view(scene, emitter_net, material_net, model_crf, rays, img_hw, SPP, 
         L_full = denoiser(L_full.reshape(H, W, 3)).reshape(B, 3)
     out["rgb_full"] = L_full.reshape(H, W, 3)
     out["rgb_ldr"] = None if model_crf is None else model_crf(L_full.contiguous(), exposure).detach().reshape(H, W, 3)
-    out["psnr"] = None
+    out["psnr"] = out["ssim"] = None
     if gt is not None and out["rgb_ldr"] is not None:
         g = gt.detach().cpu().numpy() if torch.is_tensor(gt) else np.asarray(gt)
         out["psnr"] = psnr(g.reshape(H, W, 3), out["rgb_ldr"].cpu().numpy(), 1.0)
+        if "ssim" in metrics:
+            from .utils.metrics import ssim
+            g_dev = torch.as_tensor(np.ascontiguousarray(g, dtype=np.float32).reshape(H, W, 3)).to(dev)
+            out["ssim"] = ssim(g_dev, out["rgb_ldr"].contiguous(), 1.0)
     out["rounds"] = rounds
     return out
 
@@ -130,8 +139,19 @@ def write_view(output_path, split, i, out, compression="zip"):
     return files
 
 
-def write_metrics(path, psnr_list):
-    """rgb/metrics.txt (render.py:283-290) with the PSNR column only; views without a photograph are left out of the list and of the mean"""
+def write_metrics(path, psnr_list, ssim_list=None):
+    """rgb/metrics.txt (render.py:283-290); views without a photograph are left out of the lists and of the means.  ssim_list (the same views, in the same order)
+    None: the PSNR column only; else the reference's three columns Name, PSNR, SSIM."""
+    mean = lambda l: float(np.mean([v for _, v in l])) if l else float("nan")
+    if ssim_list is not None:
+        if [i for i, _ in ssim_list] != [i for i, _ in psnr_list]:
+            raise L.IrisError("write_metrics: the PSNR and SSIM lists name different views")
+        with open(path, "w") as fh:
+            fh.write("Name, PSNR, SSIM\n")
+            for (i, p), (_, s) in zip(psnr_list, ssim_list):
+                fh.write("{:0>5d}, {:.5f}, {:.5f}\n".format(i, p, s))
+            fh.write("{:<5}, {:.5f}, {:.5f}\n".format("mean", mean(psnr_list), mean(ssim_list)))
+        return
     with open(path, "w") as fh:
         fh.write("Name, PSNR\n")
         for i, p in psnr_list:
@@ -170,6 +190,8 @@ def build_parser():
     parser.add_argument("--emor_path", type=str, default=None, help="the EMoR basis file (default: crf/emor.txt under the working directory, as the reference)")
     parser.add_argument("--denoise", type=str, default="atrous", choices=["atrous", "none"])
     parser.add_argument("--compression", type=str, default="zip", choices=["none", "zips", "zip"])
+    parser.add_argument("--metrics", type=str, default="psnr", choices=["psnr", "psnr,ssim"], metavar="psnr | psnr,ssim", help="columns of rgb/metrics.txt: psnr (default), or psnr,ssim -- the "
+                        "reference's Name, PSNR, SSIM file, SSIM evaluated on the device")
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--max_views", type=int, default=None)
     return parser
@@ -276,21 +298,26 @@ def main(argv=None):
     if args.denoise == "atrous":
         from .utils.denoise import Denoiser
         denoiser = Denoiser(img_hw[::-1], device)
-    psnr_list = []
+    metrics = tuple(args.metrics.split(","))
+    psnr_list, ssim_list = [], []
     t0 = time.time()
     for i, view in enumerate(views):
         torch.manual_seed(args.seed * 1000003 + i); torch.cuda.manual_seed(args.seed * 1000003 + i)
         rays = _view_rays(view, img_hw, device)
         gt = _read_image(view["image"], img_hw) if view.get("image") else None
         out = render_view(scene, emitter_net, material_net, model_crf, rays, img_hw, args.SPP, args.spp, args.indir_depth, exposure=float(view.get("exposure", 1.0)),
-                          gt=gt, denoise=denoiser is not None, denoiser=denoiser)
+                          gt=gt, denoise=denoiser is not None, denoiser=denoiser, metrics=metrics)
         write_view(args.output_path, args.split, i, out, args.compression)
         if out["psnr"] is not None:
             psnr_list.append((i, out["psnr"]))
+        if out["ssim"] is not None:
+            ssim_list.append((i, out["ssim"]))
     if psnr_list:
         print("Mean PSNR: {:.5f}".format(float(np.mean([p for _, p in psnr_list]))))
+    if ssim_list:
+        print("Mean SSIM: {:.5f}".format(float(np.mean([s for _, s in ssim_list]))))
     os.makedirs(os.path.join(args.output_path, args.split, "rgb"), exist_ok=True)
-    write_metrics(os.path.join(args.output_path, args.split, "rgb", "metrics.txt"), psnr_list)
+    write_metrics(os.path.join(args.output_path, args.split, "rgb", "metrics.txt"), psnr_list, ssim_list if "ssim" in metrics else None)
     torch.cuda.synchronize()
     print("[render] {} views: {:.2f} s".format(len(views), time.time() - t0))
 
