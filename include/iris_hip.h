@@ -116,7 +116,8 @@ IRIS_API int iris_sample_specular_v(const float *u2, const float *wo, const floa
 /* ---- a5: VoxelSLF.spatial_idx/forward (model/slf.py:41-70), SLFEmitter.eval_emitter (model/emitter.py:180-221) */
 IRIS_API int iris_slf_lookup(const iris_slf *, const float *x, int64_t B, int64_t *idx /*nullable*/, float *rgb /*nullable*/,
                     iris_stream_t);
-/* roughness: NULL <=> the reference's roughness=None; otherwise (B) f32. */
+/* roughness: NULL <=> the reference's roughness=None; otherwise (B) f32.  The iris_slf may be NULL when the cache cannot be reached: roughness NULL, or
+ * trace_roughness = +inf (AreaEmitter, model/emitter.py:69-98, has no cache). */
 IRIS_API int iris_eval_emitter(const iris_emitter *, const iris_slf *, const float *position, const int64_t *triangle_idx,
                       const float *roughness, float trace_roughness, int64_t B, float *Le, float *emit_pdf,
                       uint8_t *valid_next, iris_stream_t);
@@ -236,7 +237,8 @@ IRIS_API int iris_pt_bounce(const iris_scene *, const iris_emitter *, const floa
 /* :394-404  eval_emitter(..., mat_next.roughness, 0.0) + geometry term + MIS -> term2 = coef2 * radiance[e2] + const2.
  * roughness_next may be NULL: "every roughness exceeds trace_roughness" -- the only use of mat_next in the reference's path_tracing_single is the test
  * roughness > trace_roughness = 0.0 (model/emitter.py:209), and NGPBRDF's roughness is sigmoid * 0.98 + 0.02 >= 0.02 (model/brdf.py:258): a caller that knows its
- * material network's lower bound skips the second network evaluation (same outputs, bit for bit). */
+ * material network's lower bound skips the second network evaluation (same outputs, bit for bit).  The iris_slf may be NULL when roughness_next is given and
+ * trace_roughness = +inf: no roughness exceeds it, the cache is never read. */
 IRIS_API int iris_pt_brdf_finish(const iris_emitter *, const iris_slf *, const float *pos, const float *pos_next, const float *nrm_next,
                         const float *wi, const int64_t *tri_next, const float *roughness_next, const float *pdf, const float *weight,
                         int64_t N, float *coef2, float *const2, int32_t *e2, uint8_t *valid_next /*nullable*/, float trace_roughness,
@@ -254,6 +256,37 @@ IRIS_API uint64_t iris_pt_compact_workspace_bytes(int64_t N);
 IRIS_API int iris_pt_compact(const uint8_t *keep, int64_t N, int n3, const float *const *src3, float *const *dst3, uint32_t negate3,
                     int n1, const float *const *src1, float *const *dst1, int ni, const int32_t *const *srci, int32_t *const *dsti,
                     int32_t *count, void *workspace, uint64_t workspace_bytes, iris_stream_t);
+
+/* ---- the relighting stage (render_relight.py; iris_amd/csrc/iris_relight.h) -------------------------------------- */
+/* Surface classes of the composed mesh (utils/lights.py compose): surf (n_surf) int32 per triangle -- 0 = network (shaded by the material network), -1 = absorber
+ * (a lamp switched off: a path that hits it ends and adds nothing), g > 0 = constant material, row g - 1 of cmat (n_cmat,5): albedo rgb, roughness, metallic.
+ * n_surf = 0: every triangle is class 0.
+ * iris_relight_surface: for the hits tri (N) (-1 = miss: left alone) a constant-material hit overwrites its albedo (N,3) / roughness (N) / metallic (N) row in place;
+ * valid (N, nullable) &= surf >= 0.  albedo NULL (then roughness and metallic are not read either): only valid is updated. */
+IRIS_API int iris_relight_surface(const int32_t *surf, int64_t n_surf, const float *cmat, int n_cmat, const int64_t *tri, int64_t N, float *albedo,
+                         float *roughness, float *metallic, uint8_t *valid, iris_stream_t);
+/* Next-event estimation for spot lights (delta lights: no MIS).  spots (n_spots,10): origin xyz, unit axis xyz, cutoff, beam (radians), cos(cutoff), cos(beam).
+ * Per path: j = min(floor(pick * n_spots), n_spots - 1); wi = normalize(o_j - x), d = |o_j - x|; c = dot(-wi, axis_j); falloff = 1 (c >= cos beam),
+ * (cutoff - acos c) / (cutoff - beam) (cos cutoff < c < cos beam), 0 (c <= cos cutoff) -- Mitsuba 3's `spot` plug-in as documented, unpinned; the shadow ray starts at
+ * x + RayEpsilon wi and the spot is occluded iff its closest hit lies nearer than (d - RayEpsilon)(1 - 1e-4);
+ * coef (N,3) = n_spots * falloff / max(d^2, 1e-12) * eval_brdf(wi, wo, n, material).brdf (which carries NoL), 0 when occluded; e (N) = j when lit, else -1.
+ * The contribution of the path is throughput * coef * spot_intensity[e]. */
+IRIS_API int iris_pt_nee_spot(const iris_scene *, const float *pos, const float *nrm, const float *wo, const float *albedo, const float *roughness,
+                     const float *metallic, const float *pick, const float *spots, int n_spots, int64_t N, float *coef, int32_t *e, iris_stream_t);
+/* Everything of a relit bounce after the material network, ONE launch.  Per path i: (1) the surface class of tri_next[i], the constant-material override of the
+ * row i of albedo_next / roughness_next / metallic_next (the next bounce's material); (2) iris_pt_brdf_finish's arithmetic without the radiance cache -- emitter
+ * ordinal e2, emit_pdf, geometry term, power-2 MIS weight w_mis; (3) in iris_pt_apply's order and arithmetic, each product NaN -> 0:
+ *   L[rows[i]] += t * (coef1 * radiance[e1]);  += t * (coef_spot * spot_intensity[e_spot]) (e_spot given);  += t * ((weight * w_mis) * radiance[e2]);  t *= weight
+ * with t = throughput[i]; (4) valid_next[i] = the hit is a surface that is neither an emitter nor an absorber.  radiance (K,3) as iris_pt_apply takes it.
+ * e1 / coef1 and e_spot / coef_spot / spot_intensity are nullable pairs; rows nullable (identity).  rows must be unique: no atomics.
+ * CONTRACT: with n_surf = 0 and no spots the L, throughput and valid_next written are the bits of iris_pt_apply(e1) -> iris_pt_brdf_finish(trace_roughness = +inf)
+ * -> iris_pt_apply(e2, const2, weight) on the same inputs with finite weights. */
+IRIS_API int iris_relight_shade(const iris_emitter *, const int32_t *surf, int64_t n_surf, const float *cmat, int n_cmat, const float *pos,
+                       const float *pos_next, const float *nrm_next, const float *wi, const int64_t *tri_next, const float *pdf, const float *weight,
+                       float *albedo_next, float *roughness_next, float *metallic_next, const float *radiance, const int32_t *e1, const float *coef1,
+                       const float *spot_intensity, const int32_t *e_spot, const float *coef_spot, float *L, const int32_t *rows, float *throughput,
+                       uint8_t *valid_next, int64_t N, float g_eps, iris_stream_t);
+
 /* :406  L (B,3) = mean over spp; path_of (B*spp) maps a path to its row in the compacted stage arrays (or -1).
  * radiance: the (n_rad,3) parameter tensor itself (model/emitter.py:268). */
 IRIS_API int iris_pt_accumulate_fwd(const float *radiance, const int32_t *e0, const int32_t *path_of, const int32_t *e1, const float *coef1,

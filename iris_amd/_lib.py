@@ -83,6 +83,9 @@ PROTOTYPES = {
     "iris_pt_bounce": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P],
     "iris_pt_compact_workspace_bytes": [_I64],
     "iris_pt_compact": [_P, _I64, _I32, _P, _P, C.c_uint32, _I32, _P, _P, _I32, _P, _P, _P, _P, C.c_uint64, _P],
+    "iris_relight_surface": [_P, _I64, _P, _I32, _P, _I64, _P, _P, _P, _P, _P],
+    "iris_pt_nee_spot": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I64, _P, _P, _P],
+    "iris_relight_shade": [_P, _P, _I64, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _F, _P],
     "iris_pt_accumulate_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P],
     "iris_pt_accumulate_bwd": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P],
     "iris_pt_step_accumulate_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P],

@@ -19,6 +19,7 @@
 #include "iris_trace.h"
 #include "iris_bake.h"
 #include "iris_pt.h"
+#include "iris_relight.h"
 #include "iris_cache.h"
 #include "iris_denoise.h"
 #include "iris_metrics.h"
@@ -716,9 +717,11 @@ __global__ void eval_emitter_kernel(EmitDev e, SlfDev s, const float* __restrict
 extern "C" IRIS_API int iris_eval_emitter(const iris_emitter* e, const iris_slf* s, const float* position, const int64_t* triangle_idx,
                                  const float* roughness, float trace_roughness, int64_t B, float* Le, float* emit_pdf,
                                  uint8_t* valid_next, iris_stream_t stream) {
-    if (!e || !s || B < 0 || (B > 0 && (!position || !triangle_idx || !Le))) return fail(IRIS_ERR_ARG, "iris_eval_emitter: bad arguments");
+    // (no radiance cache is consulted without a roughness array, or with trace_roughness = +inf: the cache may be NULL then -- AreaEmitter has none)
+    const bool slf_unreachable = !roughness || (std::isinf(trace_roughness) && trace_roughness > 0.f);
+    if (!e || (!s && !slf_unreachable) || B < 0 || (B > 0 && (!position || !triangle_idx || !Le))) return fail(IRIS_ERR_ARG, "iris_eval_emitter: bad arguments");
     if (B == 0) return IRIS_OK;
-    return launch1d(eval_emitter_kernel, B, 8192, stream, e->dev, s->dev, position,
+    return launch1d(eval_emitter_kernel, B, 8192, stream, e->dev, s ? s->dev : SlfDev{}, position,
                        triangle_idx, roughness, trace_roughness, B, Le, emit_pdf, valid_next);
 }
 
@@ -1533,11 +1536,12 @@ extern "C" IRIS_API int iris_pt_brdf_finish(const iris_emitter* e, const iris_sl
                                    const float* wi, const int64_t* tri_next, const float* roughness_next, const float* pdf, const float* weight,
                                    int64_t N, float* coef2, float* const2, int32_t* e2, uint8_t* valid_next, float trace_roughness, float g_eps,
                                    iris_stream_t stream) {
-    if (!e || !slf || N < 0 || (N > 0 && (!pos || !pos_next || !nrm_next || !wi || !tri_next || !pdf || !weight || !coef2 || !const2 || !e2)))      // (roughness_next may be NULL: see iris_hip.h)
+    const bool slf_unreachable = roughness_next && std::isinf(trace_roughness) && trace_roughness > 0.f;      // (no roughness exceeds +inf: the cache may be NULL)
+    if (!e || (!slf && !slf_unreachable) || N < 0 || (N > 0 && (!pos || !pos_next || !nrm_next || !wi || !tri_next || !pdf || !weight || !coef2 || !const2 || !e2)))      // (roughness_next may be NULL: see iris_hip.h)
         return fail(IRIS_ERR_ARG, "iris_pt_brdf_finish: bad arguments");
     if (N == 0) return IRIS_OK;
     PtArgs a{};
-    a.em = e->dev; a.slf = slf->dev; a.N = N;
+    a.em = e->dev; a.slf = slf ? slf->dev : SlfDev{}; a.N = N;
     a.pos = pos; a.pos_n_in = pos_next; a.nrm_n_in = nrm_next; a.wi_in = wi; a.tri_n_in = tri_next; a.rough_next = roughness_next; a.pdf_in = pdf; a.w_in = weight;
     a.coef2 = coef2; a.const2 = const2; a.e2 = e2; a.valid_next_hit = valid_next; a.trace_rough = trace_roughness; a.g_eps = g_eps;
     return launch1d(pt_brdf_finish_kernel, N, 8192, stream, a);
@@ -1608,6 +1612,57 @@ extern "C" IRIS_API int iris_pt_compact(const uint8_t* keep, int64_t N, int n3, 
     hipLaunchKernelGGL(pt_compact_move_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
+}
+
+// ======================================================================================================
+// the relighting stage (iris_relight.h): surface classes, spot-light next-event estimation, the fused end of a bounce
+// ======================================================================================================
+static bool surf_args(const int32_t* surf, int64_t n_surf, const float* cmat, int n_cmat, SurfDev& sf) {
+    if (n_surf < 0 || n_cmat < 0 || (n_surf > 0 && !surf) || (n_cmat > 0 && !cmat)) return false;
+    sf.surf = n_surf > 0 ? surf : nullptr; sf.cmat = cmat; sf.nf = n_surf; sf.n_cmat = n_cmat;
+    return true;
+}
+extern "C" IRIS_API int iris_relight_surface(const int32_t* surf, int64_t n_surf, const float* cmat, int n_cmat, const int64_t* tri, int64_t N, float* albedo,
+                                    float* roughness, float* metallic, uint8_t* valid, iris_stream_t stream) {
+    SurfDev sf{};
+    if (!surf_args(surf, n_surf, cmat, n_cmat, sf) || N < 0 || (N > 0 && (!tri || (albedo && (!roughness || !metallic)) || (!albedo && !valid))))
+        return fail(IRIS_ERR_ARG, "iris_relight_surface: bad arguments");
+    if (N == 0) return IRIS_OK;
+    return launch1d(relight_surface_kernel, N, 8192, stream, sf, tri, N, albedo, roughness, metallic, valid);
+}
+extern "C" IRIS_API int iris_pt_nee_spot(const iris_scene* sc, const float* pos, const float* nrm, const float* wo, const float* albedo, const float* roughness,
+                                const float* metallic, const float* pick, const float* spots, int n_spots, int64_t N, float* coef, int32_t* e,
+                                iris_stream_t stream) {
+    if (!sc || n_spots < 1 || !spots) return fail(IRIS_ERR_ARG, "iris_pt_nee_spot: a scene and at least one spot are required");
+    if (N < 0 || (N > 0 && (!pos || !nrm || !wo || !albedo || !roughness || !metallic || !pick || !coef || !e))) return fail(IRIS_ERR_ARG, "iris_pt_nee_spot: bad arguments");
+    if (N == 0) return IRIS_OK;
+    SpotArgs a{};
+    a.sc = sc->dev; a.N = N; a.S = n_spots;
+    a.pos = pos; a.nrm = nrm; a.wo = wo; a.albedo = albedo; a.rough = roughness; a.metal = metallic; a.pick = pick; a.spots = spots; a.coef = coef; a.e = e;
+    with_trace(a.sc, N, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pt_nee_spot_kernel<T::layout, T::joint>), dim3(grid_for(N, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, a);
+    });
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_relight_shade(const iris_emitter* em, const int32_t* surf, int64_t n_surf, const float* cmat, int n_cmat, const float* pos,
+                                  const float* pos_next, const float* nrm_next, const float* wi, const int64_t* tri_next, const float* pdf, const float* weight,
+                                  float* albedo_next, float* roughness_next, float* metallic_next, const float* radiance, const int32_t* e1, const float* coef1,
+                                  const float* spot_intensity, const int32_t* e_spot, const float* coef_spot, float* L, const int32_t* rows, float* throughput,
+                                  uint8_t* valid_next, int64_t N, float g_eps, iris_stream_t stream) {
+    RelightShadeArgs a{};
+    if (!em || !surf_args(surf, n_surf, cmat, n_cmat, a.sf) || (n_surf > 0 && n_surf != em->dev.nf) || N < 0 ||
+        (N > 0 && (!pos || !pos_next || !nrm_next || !wi || !tri_next || !pdf || !weight || !albedo_next || !roughness_next || !metallic_next || !L || !throughput ||
+                   !valid_next || (e1 && (!radiance || !coef1)) || (em->k > 0 && !radiance) || (e_spot && (!spot_intensity || !coef_spot)))))
+        return fail(IRIS_ERR_ARG, "iris_relight_shade: bad arguments");
+    if (N == 0) return IRIS_OK;
+    a.em = em->dev; a.N = N;
+    a.pos = pos; a.pos_next = pos_next; a.nrm_next = nrm_next; a.wi = wi; a.pdf = pdf; a.w = weight; a.tri_next = tri_next;
+    a.albedo_next = albedo_next; a.rough_next = roughness_next; a.metal_next = metallic_next;
+    a.radiance = radiance; a.e1 = e1; a.coef1 = coef1; a.spot_intensity = spot_intensity; a.es = e_spot; a.coef_s = coef_spot;
+    a.L = L; a.rows = rows; a.throughput = throughput; a.valid_next = valid_next; a.g_eps = g_eps;
+    return launch1d(relight_shade_kernel, N, 8192, stream, a);
 }
 
 // ======================================================================================================

@@ -1,4 +1,4 @@
-"""SLFEmitter: triangle emitters + diffuse radiance cache (reference: model/emitter.py:134-221)."""
+"""AreaEmitter: triangle emitters (reference: model/emitter.py:15-131); SLFEmitter: triangle emitters + diffuse radiance cache (:134-221)."""
 import ctypes as C
 
 import numpy as np
@@ -10,16 +10,11 @@ from .. import _lib as L
 from .slf import VoxelSLF
 
 
-class SLFEmitter(nn.Module):
-    """Loads the reference's ``emitter.pth`` / ``vslf.npz`` files (extract_emitter_ldr.py:109-115, slf_bake.py:140-145)."""
+class _TriangleEmitter(nn.Module):
+    """The emitter tables of an ``emitter.pth`` file and their device-side copy: what AreaEmitter and SLFEmitter share."""
 
-    def __init__(self, emitter_path, slf_path):
-        super().__init__()
-        state_dict = torch.load(slf_path, map_location="cpu")
-        self.slf = VoxelSLF(state_dict["mask"], state_dict["voxel_min"], state_dict["voxel_max"])
-        self.slf.load_state_dict(state_dict["weight"])
-
-        weight = torch.load(emitter_path, map_location="cpu")
+    def _load_tables(self, emitter_path):
+        weight = emitter_path if isinstance(emitter_path, dict) else torch.load(emitter_path, map_location="cpu")
         is_emitter = weight["is_emitter"]
         self.register_buffer("is_emitter", is_emitter)
         self.register_buffer("emitter_vertices", weight["emitter_vertices"])
@@ -70,6 +65,66 @@ class SLFEmitter(nn.Module):
         """`radiance` as a detached, contiguous float32 tensor on `device` (the files are loaded with map_location='cpu')."""
         return self.radiance.detach().to(device=device, dtype=torch.float32).contiguous()
 
+    def sample_emitter(self, sample1, sample2, position):
+        """importance sampling emitters (model/emitter.py:100-131, :224-255): uniform emitter pick through the cdf, uniform point on
+        the triangle.  Returns wi Bx3, pdf Bx1 (area measure), triangle_idx B."""
+        sample1 = L.require_gpu(sample1, torch.float32, "sample1").reshape(-1)
+        sample2 = L.require_gpu(sample2, torch.float32, "sample2").reshape(-1, 2)
+        position = L.require_gpu(position, torch.float32, "position").reshape(-1, 3)
+        B = position.shape[0]
+        wi = torch.empty(B, 3, device=position.device, dtype=torch.float32)
+        pdf = torch.empty(B, 1, device=position.device, dtype=torch.float32)
+        tri = torch.empty(B, device=position.device, dtype=torch.int64)
+        with torch.cuda.device(position.device):
+            L.check(L.lib().iris_sample_emitter(self.handle(position.device), L.ptr(sample1), L.ptr(sample2), L.ptr(position), B, L.ptr(wi), L.ptr(pdf),
+                                                L.ptr(tri), L.stream()))
+        return wi, pdf, tri
+
+
+class AreaEmitter(_TriangleEmitter):
+    """Triangle-mesh emitters without a radiance cache (model/emitter.py:15-131): the emitter of the relighting stage.  `emitter_path`: an ``emitter_relight.pth``
+    file (render_video.py:143) or the state dict itself (utils.lights.compose returns one).  A table without any area light (K = 0) is legal: nothing is sampled
+    from it (sample_emitter raises)."""
+
+    def __init__(self, emitter_path):
+        super().__init__()
+        self._load_tables(emitter_path)
+
+    @property
+    def n_emitters(self):
+        return int(self.emitter_area.shape[0])
+
+    def forward(self, triangle_idx):
+        """emitter radiance of the triangles (model/emitter.py:53-67; the reference reads an undefined `position` there: this is its evident meaning, on
+        triangle_idx alone)"""
+        triangle_idx = L.require_gpu(triangle_idx, torch.int64, "triangle_idx").reshape(-1)
+        return self.eval_emitter(torch.zeros(triangle_idx.shape[0], 3, device=triangle_idx.device), None, triangle_idx)[0]
+
+    def eval_emitter(self, position, light_dir, triangle_idx, *args):
+        """surface emission and pdf (model/emitter.py:69-98).  Returns Le Bx3, emit_pdf Bx1, valid_next B (bool): a surface that is not an emitter.
+        ``light_dir`` and further arguments (SLFEmitter's roughness) are unused, as in the reference."""
+        position = L.require_gpu(position, torch.float32, "position").reshape(-1, 3)
+        triangle_idx = L.require_gpu(triangle_idx, torch.int64, "triangle_idx").reshape(-1)
+        B = position.shape[0]
+        Le = torch.empty(B, 3, device=position.device, dtype=torch.float32)
+        pdf = torch.empty(B, 1, device=position.device, dtype=torch.float32)
+        vn = torch.empty(B, device=position.device, dtype=torch.bool)
+        with torch.cuda.device(position.device):
+            L.check(L.lib().iris_eval_emitter(self.handle(position.device), None, L.ptr(position), L.ptr(triangle_idx), None, 0.0, B, L.ptr(Le), L.ptr(pdf),
+                                              L.ptr(vn), L.stream()))
+        return Le, pdf, vn
+
+
+class SLFEmitter(_TriangleEmitter):
+    """Loads the reference's ``emitter.pth`` / ``vslf.npz`` files (extract_emitter_ldr.py:109-115, slf_bake.py:140-145)."""
+
+    def __init__(self, emitter_path, slf_path):
+        super().__init__()
+        state_dict = torch.load(slf_path, map_location="cpu")
+        self.slf = VoxelSLF(state_dict["mask"], state_dict["voxel_min"], state_dict["voxel_max"])
+        self.slf.load_state_dict(state_dict["weight"])
+        self._load_tables(emitter_path)
+
     def forward(self, position):
         """surface light field from queried location (model/emitter.py:175-178)"""
         return self.slf(position)["rgb"]
@@ -90,21 +145,6 @@ class SLFEmitter(nn.Module):
             L.check(L.lib().iris_eval_emitter(self.handle(position.device), self.slf.handle(position.device), L.ptr(position),
                                               L.ptr(triangle_idx), L.ptr(r), float(trace_roughness), B, L.ptr(Le), L.ptr(pdf), L.ptr(vn), L.stream()))
         return Le, pdf, vn
-
-    def sample_emitter(self, sample1, sample2, position):
-        """importance sampling emitters (model/emitter.py:224-255): uniform emitter pick through the cdf, uniform point on
-        the triangle.  Returns wi Bx3, pdf Bx1 (area measure), triangle_idx B."""
-        sample1 = L.require_gpu(sample1, torch.float32, "sample1").reshape(-1)
-        sample2 = L.require_gpu(sample2, torch.float32, "sample2").reshape(-1, 2)
-        position = L.require_gpu(position, torch.float32, "position").reshape(-1, 3)
-        B = position.shape[0]
-        wi = torch.empty(B, 3, device=position.device, dtype=torch.float32)
-        pdf = torch.empty(B, 1, device=position.device, dtype=torch.float32)
-        tri = torch.empty(B, device=position.device, dtype=torch.int64)
-        with torch.cuda.device(position.device):
-            L.check(L.lib().iris_sample_emitter(self.handle(position.device), L.ptr(sample1), L.ptr(sample2), L.ptr(position), B, L.ptr(wi), L.ptr(pdf),
-                                                L.ptr(tri), L.stream()))
-        return wi, pdf, tri
 
 
 class SLFEmitterLearn(SLFEmitter):

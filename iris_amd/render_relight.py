@@ -1,0 +1,204 @@
+"""The relighting stage (reference: render_relight.py) on MI355X: the room's recovered materials under NEW lights.
+
+    python -m iris_amd.render_relight --experiment_name EXP --ckpt last_1.ckpt --dataset synthetic DATA/kitchen --emitter_path checkpoints/EXP/bake
+        --light_cfg configs/fipt/kitchen/relight_0.yaml --output_path OUT --SPP 256 --spp 16
+
+The reference loads the light configuration into a Mitsuba scene and lets Mitsuba's `path` integrator call the material network per bounce.  Here the
+configuration is parsed by utils.lights, the room mesh is composed with the inserted shapes and lights, and `utils.relight.path_tracing_relit` traces it with the
+HIP stages of this package.  Per view: SPP // spp rounds at (h a, w a) pixels (a = --anti_aliasing), NaN -> 0, the mean, the a-trous denoiser guided by the
+composed scene's primary hits, the camera response model at exposure 1, the a x a box average (cv2.INTER_AREA for an integer factor), and
+{i:05d}_rgb.png (when PIL imports) + {i:05d}_rgb.exr (an addition) under --output_path.
+
+Not here: --mode traj from the dataset's own trajectory file (utils/cameras.py does not load render_traj_c2w: pass --cameras), relight.mp4, inserted obj / ply
+meshes, textures, environment maps, point lights.
+"""
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .utils import lights as LT
+from .utils.path_tracing import load_mesh, ray_intersect
+from .utils.relight import RelitScene, path_tracing_relit
+
+INDIR_DEPTH = 5
+
+
+def scaled_view(view, a):
+    """the view with its intrinsics scaled by the integer anti-aliasing factor `a` (render_relight.py:219-233)"""
+    v = dict(view)
+    if v["kind"] == "synthetic":
+        v["focal"] = float(v["focal"]) * a
+    else:
+        K = np.asarray(v["K"], np.float32).copy()
+        K[:2, :] *= a
+        v["K"] = K
+    return v
+
+
+@torch.no_grad()
+def relight_view(relit, material_net, model_crf, rays, img_hw, SPP, spp, indir_depth=INDIR_DEPTH, anti_aliasing=1, exposure=1.0, denoise=True, denoiser=None):
+    """One iteration of the reference's per-view loop (render_relight.py:265-298).
+
+    relit: the RelitScene of this view; rays: the four (H a * W a, 3) tensors (origin, direction, dxdu, dydv) of the view at the anti-aliased size, or one
+    (.., 12) tensor; img_hw: the OUTPUT size (h, w).  SPP // spp rounds of path_tracing_relit(..., spp, max_depth = indir_depth + 2), NaN -> 0 per round, the mean,
+    the denoiser (guides: the composed scene's pixel-centre primary hits), model_crf(L, exposure) (None: no LDR image), the a x a box average.
+    Returns {'rgb_full' (h a, w a, 3) HDR (denoised), 'rgb_ldr' (h, w, 3) or None, 'rounds'}, device tensors."""
+    a = int(anti_aliasing)
+    if a < 1:
+        raise L.IrisError(f"relight_view: anti_aliasing = {anti_aliasing} must be a positive integer")
+    h, w = int(img_hw[0]), int(img_hw[1])
+    H, W = h * a, w * a
+    if isinstance(rays, (tuple, list)):
+        rays_x, rays_d, dxdu, dydv = rays
+    else:
+        rays = L.require_gpu(rays, torch.float32, "rays").reshape(-1, 12)
+        rays_x, rays_d, dxdu, dydv = (rays[:, 3 * k:3 * k + 3].contiguous() for k in range(4))
+    rays_x = L.require_gpu(rays_x, torch.float32, "rays_x").reshape(-1, 3)
+    B, dev = rays_x.shape[0], rays_x.device
+    if B != H * W:
+        raise L.IrisError(f"relight_view: {B} rays for an image of {H} x {W} ({h} x {w} at anti_aliasing {a})")
+    rounds = int(SPP) // int(spp)
+    if rounds < 1:
+        raise L.IrisError(f"relight_view: SPP ({SPP}) // spp ({spp}) is zero: nothing would be rendered")
+    img = torch.zeros(B, 3, device=dev)
+    for _ in range(rounds):
+        img_ = path_tracing_relit(relit, material_net, rays_x, rays_d, dxdu, dydv, spp, int(indir_depth) + 2)
+        img_[img_.isnan()] = 0                                           # render_relight.py:283
+        img += img_
+    img = img / rounds
+    if denoise:
+        if denoiser is None:
+            from .utils.denoise import Denoiser
+            denoiser = Denoiser((W, H), dev)
+        pos, nrm, _, _, valid = ray_intersect(relit.scene, rays_x, torch.nn.functional.normalize(L.require_gpu(rays_d, torch.float32, "rays_d").reshape(-1, 3), dim=-1))
+        denoiser.set_guides(nrm, pos, valid)
+        img = denoiser(img.reshape(H, W, 3)).reshape(B, 3)
+    out = {"rgb_full": img.reshape(H, W, 3), "rgb_ldr": None, "rounds": rounds}
+    if model_crf is not None:
+        ldr = model_crf(img.contiguous(), exposure).detach().reshape(H, W, 3)
+        if a > 1:
+            ldr = torch.nn.functional.avg_pool2d(ldr.permute(2, 0, 1)[None], a)[0].permute(1, 2, 0).contiguous()
+        out["rgb_ldr"] = ldr
+    return out
+
+
+def save_image(image, path):
+    """render_relight.py:43-55 save_image without the colour map: clip to [0,1], * 255, uint8, odd trailing row / column dropped.  Written only when PIL imports."""
+    try:
+        from PIL import Image
+    except ImportError:
+        return False
+    a = image.detach().cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
+    a = (np.clip(a, 0.0, 1.0) * 255).astype(np.uint8)
+    hh, ww = a.shape[:2]
+    Image.fromarray(a[:hh - hh % 2, :ww - ww % 2]).save(path)
+    return True
+
+
+def build_parser():
+    """The reference's render_relight.py arguments (render_relight.py:117-131 + configs/config.py); the trainers' options are accepted and ignored."""
+    import argparse
+    parser = argparse.ArgumentParser(description="python -m iris_amd.render_relight: the reference's render_relight.py on MI355X")
+    parser.add_argument("--experiment_name", type=str, required=True)
+    parser.add_argument("--mode", type=str, default="train_val", choices=["train_val", "traj"])
+    parser.add_argument("--log_path", type=str, default="./logs")
+    parser.add_argument("--checkpoint_path", type=str, default="./checkpoints")
+    parser.add_argument("--output_path", type=str, default="outputs/kitchen_output")
+    parser.add_argument("--device", type=int, default=0)
+    parser.add_argument("--split", type=str, default="val")
+    parser.add_argument("--ckpt", type=str, default="last.ckpt")
+    parser.add_argument("--anti_aliasing", type=int, default=1)
+    parser.add_argument("--light_cfg", type=str, required=True)
+    parser.add_argument("--dataset", type=str, nargs=2, default=["synthetic", "../data/indoor_synthetic/kitchen"], help="dataset type (synthetic | real | scannetpp) and its path")
+    parser.add_argument("--scene", type=str, default="")
+    parser.add_argument("--emitter_path", type=str, required=True, help="folder holding vslf.npz and emitter.pth (render_relight.py:184-198)")
+    parser.add_argument("--SPP", type=int, default=512)
+    parser.add_argument("--spp", type=int, default=8)
+    parser.add_argument("--indir_depth", type=int, default=INDIR_DEPTH)
+    parser.add_argument("--crf_basis", type=int, default=3)
+    parser.add_argument("--res_scale", type=float, default=1.0)
+    parser.add_argument("--ldr_img_dir", type=str, default=None)
+    for name, typ in (("batch_size", int), ("voxel_path", str), ("num_workers", int), ("dir_val", str), ("val_step", int), ("has_part", int), ("load_crf", int)):
+        parser.add_argument("--" + name, type=typ, default=None, help="(a trainer option of configs/config.py: accepted, unused)")
+    # additions (defaults reproduce the reference)
+    parser.add_argument("--material", type=str, default=None, help="pkg.module:factory returning material_net(position) -> {'albedo','roughness','metallic'} "
+                        "(default: the reference's NGPBRDF, loaded from the checkpoint's 'material.' entries)")
+    parser.add_argument("--cameras", type=str, default=None, help="generic camera JSON instead of the dataset's own camera files (needed for --mode traj)")
+    parser.add_argument("--emor_path", type=str, default=None, help="the EMoR basis file (default: crf/emor.txt under the working directory, as the reference)")
+    parser.add_argument("--denoise", type=str, default="atrous", choices=["atrous", "none"])
+    parser.add_argument("--compression", type=str, default="zip", choices=["none", "zips", "zip"])
+    parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--max_views", type=int, default=None)
+    parser.add_argument("--keep_lights", type=float, default=0.0, help="0: the room's own lamps are switched off (absorbers); s > 0: they stay, their radiance times s")
+    parser.add_argument("--sphere_subdiv", type=int, default=2, help="icosphere subdivisions of inserted spheres (2: 320 triangles)")
+    return parser
+
+
+def main(argv=None):
+    from .model.crf import EmorCRF
+    from .refine_shading import _load_material
+    from .render import _load_state, _view_rays, _views
+    from .utils.exr import write_exr
+    args = build_parser().parse_args(argv)
+    if args.mode == "traj" and not args.cameras:
+        raise L.IrisError("--mode traj: the dataset's render trajectory (render_traj_c2w) is not loaded by this package; pass the views with --cameras cameras.json")
+    if not torch.cuda.is_available():
+        raise L.IrisError("render_relight needs a HIP device; there is no CPU path")
+    torch.cuda.set_device(args.device)
+    device = torch.device("cuda", args.device)
+    print("==========================\nExp: {}\nMode: {}\nOutput: {}\nSplit: {}\n==========================".format(args.experiment_name, args.mode, args.output_path, args.split))
+    name, path = args.dataset
+    if name == "scannetpp":
+        mesh_path = os.path.join(path, "data", args.scene, "scans", "scene.ply")
+    else:
+        mesh_path = os.path.join(path, "scene.obj")
+        if not os.path.exists(mesh_path) and os.path.exists(os.path.join(path, "scene.ply")):
+            mesh_path = os.path.join(path, "scene.ply")
+    assert os.path.exists(mesh_path), "mesh not found: " + mesh_path
+    verts, faces = load_mesh(mesh_path)
+    emitter_state = torch.load(os.path.join(args.emitter_path, "emitter.pth"), map_location="cpu")
+    lights = LT.load_light_config(args.light_cfg)
+    img_hw, views = _views(args)
+    if args.max_views is not None:
+        views = views[:args.max_views]
+    ckpt = os.path.join(args.checkpoint_path, args.experiment_name, args.ckpt)
+    material_net = _load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), ckpt)
+    if isinstance(material_net, torch.nn.Module):
+        material_net.to(device)
+    crf_state = {k.replace("model_crf.", ""): v for k, v in _load_state(ckpt).items() if "model_crf." in k}
+    if args.emor_path is None and not os.path.isfile(os.path.join(os.getcwd(), "crf", "emor.txt")) and "f0" in crf_state and "basis" in crf_state:
+        model_crf = EmorCRF.from_arrays(crf_state["f0"][0], crf_state["basis"])
+    else:
+        model_crf = EmorCRF(args.crf_basis, emor_path=args.emor_path)
+    model_crf.load_state_dict(crf_state)
+    model_crf.to(device)
+    for mod in (material_net, model_crf):
+        if isinstance(mod, torch.nn.Module):
+            for p in mod.parameters():
+                p.requires_grad = False
+    a = int(args.anti_aliasing)
+    hw_aa = (img_hw[0] * a, img_hw[1] * a)
+    denoiser = None
+    if args.denoise == "atrous":
+        from .utils.denoise import Denoiser
+        denoiser = Denoiser(hw_aa[::-1], device)
+    os.makedirs(args.output_path, exist_ok=True)
+    relit, t0 = None, time.time()
+    for i, view in enumerate(views):
+        torch.manual_seed(args.seed * 1000003 + i); torch.cuda.manual_seed(args.seed * 1000003 + i)
+        if relit is None or lights.disco is not None:                   # the scene is recomposed per view only for the disco ball (timestep = i)
+            relit = RelitScene(LT.compose(verts, faces, emitter_state, lights.at(i), args.keep_lights, args.sphere_subdiv), device)
+        rays = _view_rays(scaled_view(view, a), hw_aa, device)
+        out = relight_view(relit, material_net, model_crf, rays, img_hw, args.SPP, args.spp, args.indir_depth, anti_aliasing=a, exposure=1.0,
+                           denoise=denoiser is not None, denoiser=denoiser)
+        save_image(out["rgb_ldr"], os.path.join(args.output_path, "{:0>5d}_rgb.png".format(i)))
+        write_exr(os.path.join(args.output_path, "{:0>5d}_rgb.exr".format(i)), out["rgb_full"].detach().cpu().numpy(), args.compression)
+    torch.cuda.synchronize()
+    print("[render_relight] {} views: {:.2f} s".format(len(views), time.time() - t0))
+
+
+if __name__ == "__main__":
+    main()
