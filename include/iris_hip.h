@@ -455,6 +455,27 @@ IRIS_API uint64_t iris_image_metrics_workspace_bytes(int32_t N, int32_t H, int32
 IRIS_API int iris_image_metrics(const float *a, const float *b, int32_t N, int32_t H, int32_t W, int32_t C, float data_range, double *sums,
                        float *ssim_map, void *workspace, uint64_t workspace_bytes, iris_stream_t);
 
+/* ---- texture export: UV rasteriser, per-texel resolve, quantisation (utils/export.py:77-135) ------------------- */
+/* The reference rasterises the UV triangles with nvdiffrast (third party, GL): parity is unpinned and the contract is this project's, exact in integers
+ * (iris_amd/csrc/iris_texture.h).  Texture of H rows x W columns, both in [1, 8192]; texel (r, c) has its centre at
+ * u = (c + .5) / W, v = (r + .5) / H, row 0 at v ~ 0.  vt (n_vt, 2) float32 UVs (finite, in [-1, 2]: the caller checks), ft (F, 3) int32 indices into vt;
+ * v (n_v, 3) float32 positions, f (F, 3) int32 indices into v.  UVs are snapped to 1 / 256 texel, coverage is decided by int64 edge functions with a
+ * top-left rule, the lowest face index wins where triangles overlap.  A triangle that names a vertex out of range covers nothing.
+ * iris_uv_raster: ids (H W) int32 receives the face index per texel, -1 where uncovered.  workspace: iris_uv_raster_workspace_bytes(F) bytes, 8-byte
+ *   aligned.  Integer atomicMin only: the result does not depend on scheduling.  Two memsets and two launches on the stream.
+ * iris_uv_resolve: for the texels [texel0, texel0 + n) of a texture rasterised into ids: bary (n, 2) float32 (weights of vertices 0 and 1; NULL: not
+ *   written) and xyz (n, 3) float32, the position interpolated in float32 as ((b0 v0) + (b1 v1)) + (b2 v2), b2 = 1 - b0 - b1.  Uncovered: zeros.
+ * iris_texture_quantize: albedo (n, 3), roughness (n), metallic (n) float32 of the same texel range -> bytes 3 texel0 .. 3 (texel0 + n) of the two uint8
+ *   RGB images of n_texels texels (albedo; roughness, metallic, 0): clamp to [0, 1] with NaN -> 0, times 255 in float32, truncated; 0 where ids < 0.
+ *   The images must be 4-byte aligned. */
+IRIS_API uint64_t iris_uv_raster_workspace_bytes(int64_t F);
+IRIS_API int iris_uv_raster(const float *vt, int64_t n_vt, const int32_t *ft, int64_t F, int32_t H, int32_t W, int32_t *ids, void *workspace,
+                   uint64_t workspace_bytes, iris_stream_t);
+IRIS_API int iris_uv_resolve(const float *vt, int64_t n_vt, const int32_t *ft, const float *v, int64_t n_v, const int32_t *f, int64_t F, int32_t H, int32_t W,
+                    const int32_t *ids, int64_t texel0, int64_t n, float *bary, float *xyz, iris_stream_t);
+IRIS_API int iris_texture_quantize(const float *albedo, const float *roughness, const float *metallic, const int32_t *ids, int64_t texel0, int64_t n,
+                          int64_t n_texels, uint8_t *albedo_img, uint8_t *rm_img, iris_stream_t);
+
 /* ---- OpenEXR ZIP / ZIPS writer, device half ------------------------------------------------------------- */
 /* Deflate of the scanline blocks of n_maps maps (utils/exr.py scanline_blocks_torch): full (n_maps, n_full, block_bytes) and tail (n_maps, tail_bytes)
  * hold the PREDICTED bytes (reordered, delta-coded) of every block, device uint8, contiguous.  records receives, map by map, every chunk record as the

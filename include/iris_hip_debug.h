@@ -52,6 +52,13 @@ IRIS_API int iris_debug_set(const char *key, long long value);
 /* NGPBRDF: the hash-grid encoding alone (tests compare it bit for bit with the restatement; the perceptron behind it only to a tolerance):
  * features of N <= 2^20 positions as the kernels hand them over, feat[level * N + i] = the level's two half features of point i (one uint32). */
 IRIS_API int iris_debug_ngp_encode(const iris_ngp *, const float *position, int64_t N, uint32_t *feat, iris_stream_t);
+/* iris_uv_raster plus `mode`: which of the rasteriser's two triangle classes a triangle goes through (iris_amd/csrc/iris_texture.h).  AUTO: by the texel
+ * count of its clipped bounding box, as iris_uv_raster; ALL_SMALL: every triangle is walked by one lane; ALL_LARGE: every triangle is queued and walked by
+ * waves in 64-texel row segments; a value >= 64: AUTO with that many texels as the class threshold (the measurement that picks the built-in constant,
+ * tools/bench_texture.py).  Every mode returns identical ids. */
+enum { IRIS_UV_RASTER_AUTO = 0, IRIS_UV_RASTER_ALL_SMALL = 1, IRIS_UV_RASTER_ALL_LARGE = 2 };
+IRIS_API int iris_debug_uv_raster(const float *vt, int64_t n_vt, const int32_t *ft, int64_t F, int32_t H, int32_t W, int32_t *ids, void *workspace,
+                         uint64_t workspace_bytes, int mode, iris_stream_t);
 /* The compiler flags this library was built with (iris_amd/csrc/Makefile embeds them): part of the stamp that ties a counter profile to a build. */
 IRIS_API const char *iris_debug_build_flags(void);
 /* sha256 (16 hex digits) over EVERY file this library was compiled from (kernels of all stages, host code, ABI headers), taken by the Makefile at build

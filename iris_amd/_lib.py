@@ -113,6 +113,11 @@ PROTOTYPES = {
     "iris_denoise": [_P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _F, _F, _F, _P, _U64, _P],
     "iris_image_metrics_workspace_bytes": [_I32, _I32, _I32, _I32],
     "iris_image_metrics": [_P, _P, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _U64, _P],
+    "iris_uv_raster_workspace_bytes": [_I64],
+    "iris_uv_raster": [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _U64, _P],
+    "iris_debug_uv_raster": [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _U64, _I32, _P],
+    "iris_uv_resolve": [_P, _I64, _P, _P, _I64, _P, _I64, _I32, _I32, _P, _I64, _I64, _P, _P, _P],
+    "iris_texture_quantize": [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P],
     "iris_exr_zip_workspace_bytes": [_I32, _I64, _I64, _I64],
     "iris_exr_zip_encode": [_P, _P, _I32, _I64, _I64, _I64, _I32, _P, _P, _P, _U64, _P],
     "iris_bake_tile_max_spp": [],
@@ -122,7 +127,7 @@ PROTOTYPES = {
 _RESTYPE = {"iris_scene_destroy": None, "iris_slf_destroy": None, "iris_emitter_destroy": None,
             "iris_last_error": C.c_char_p, "iris_version": C.c_char_p, "iris_debug_build_flags": C.c_char_p, "iris_debug_source_hash": C.c_char_p, "iris_ngp_n_params": C.c_int64, "iris_ngp_destroy": None, "iris_bake_workspace_bytes": C.c_uint64, "iris_pt_compact_workspace_bytes": C.c_uint64, "iris_denoise_workspace_bytes": C.c_uint64,
             "iris_exr_zip_workspace_bytes": C.c_uint64, "iris_ngp_backward_workspace_bytes": C.c_uint64, "iris_crf_bwd_workspace_bytes": C.c_uint64,
-            "iris_image_metrics_workspace_bytes": C.c_uint64}
+            "iris_image_metrics_workspace_bytes": C.c_uint64, "iris_uv_raster_workspace_bytes": C.c_uint64}
 
 _lib = None
 

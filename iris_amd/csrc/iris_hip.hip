@@ -23,6 +23,7 @@
 #include "iris_cache.h"
 #include "iris_denoise.h"
 #include "iris_metrics.h"
+#include "iris_texture.h"
 #include "iris_ngp.h"
 #include "iris_prop.h"
 #include "iris_crf.h"
@@ -1087,6 +1088,88 @@ extern "C" IRIS_API int iris_image_metrics(const float* a, const float* b, int32
         hipLaunchKernelGGL(metrics_tile_kernel<3>, dim3(N * tiles), dim3(kMetThreads), 0, st, g);
         hipLaunchKernelGGL(metrics_slab_sum_kernel<3>, dim3(N), dim3(kMetThreads), 0, st, (const double*)workspace, tiles, sums);
     }
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
+// ======================================================================================================
+// texture export: UV rasteriser, per-texel resolve, quantisation (iris_texture.h)
+// ======================================================================================================
+static_assert(kUvSub == 256, "uv_setup shifts by 8");
+static const int64_t kUvMaxRes = 8192;
+static bool uv_shape(int64_t n_vt, int64_t F, int H, int W) {
+    return n_vt >= 0 && F >= 0 && F <= INT32_MAX && H >= 1 && W >= 1 && H <= kUvMaxRes && W <= kUvMaxRes;
+}
+static int64_t uv_blocks(int64_t n) { return (n + kUvThreads - 1) / kUvThreads; }
+extern "C" IRIS_API uint64_t iris_uv_raster_workspace_bytes(int64_t F) {
+    if (F < 0 || F > INT32_MAX) return 0;
+    return (uint64_t)((16 + 12 * F + 15) / 16 * 16);       // header, then per triangle an int64 first item and an int32 face index
+}
+static int uv_raster(const char* who, const float* vt, int64_t n_vt, const int32_t* ft, int64_t F, int H, int W, int32_t* ids, void* workspace,
+                     uint64_t workspace_bytes, int mode, iris_stream_t stream) {
+    if (!uv_shape(n_vt, F, H, W))
+        return fail(IRIS_ERR_ARG, std::string(who) + ": bad sizes (n_vt " + std::to_string(n_vt) + ", F " + std::to_string(F) + ", H " + std::to_string(H) + ", W " +
+                                      std::to_string(W) + "): H and W in [1, 8192], F below 2^31");
+    if (!ids || (uintptr_t)ids % 4 || (F > 0 && (!vt || !ft || (uintptr_t)vt % 4 || (uintptr_t)ft % 4)))
+        return fail(IRIS_ERR_ARG, std::string(who) + ": null or misaligned vt / ft / ids");
+    const uint64_t need = iris_uv_raster_workspace_bytes(F);
+    if (!workspace || workspace_bytes < need || (uintptr_t)workspace % 8)
+        return fail(IRIS_ERR_ARG, std::string(who) + ": an 8-byte aligned workspace of " + std::to_string(need) + " bytes is required (got " +
+                                      std::to_string(workspace_bytes) + ")");
+    if (mode < 0 || (mode > kUvModeAllLarge && mode < 64)) return fail(IRIS_ERR_ARG, std::string(who) + ": unknown mode " + std::to_string(mode));
+    const hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(ids, 0xFF, (size_t)H * W * sizeof(int32_t), st));          // -1: uncovered, and the largest value of the unsigned atomicMin
+    if (F == 0) return IRIS_OK;
+    // the queue's slot field holds 24 bits, its item field 40: F triangles of at most 2^16 items each (8192 rows x 128 segments / 16) fit when F < 2^24.
+    // A larger mesh keeps every triangle with its lane (correct at any size; such a mesh has no room for large triangles anyway).
+    static_assert(kUvMaxRes * ((kUvMaxRes + 63) / 64) / kUvChunkSegs <= (1 << (kUvItemBits - kUvSlotBits)), "items of one triangle");
+    int64_t small_max = mode == kUvModeAuto ? kUvSmallMaxTexels : mode == kUvModeAllSmall ? INT64_MAX : mode == kUvModeAllLarge ? 0 : (int64_t)mode;
+    if (F >= ((int64_t)1 << kUvSlotBits)) small_max = INT64_MAX;
+    UvQueue q;
+    q.head = (unsigned long long*)workspace;
+    q.first = (int64_t*)((char*)workspace + 16);
+    q.face = (int32_t*)((char*)workspace + 16 + 8 * F);
+    q.capacity = F;
+    HIP_TRY(hipMemsetAsync(workspace, 0, 16, st));
+    hipLaunchKernelGGL(uv_class_kernel, dim3((unsigned)uv_blocks(F)), dim3(kUvThreads), 0, st, vt, n_vt, ft, F, H, W, (uint32_t*)ids, q, small_max);
+    if (small_max != INT64_MAX)
+        hipLaunchKernelGGL(uv_span_kernel, dim3(kUvSpanBlocks), dim3(kUvThreads), 0, st, vt, n_vt, ft, H, W, (uint32_t*)ids, q);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_uv_raster(const float* vt, int64_t n_vt, const int32_t* ft, int64_t F, int32_t H, int32_t W, int32_t* ids, void* workspace,
+                                       uint64_t workspace_bytes, iris_stream_t stream) {
+    return uv_raster("iris_uv_raster", vt, n_vt, ft, F, H, W, ids, workspace, workspace_bytes, kUvModeAuto, stream);
+}
+extern "C" IRIS_API int iris_debug_uv_raster(const float* vt, int64_t n_vt, const int32_t* ft, int64_t F, int32_t H, int32_t W, int32_t* ids, void* workspace,
+                                             uint64_t workspace_bytes, int mode, iris_stream_t stream) {
+    return uv_raster("iris_debug_uv_raster", vt, n_vt, ft, F, H, W, ids, workspace, workspace_bytes, mode, stream);
+}
+extern "C" IRIS_API int iris_uv_resolve(const float* vt, int64_t n_vt, const int32_t* ft, const float* v, int64_t n_v, const int32_t* f, int64_t F, int32_t H,
+                                        int32_t W, const int32_t* ids, int64_t texel0, int64_t n, float* bary, float* xyz, iris_stream_t stream) {
+    if (!uv_shape(n_vt, F, H, W) || n_v < 0 || texel0 < 0 || n < 0 || texel0 + n > (int64_t)H * W)
+        return fail(IRIS_ERR_ARG, "iris_uv_resolve: bad sizes or a texel range outside the texture (texel0 " + std::to_string(texel0) + ", n " + std::to_string(n) + ")");
+    if (n == 0) return IRIS_OK;
+    if (!ids || !xyz || (uintptr_t)ids % 4 || (uintptr_t)xyz % 4 || (uintptr_t)bary % 4 ||
+        (F > 0 && (!vt || !ft || !v || !f || (uintptr_t)vt % 4 || (uintptr_t)ft % 4 || (uintptr_t)v % 4 || (uintptr_t)f % 4)))
+        return fail(IRIS_ERR_ARG, "iris_uv_resolve: null or misaligned pointer");
+    hipLaunchKernelGGL(uv_resolve_kernel, dim3((unsigned)uv_blocks(n)), dim3(kUvThreads), 0, (hipStream_t)stream, vt, n_vt, ft, v, n_v, f, F, H, W, ids, texel0, n,
+                       bary, xyz);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_texture_quantize(const float* albedo, const float* roughness, const float* metallic, const int32_t* ids, int64_t texel0, int64_t n,
+                                              int64_t n_texels, uint8_t* albedo_img, uint8_t* rm_img, iris_stream_t stream) {
+    if (texel0 < 0 || n < 0 || n_texels < 0 || n_texels > kUvMaxRes * kUvMaxRes || texel0 + n > n_texels)
+        return fail(IRIS_ERR_ARG, "iris_texture_quantize: texel range [" + std::to_string(texel0) + ", +" + std::to_string(n) + ") outside the texture of " +
+                                      std::to_string(n_texels) + " texels");
+    if (n == 0) return IRIS_OK;
+    if (!albedo || !roughness || !metallic || !ids || !albedo_img || !rm_img || (uintptr_t)albedo % 4 || (uintptr_t)roughness % 4 || (uintptr_t)metallic % 4 ||
+        (uintptr_t)ids % 4 || (uintptr_t)albedo_img % 4 || (uintptr_t)rm_img % 4)
+        return fail(IRIS_ERR_ARG, "iris_texture_quantize: null pointer, or one that is not 4-byte aligned (the images are stored in words)");
+    const int64_t groups = (texel0 + n + 3) / 4 - texel0 / 4;
+    hipLaunchKernelGGL(uv_quantize_kernel, dim3((unsigned)uv_blocks(groups)), dim3(kUvThreads), 0, (hipStream_t)stream, albedo, roughness, metallic, ids, texel0, n,
+                       albedo_img, rm_img);
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }

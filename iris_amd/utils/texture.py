@@ -1,0 +1,227 @@
+"""Texture export on the device (reference: utils/export.py): UV rasteriser, material bake into albedo / roughness-metallic images, and the small host
+pieces the stage needs (an atlas stand-in, a PNG writer, a textured OBJ writer).
+
+The reference unwraps with xatlas and rasterises with nvdiffrast; both are third-party CUDA / GL packages without a ROCm build and neither is a dependency
+here.  The rasteriser is this project's own HIP (iris_amd/csrc/iris_texture.h) with an exact contract: texel (r, c) of an H x W
+texture has its centre at u = (c + .5) / W, v = (r + .5) / H, row 0 at v ~ 0; UVs snapped to 1 / 256 texel; int64 edge functions with a top-left rule; the
+lowest face index wins an overlap; barycentrics from a float64 division, positions interpolated in float32 in one stated order.  tests/uv_raster_ref.py is
+the same contract in numpy, and the kernels equal it bit for bit.
+"""
+import os
+import struct
+import zlib
+
+import numpy as np
+import torch
+
+from .. import _lib as L
+
+MAX_TEX_RES = 8192
+RASTER_AUTO, RASTER_ALL_SMALL, RASTER_ALL_LARGE = 0, 1, 2        # include/iris_hip_debug.h IRIS_UV_RASTER_*
+
+
+def _hw(tex_res):
+    if isinstance(tex_res, (tuple, list)):
+        if len(tex_res) != 2:
+            raise L.IrisError(f"tex_res = {tex_res!r}: an integer or (H, W)")
+        H, W = tex_res
+    else:
+        H = W = tex_res
+    for n in (H, W):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= MAX_TEX_RES:
+            raise L.IrisError(f"tex_res = {tex_res!r}: every side must be an integer in [1, {MAX_TEX_RES}]")
+    return int(H), int(W)
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+def _summary(a):
+    """(shape, kind 'f' / 'i' / other, all finite, min, max) of a host array or of a tensor WHERE IT LIVES: a device tensor is reduced on its device and three
+    scalars are read back, the array itself is not copied"""
+    if torch.is_tensor(a):
+        a = a.detach()
+        kind = "f" if a.is_floating_point() else "i" if a.dtype in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) else "?"
+        if a.numel() == 0 or kind == "?":
+            return tuple(a.shape), kind, True, 0, 0
+        lo, hi = torch.aminmax(a)
+        finite = bool(torch.isfinite(a).all()) if kind == "f" else True
+        return tuple(a.shape), kind, finite, lo.item(), hi.item()
+    a = np.asarray(a)
+    kind = "f" if a.dtype.kind == "f" else "i" if a.dtype.kind in "iu" else "?"
+    if a.size == 0 or kind == "?":
+        return a.shape, kind, True, 0, 0
+    return a.shape, kind, bool(np.isfinite(a).all()) if kind == "f" else True, a.min(), a.max()
+
+
+def check_inputs(vt, ft, v, f, tex_res):
+    """The host checks of the contract, before anything is uploaded -> (H, W).  Raises IrisError on: a tex_res outside [1, 8192]; vt not (N, 2), v not (V, 3),
+    ft / f not (F, 3) integers or of different shapes; UVs that are not finite or lie outside [-1, 2]; an index of ft outside vt or of f outside v.
+    Under these limits every edge value of the rasteriser stays far below 2^53.  (An input that already is a device tensor is reduced there.)"""
+    H, W = _hw(tex_res)
+    (s_vt, k_vt, finite, vt_lo, vt_hi), (s_ft, k_ft, _, ft_lo, ft_hi) = _summary(vt), _summary(ft)
+    (s_v, k_v, _, _, _), (s_f, k_f, _, f_lo, f_hi) = _summary(v), _summary(f)
+    if len(s_vt) != 2 or s_vt[1] != 2 or len(s_v) != 2 or s_v[1] != 3:
+        raise L.IrisError(f"rasterize_uv: vt {s_vt} must be (N, 2) and v {s_v} must be (V, 3)")
+    if s_ft != s_f:
+        raise L.IrisError(f"rasterize_uv: ft {s_ft} and f {s_f} differ in shape (one UV triangle per face)")
+    if len(s_ft) != 2 or s_ft[1] != 3 or k_ft != "i" or k_f != "i":
+        raise L.IrisError(f"rasterize_uv: ft {s_ft} and f {s_f} must be (F, 3) integer arrays")
+    if s_ft[0] > 2 ** 31 - 1:
+        raise L.IrisError("rasterize_uv: more than 2^31 - 1 faces")
+    if k_vt != "f" or k_v != "f":
+        raise L.IrisError("rasterize_uv: vt and v must be floating point")
+    if not finite:
+        raise L.IrisError("rasterize_uv: vt holds a non-finite UV")
+    if vt_lo < -1.0 or vt_hi > 2.0:
+        raise L.IrisError(f"rasterize_uv: UVs must lie in [-1, 2] (got [{vt_lo}, {vt_hi}])")
+    if s_ft[0] and (ft_lo < 0 or ft_hi >= s_vt[0]):
+        raise L.IrisError(f"rasterize_uv: ft indexes [{ft_lo}, {ft_hi}] outside the {s_vt[0]} UV vertices")
+    if s_f[0] and (f_lo < 0 or f_hi >= s_v[0]):
+        raise L.IrisError(f"rasterize_uv: f indexes [{f_lo}, {f_hi}] outside the {s_v[0]} vertices")
+    return H, W
+
+
+def _upload(a, dtype, dev):
+    t = a.detach() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.to(device=dev, dtype=dtype).contiguous()
+
+
+class UVMesh:
+    """The checked, uploaded inputs of one export: vt (N, 2) f32, ft (F, 3) i32, v (V, 3) f32, f (F, 3) i32 on the device, and the texture size."""
+
+    def __init__(self, vt, ft, v, f, tex_res, device=None):
+        L.no_autograd("rasterize_uv", vt, v)
+        self.H, self.W = check_inputs(vt, ft, v, f, tex_res)
+        if device is None:
+            device = next((a.device for a in (vt, ft, v, f) if torch.is_tensor(a) and a.is_cuda), "cuda")
+        self.device = torch.device("cuda", L.device_index(device))
+        self.vt, self.v = _upload(vt, torch.float32, self.device), _upload(v, torch.float32, self.device)
+        self.ft, self.f = _upload(ft, torch.int32, self.device), _upload(f, torch.int32, self.device)
+        self.F = int(self.ft.shape[0])
+
+    def raster(self, mode=None):
+        """ids (H, W) int32: the face per texel, -1 where uncovered.  mode: None = iris_uv_raster, else IRIS_UV_RASTER_* through iris_debug_uv_raster."""
+        lib = L.lib()
+        ids = torch.empty(self.H, self.W, dtype=torch.int32, device=self.device)
+        need = int(lib.iris_uv_raster_workspace_bytes(self.F))
+        ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            if mode is None:
+                L.check(lib.iris_uv_raster(L.ptr(self.vt), self.vt.shape[0], L.ptr(self.ft), self.F, self.H, self.W, L.ptr(ids), L.ptr(ws), need, L.stream()))
+            else:
+                L.check(lib.iris_debug_uv_raster(L.ptr(self.vt), self.vt.shape[0], L.ptr(self.ft), self.F, self.H, self.W, L.ptr(ids), L.ptr(ws), need, int(mode),
+                                                 L.stream()))
+        return ids
+
+    def resolve(self, ids, texel0=0, n=None, bary=True):
+        """(bary (n, 2) or None, xyz (n, 3)) of the texels [texel0, texel0 + n) of the texture rasterised into ids."""
+        n = self.H * self.W - texel0 if n is None else int(n)
+        b = torch.empty(n, 2, device=self.device) if bary else None
+        xyz = torch.empty(n, 3, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().iris_uv_resolve(L.ptr(self.vt), self.vt.shape[0], L.ptr(self.ft), L.ptr(self.v), self.v.shape[0], L.ptr(self.f), self.F, self.H, self.W,
+                                            L.ptr(ids), int(texel0), n, L.ptr(b), L.ptr(xyz), L.stream()))
+        return b, xyz
+
+
+def rasterize_uv(vt, ft, v, f, tex_res, device=None):
+    """Rasterise the UV triangles (vt (N, 2), ft (F, 3)) into a texture of tex_res (an integer, or (H, W)) and interpolate the mesh (v (V, 3), f (F, 3)) there:
+    what `dr.rasterize` + `dr.interpolate` give the reference (utils/export.py:83-92), under this project's exact contract.  Inputs: GPU tensors or host arrays.
+    -> {'ids' (H, W) int32, -1 uncovered; 'mask' (H, W) bool; 'bary' (H, W, 2) f32, weights of vertices 0 and 1; 'xyz' (H, W, 3) f32}, device tensors
+    (zeros where uncovered).  No backward pass: an input that requires grad raises."""
+    m = UVMesh(vt, ft, v, f, tex_res, device)
+    ids = m.raster()
+    bary, xyz = m.resolve(ids)
+    return {"ids": ids, "mask": ids >= 0, "bary": bary.reshape(m.H, m.W, 2), "xyz": xyz.reshape(m.H, m.W, 3)}
+
+
+def quantize_into(albedo, roughness, metallic, ids, texel0, albedo_img, rm_img):
+    """iris_texture_quantize: float32 albedo (n, 3), roughness (n[, 1]), metallic (n[, 1]) of the texels [texel0, texel0 + n) -> their bytes of the two
+    (H, W, 3) uint8 images; 0 where ids < 0."""
+    albedo = L.require_gpu(albedo, torch.float32, "albedo").detach().reshape(-1, 3)
+    roughness = L.require_gpu(roughness, torch.float32, "roughness").detach().reshape(-1)
+    metallic = L.require_gpu(metallic, torch.float32, "metallic").detach().reshape(-1)
+    n = albedo.shape[0]
+    if roughness.shape[0] != n or metallic.shape[0] != n:
+        raise L.IrisError(f"quantize: albedo {n}, roughness {roughness.shape[0]} and metallic {metallic.shape[0]} texels differ")
+    ids = L.require_gpu(ids, torch.int32, "ids")
+    for img in (albedo_img, rm_img):
+        if img.dtype != torch.uint8 or not img.is_contiguous() or img.numel() != ids.numel() * 3 or img.device != ids.device:
+            raise L.IrisError("quantize: the images must be contiguous (H, W, 3) uint8 tensors on the device of ids")
+    with torch.cuda.device(ids.device):
+        L.check(L.lib().iris_texture_quantize(L.ptr(albedo), L.ptr(roughness), L.ptr(metallic), L.ptr(ids), int(texel0), n, ids.numel(), L.ptr(albedo_img),
+                                              L.ptr(rm_img), L.stream()))
+
+
+@torch.no_grad()
+def bake_textures(material_net, vt, ft, v, f, tex_res, chunk_size=160000, device=None):
+    """The material network baked into the UV atlas (utils/export.py:77-135) -> (albedo, rm): two (H, W, 3) uint8 device tensors, rm = (roughness, metallic, 0).
+    The ids are rasterised once; then, per chunk of `chunk_size` consecutive texels: resolve, material_net(xyz), quantise.  The network runs on EVERY texel of
+    a chunk, covered or not (uncovered ones sit at the origin and are masked by the quantiser): no compaction pass, no host round trip.
+    material_net: any callable with NGPBRDF.forward's contract."""
+    chunk_size = int(chunk_size)
+    if chunk_size < 1:
+        raise L.IrisError(f"bake_textures: chunk_size = {chunk_size}")
+    m = UVMesh(vt, ft, v, f, tex_res, device)
+    ids = m.raster()
+    albedo = torch.empty(m.H, m.W, 3, dtype=torch.uint8, device=m.device)
+    rm = torch.empty(m.H, m.W, 3, dtype=torch.uint8, device=m.device)
+    for texel0 in range(0, m.H * m.W, chunk_size):
+        _, xyz = m.resolve(ids, texel0, min(chunk_size, m.H * m.W - texel0), bary=False)
+        mat = material_net(xyz)
+        quantize_into(mat["albedo"], mat["roughness"], mat["metallic"], ids, texel0, albedo, rm)
+    return albedo, rm
+
+
+def grid_atlas(n_faces, tex_res):
+    """The stand-in for xatlas, which is not a dependency: (vt (3F, 2) float32, ft = arange(3F).reshape(F, 3) int32), host numpy.
+    Every face gets its own three UV vertices.  Two faces share a cell of a G x G grid, G = ceil(sqrt(ceil(F / 2))), as the two halves on either side of the
+    cell's diagonal; each is inset by a quarter texel from the cell and from the diagonal, so that no texel centre is covered by two faces, and at a tex_res
+    that gives cells of 4 texels or more every face covers a texel centre.
+    It IGNORES the triangles' shape and area: every face gets the same right triangle.  Valid (a bijection onto disjoint charts), but not a good atlas: no
+    chart shares an edge with its neighbour in 3-D, texel density is unrelated to surface area.  An atlas made elsewhere drops in as vt.npy / ft.npy."""
+    F = int(n_faces)
+    if F < 1:
+        raise L.IrisError(f"grid_atlas: n_faces = {n_faces}")
+    H, W = _hw(tex_res)
+    G = int(np.ceil(np.sqrt((F + 1) // 2)))
+    while G * G < (F + 1) // 2:
+        G += 1
+    m = g = 0.25                                                   # texels: margin to the cell's border, half gap along the diagonal
+    cell = np.arange((F + 1) // 2)
+    x0, y0 = (cell % G) * (W / G), (cell // G) * (H / G)           # the cell's corner, texels (float64)
+    x1, y1 = x0 + W / G, y0 + H / G
+    lower = np.stack([np.stack([x0 + m, y0 + m], -1), np.stack([x1 - m - g, y0 + m], -1), np.stack([x0 + m, y1 - m - g], -1)], 1)       # (cells, 3, 2)
+    upper = np.stack([np.stack([x1 - m, y1 - m], -1), np.stack([x0 + m + g, y1 - m], -1), np.stack([x1 - m, y0 + m + g], -1)], 1)
+    tri = np.stack([lower, upper], 1).reshape(-1, 3, 2)[:F]        # faces 2 k and 2 k + 1 share cell k
+    vt = (tri / np.array([W, H], np.float64)).reshape(-1, 2).astype(np.float32)
+    return vt, np.arange(3 * F, dtype=np.int32).reshape(F, 3)
+
+
+def write_png(path, rgb_uint8):
+    """8-bit RGB PNG of an (H, W, 3) uint8 array (host array or tensor) with the standard library alone: every scanline with filter 0, one IDAT chunk."""
+    a = _host(rgb_uint8)
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise L.IrisError(f"write_png: expected an (H, W, 3) uint8 image, got {a.shape} {a.dtype}")
+    H, W = a.shape[:2]
+    raw = np.concatenate([np.zeros((H, 1), np.uint8), np.ascontiguousarray(a).reshape(H, W * 3)], 1).tobytes()
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+
+
+def write_textured_obj(dir_save, v, f, vt, ft):
+    """<dir>/mesh.obj (v, vt, f a/ta b/tb c/tc; floats with 9 significant digits: float32 round-trips) and <dir>/mesh.mtl with map_Kd albedo.png: what makes
+    the export folder loadable (the reference leaves that to the user).  vt is written as it is: image row 0 is v ~ 0, the reference's layout."""
+    v, f, vt, ft = _host(v), _host(f), _host(vt), _host(ft)
+    with open(os.path.join(dir_save, "mesh.mtl"), "w") as fh:
+        fh.write("newmtl material_0\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nmap_Kd albedo.png\n")
+    with open(os.path.join(dir_save, "mesh.obj"), "w") as fh:
+        fh.write("mtllib mesh.mtl\nusemtl material_0\n")
+        fh.write("".join("v %.9g %.9g %.9g\n" % tuple(float(x) for x in p) for p in v))
+        fh.write("".join("vt %.9g %.9g\n" % tuple(float(x) for x in p) for p in vt))
+        fh.write("".join("f %d/%d %d/%d %d/%d\n" % (a[0] + 1, b[0] + 1, a[1] + 1, b[1] + 1, a[2] + 1, b[2] + 1) for a, b in zip(f.tolist(), ft.tolist())))
