@@ -414,6 +414,24 @@ IRIS_API int iris_prop_part_fwd(const int32_t *runs, const int64_t *order, const
 IRIS_API int iris_prop_part_bwd(const int32_t *runs, const int64_t *order, const float *roughness, const float *seg_means, const float *signs, int64_t N, float lp,
                        const float *g_loss, float *g_roughness, float *g_metallic, iris_stream_t);
 
+/* ---- the trainers' albedo regulariser (train_brdf_crf.py:292-306 with utils/loss.py:14-37; initialize.py:188-201) ---------------------- */
+/* Works on the sorted batch of the propagation calls: runs from iris_prop_runs, order = torch.sort(segmentation, stable=True)'s permutation; N < 2^31 - 64.
+ * albedo, prior (N, 3) f32 by pixel.  T_s = (sum over segment s of prior) / count, tbar_i = T_s(i);
+ *   fit_scale == 0:  k = 1;                                                              (initialize.py:201)
+ *   fit_scale != 0:  k = sum(tbar * albedo) / sum(tbar * tbar) over the 3 N entries (utils/loss.py:14-20; the scale multiplies the prior);
+ *   loss[0] = weight / (3 N) * sum (k tbar - albedo)^2.
+ * k[0] is written on the device and read there by the backward: nothing synchronises.  sum(tbar * tbar) = 0 gives k = NaN and a NaN loss, as the reference.
+ * One wave per segment sums the priors lane-strided in position order; every other sum is a fixed tree per 256 positions and one fixed-order pass over
+ * those partials; no atomics: two calls on the same inputs agree bit for bit.  Kept for the backward: seg_means (N, 4) f32, row `start` of a run =
+ * (T.x, T.y, T.z, 0), other rows unwritten, 16-byte aligned; k.  partials: 3 * min(ceil(N / 256), 4096) f32 of scratch, 8-byte aligned.
+ * N = 0 writes loss[0] = 0 and leaves k alone. */
+IRIS_API int iris_loss_albedo_fwd(const int32_t *runs, const int64_t *order, const float *albedo, const float *prior, int64_t N, int fit_scale,
+                         float weight, float *seg_means, float *partials, float *k, float *loss, iris_stream_t);
+/* g_albedo[i] = weight * 2 / (3 N) * g_loss[0] * (albedo_i - k tbar_i) with the forward's seg_means and k (k is a constant of the backward, as the
+ * reference's .item() makes it); one plain store per entry, every pixel written once; the prior gets no gradient. */
+IRIS_API int iris_loss_albedo_bwd(const int32_t *runs, const int64_t *order, const float *albedo, const float *seg_means, const float *k, int64_t N, float weight,
+                         const float *g_loss, float *g_albedo, iris_stream_t);
+
 /* ---- the camera response model EmorCRF (crf/model_crf.py:32-122) ---------------------------------------------------------------------- */
 /* The interpolator is this project's contract (the reference's torch_interpolations is third-party and has no ROCm build: parity unpinned).  Knots p[0..n)
  * non-decreasing, values v[0..n), query q:  r = first index with p[r] >= q, clamped to n - 1 (torch.bucketize);  l = max(r - 1, 0);  dl = max(q - p[l], 0);

@@ -104,6 +104,8 @@ PROTOTYPES = {
     "iris_prop_semantic_bwd": [_P, _P, _P, _P, _I64, _I32, _P, _U64, _D, _D, _F, _P, _P, _P, _P, _P],
     "iris_prop_part_fwd": [_P, _P, _P, _P, _I64, _F, _P, _P, _P, _P, _P],
     "iris_prop_part_bwd": [_P, _P, _P, _P, _P, _I64, _F, _P, _P, _P, _P],
+    "iris_loss_albedo_fwd": [_P, _P, _P, _P, _I64, _I32, _F, _P, _P, _P, _P, _P],
+    "iris_loss_albedo_bwd": [_P, _P, _P, _P, _P, _I64, _F, _P, _P, _P],
     "iris_crf_fwd": [_P, _P, _I32, _P, _P, _I64, _F, _I64, _P, _P],
     "iris_crf_lookup_inv": [_P, _P, _I32, _P, _P, _I64, _F, _I64, _P, _P],
     "iris_crf_bwd_workspace_bytes": [_I64, _I32],

@@ -26,6 +26,7 @@
 #include "iris_texture.h"
 #include "iris_ngp.h"
 #include "iris_prop.h"
+#include "iris_loss.h"
 #include "iris_crf.h"
 #include "iris_render.h"
 #include "iris_deflate.h"
@@ -945,6 +946,42 @@ extern "C" IRIS_API int iris_prop_part_bwd(const int32_t* runs, const int64_t* o
     if (N == 0) return IRIS_OK;
     return launch1d(prop_part_bwd_kernel, N * 64, 1 << 16, stream, (const int2*)runs, order, roughness, (const float4*)seg_means, (const float2*)signs, g_loss, lp,
                     (int)N, g_roughness, g_metallic);
+}
+
+// ---- the trainers' albedo regulariser (iris_loss.h; train_brdf_crf.py:292-306, initialize.py:188-201)
+static int loss_blocks(int64_t N) { return grid_for(N, kLossThreads, kLossMaxBlocks); }       // a function of N alone: the sums' grouping does not depend on the device
+extern "C" IRIS_API int iris_loss_albedo_fwd(const int32_t* runs, const int64_t* order, const float* albedo, const float* prior, int64_t N, int fit_scale,
+                                             float weight, float* seg_means, float* partials, float* k, float* loss, iris_stream_t stream) {
+    if (!prop_n_ok(N) || !loss || !k || (N > 0 && (!runs || !order || !albedo || !prior || !seg_means || !partials)))
+        return fail(IRIS_ERR_ARG, "iris_loss_albedo_fwd: bad arguments");
+    if ((uintptr_t)seg_means % 16 || (uintptr_t)partials % 8) return fail(IRIS_ERR_ARG, "iris_loss_albedo_fwd: seg_means must be 16-byte, partials 8-byte aligned");
+    const int blocks = N > 0 ? loss_blocks(N) : 0;
+    float2* dots = (float2*)partials;                 // 2 x blocks floats, then the terms' blocks floats
+    float* terms = partials + 2 * (size_t)blocks;
+    if (N > 0) {
+        int rc = launch1d(loss_seg_means_kernel, N * 64, 1 << 16, stream, (const int2*)runs, order, prior, (int)N, (float4*)seg_means);
+        if (rc) return rc;
+        if (fit_scale) {
+            hipLaunchKernelGGL(loss_dots_kernel, dim3(blocks), dim3(kLossThreads), 0, (hipStream_t)stream, (const int2*)runs, order, albedo,
+                               (const float4*)seg_means, (int)N, dots);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(loss_terms_kernel, dim3(blocks), dim3(kLossThreads), 0, (hipStream_t)stream, (const int2*)runs, order, albedo,
+                           (const float4*)seg_means, fit_scale ? (const float2*)dots : (const float2*)nullptr, blocks, (int)N, terms, k);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(prop_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)terms, blocks, N > 0 ? (float)((double)weight / (3.0 * (double)N)) : 0.f, loss);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_loss_albedo_bwd(const int32_t* runs, const int64_t* order, const float* albedo, const float* seg_means, const float* k, int64_t N,
+                                             float weight, const float* g_loss, float* g_albedo, iris_stream_t stream) {
+    if (!prop_n_ok(N) || (N > 0 && (!runs || !order || !albedo || !seg_means || !k || !g_loss || !g_albedo)))
+        return fail(IRIS_ERR_ARG, "iris_loss_albedo_bwd: bad arguments");
+    if ((uintptr_t)seg_means % 16) return fail(IRIS_ERR_ARG, "iris_loss_albedo_bwd: seg_means must be 16-byte aligned");
+    if (N == 0) return IRIS_OK;
+    return launch1d(loss_albedo_bwd_kernel, N, 4096, stream, (const int2*)runs, order, albedo, (const float4*)seg_means, k, g_loss,
+                    (float)(2.0 * (double)weight / (3.0 * (double)N)), (int)N, g_albedo);
 }
 
 // ---- the camera response model (iris_crf.h; crf/model_crf.py:32-122)
