@@ -98,6 +98,20 @@ IRIS_API int iris_raygen_real(const float K[9], const float c2w[12], int H, int 
 /* get_ray_directions + get_rays (utils/dataset/synthetic_ldr.py:21-57) */
 IRIS_API int iris_raygen_synthetic(float focal, const float c2w[12], int H, int W, int ray_diff, float *rays_o, float *rays_d,
                           float *dxdu, float *dydv, iris_stream_t);
+/* The trainers' pixel batch: what Inv*DatasetLDR(pixel=True).__getitem__ slices from its host table (utils/dataset/real_ldr.py:399-427), from a
+ * list of global pixel ids.  ALL pointers are DEVICE pointers.  ids (B) int64: view * H*W + y*W + x, each in [0, V*H*W) -- bounding them is the
+ * caller's; an id outside the range reads nothing and yields a row of zeros (segmentation -1).  cameras (V,24) f32, 16-B aligned, per view
+ * K[9] | c2w[12] | focal | 2 pad (row-major; K is unused when synthetic, focal when not).
+ * Stores, each NULL or per pixel of all views in id order: rgb and int_albedo (N,3), uint8 when *_is_u8 else float32; segmentation (N) int32;
+ * positions (N,3) f32; exposure (V) f32, per VIEW.
+ * Outputs, each NULL or written in full (an output whose store is NULL is an error): rays (B,12) f32, 16-B aligned, = [o | d | dxdu | dydv], the bits
+ * iris_raygen_real / iris_raygen_synthetic write for that view and pixel with the same ray_diff (ray_diff = 0: d normalised, dxdu = dydv = 0);
+ * rgbs, int_albedo (B,3) f32, a uint8 level u decoded as (float)((double)u / 255.0); segmentation (B) int64; exposure (B,1) f32; positions (B,3)
+ * f32.  One launch; B = 0 is a no-op. */
+IRIS_API int iris_pixel_batch(const int64_t *ids, int64_t B, const float *cameras, int64_t V, int H, int W, int ray_diff, int synthetic,
+                     const void *rgb, int rgb_is_u8, const void *int_albedo, int int_albedo_is_u8, const int32_t *segmentation,
+                     const float *positions, const float *exposure, float *out_rays, float *out_rgbs, float *out_int_albedo,
+                     int64_t *out_segmentation, float *out_exposure, float *out_positions, iris_stream_t);
 
 /* ---- a2: ray_intersect(scene, xs, ds)  (utils/path_tracing.py:17-48) ---------------------------------- */
 /* Any output pointer may be NULL.  Miss: idx=-1, valid=0, pos/nrm/uv=0. */

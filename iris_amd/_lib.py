@@ -38,6 +38,7 @@ PROTOTYPES = {
     "iris_emitter_destroy": [_P],
     "iris_raygen_real": [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P],
     "iris_raygen_synthetic": [_F, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P],
+    "iris_pixel_batch": [_P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "iris_intersect": [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P],
     "iris_sample_diffuse": [_P, _P, _I64, _P, _P, _P, _P],
     "iris_sample_specular": [_P, _P, _P, _F, _I64, _P, _P, _P, _P, _P],

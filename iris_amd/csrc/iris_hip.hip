@@ -30,6 +30,7 @@
 #include "iris_crf.h"
 #include "iris_render.h"
 #include "iris_deflate.h"
+#include "iris_batch.h"
 
 using namespace iris;
 
@@ -544,29 +545,12 @@ __global__ void raygen_kernel(RaygenArgs a, float* __restrict__ rays_o, float* _
     const int64_t n = (int64_t)a.H * a.W;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int y = (int)(i / a.W), x = (int)(i - (int64_t)y * a.W);
-        float dc0, dc1, ifx, ify;
-        if (a.synthetic) {  // utils/dataset/synthetic_ldr.py:21-34
-            const float hw = (float)((double)a.W / 2.0), hh = (float)((double)a.H / 2.0);
-            dc0 = -(((float)x + 0.5f) - hw) / a.focal;
-            dc1 = -(((float)y + 0.5f) - hh) / a.focal;
-            ifx = ify = 1.0f / a.focal;
-        } else {  // utils/dataset/real_ldr.py:49-61
-            dc0 = ((float)x + 0.5f - a.K[2]) / a.K[0];
-            dc1 = ((float)y + 0.5f - a.K[5]) / a.K[4];
-            ifx = 1.0f / a.K[0]; ify = 1.0f / a.K[4];
-        }
-        f3 d = mk3((dc0 * a.c2w[0] + dc1 * a.c2w[1]) + a.c2w[2], (dc0 * a.c2w[4] + dc1 * a.c2w[5]) + a.c2w[6],
-                   (dc0 * a.c2w[8] + dc1 * a.c2w[9]) + a.c2w[10]);
-        rays_o[i * 3] = a.c2w[3]; rays_o[i * 3 + 1] = a.c2w[7]; rays_o[i * 3 + 2] = a.c2w[11];
+        const PixelRay r = raygen_pixel(a.K, a.c2w, a.focal, a.H, a.W, a.ray_diff, a.synthetic, x, y);      // iris_batch.h: shared with pixel_batch_kernel
+        st3(rays_o + i * 3, r.o);
+        st3(rays_d + i * 3, r.d);
         if (a.ray_diff) {
-            st3(rays_d + i * 3, d);
-            dxdu[i * 3] = ifx * a.c2w[0]; dxdu[i * 3 + 1] = ifx * a.c2w[4]; dxdu[i * 3 + 2] = ifx * a.c2w[8];
-            dydv[i * 3] = ify * a.c2w[1]; dydv[i * 3 + 1] = ify * a.c2w[5]; dydv[i * 3 + 2] = ify * a.c2w[9];
-        } else if (a.synthetic) {
-            float nrm = sqrtf((d.x * d.x + d.y * d.y) + d.z * d.z);  // rays_d / torch.norm(rays_d)
-            st3(rays_d + i * 3, mk3(d.x / nrm, d.y / nrm, d.z / nrm));
-        } else {
-            st3(rays_d + i * 3, t_normalize(d));
+            st3(dxdu + i * 3, r.dxdu);
+            st3(dydv + i * 3, r.dydv);
         }
     }
 }
@@ -589,6 +573,27 @@ extern "C" IRIS_API int iris_raygen_synthetic(float focal, const float c2w[12], 
     std::memcpy(a.c2w, c2w, 48);
     a.H = H; a.W = W; a.ray_diff = ray_diff; a.synthetic = 1; a.focal = focal;
     return raygen_launch(a, rays_o, rays_d, dxdu, dydv, stream);
+}
+
+// 5c-9: the trainers' pixel batch (iris_batch.h)
+extern "C" IRIS_API int iris_pixel_batch(const int64_t* ids, int64_t B, const float* cameras, int64_t V, int H, int W, int ray_diff, int synthetic,
+                                const void* rgb, int rgb_is_u8, const void* int_albedo, int int_albedo_is_u8, const int32_t* segmentation,
+                                const float* positions, const float* exposure, float* out_rays, float* out_rgbs, float* out_int_albedo,
+                                int64_t* out_segmentation, float* out_exposure, float* out_positions, iris_stream_t stream) {
+    if (B < 0 || V <= 0 || H <= 0 || W <= 0 || !cameras) return fail(IRIS_ERR_ARG, "iris_pixel_batch: bad arguments");
+    if ((out_rgbs && !rgb) || (out_int_albedo && !int_albedo) || (out_segmentation && !segmentation) || (out_exposure && !exposure) ||
+        (out_positions && !positions))
+        return fail(IRIS_ERR_ARG, "iris_pixel_batch: an output was asked for whose store is NULL");
+    if (B == 0) return IRIS_OK;
+    if (!ids) return fail(IRIS_ERR_ARG, "iris_pixel_batch: null ids");
+    PixelBatchArgs a{};
+    a.ids = ids; a.B = B; a.cameras = cameras; a.V = V;
+    a.H = H; a.W = W; a.ray_diff = ray_diff != 0; a.synthetic = synthetic != 0;
+    a.rgb = rgb; a.albedo = int_albedo; a.rgb_u8 = rgb_is_u8 != 0; a.albedo_u8 = int_albedo_is_u8 != 0;
+    a.segmentation = segmentation; a.positions = positions; a.exposure = exposure;
+    a.o_rays = out_rays; a.o_rgbs = out_rgbs; a.o_albedo = out_int_albedo; a.o_segmentation = out_segmentation; a.o_exposure = out_exposure;
+    a.o_positions = out_positions;
+    return launch1d(pixel_batch_kernel, B, 4096, stream, a);
 }
 
 // ======================================================================================================

@@ -1,0 +1,1 @@
+from .pixel_set import PixelSet  # noqa: F401

@@ -10,8 +10,8 @@ The reference builds the albedo term from a ``segmentation.unique``, three ``tor
     out = initialize_loss(mat['albedo'], L, crf=model_crf, exposure=exposure, rgbs_gt=rgbs_gt, albedo_prior=int_albedo, segmentation=segmentation)
     out['loss'].backward()
 
-A trainer stage is a data loader, ``torch.optim.Adam`` and a checkpoint writer around one of these calls; the ``valid`` filtering of the batch is the
-caller's.  Every returned entry is a device tensor: logging them is the caller's synchronisation, not the step's.
+A trainer stage is a data loader (``iris_amd.utils.dataset.PixelSet``), ``torch.optim.Adam`` and a checkpoint writer around one of these calls; the
+``valid`` filtering of the batch is the caller's (``PixelSet.restrict_to_hits`` makes every batch all-valid).  Every returned entry is a device tensor: logging them is the caller's synchronisation, not the step's.
 """
 import torch
 
