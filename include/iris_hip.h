@@ -390,6 +390,23 @@ IRIS_API int iris_ngp_backward(const iris_ngp *, const float *position, int64_t 
                       float loss_scale, float *grad_params, void *workspace, uint64_t workspace_bytes, iris_stream_t);
 IRIS_API void iris_ngp_destroy(iris_ngp *);
 
+/* ---- the trainers' optimizer step ---------------------------------------------------------------------------------- */
+/* torch.optim.Adam (no amsgrad, no maximize; weight_decay is L2: added to the gradient) on DEVICE float32 buffers of n entries, in place, one pass.
+ * step counts from 1 (the step being taken).  The host forms w1 = 1 - beta1, w2 = 1 - beta2, step_size = lr / (1 - beta1^step) and
+ * bc2 = sqrt(1 - beta2^step) in double and rounds each to float once, as it does beta2, eps and weight_decay; per element, in float32 without contraction:
+ *     g' = wd != 0 ? g + wd p : g;   m' = m + w1 (g' - m);   v' = v beta2 + (w2 g') g';   p' = p - step_size (m' / (sqrtf(v') / bc2 + eps)).
+ * Checked on the host before anything is launched: step >= 1; lr and eps finite and positive; 0 <= beta < 1; weight_decay >= 0 and finite; n >= 0;
+ * no NULL pointer when n > 0.  n = 0 is a no-op.
+ * iris_adam_step: any n, 4-byte-aligned pointers; 16-byte accesses where all four pointers are 16-byte aligned, one element per thread otherwise and
+ *   for the last n % 4 entries: the same bits either way.  The four buffers must not overlap.
+ * iris_ngp_adam_step: the step of NGPBRDF's mlp.params (n_params == iris_ngp_n_params(), all four pointers 16-byte aligned) which, in the same pass,
+ *   writes the handle's half copy of the new parameters (round to nearest even: what iris_ngp_set_params_dev would make of them), so that the next
+ *   forward needs no refresh.  Ordered against the handle's other calls as iris_ngp_set_params_dev is. */
+IRIS_API int iris_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, int64_t step, double lr, double beta1,
+                   double beta2, double eps, double weight_decay, iris_stream_t);
+IRIS_API int iris_ngp_adam_step(iris_ngp *, float *params_dev, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n_params, int64_t step,
+                       double lr, double beta1, double beta2, double eps, double weight_decay, iris_stream_t);
+
 /* ---- the BRDF trainer's roughness-metallic propagation regulariser (train_brdf_crf.py:212-290) ------------------------ */
 /* All six calls work on the batch SORTED by segment id: sorted_seg, order = torch.sort(segmentation, stable=True) (N int64 each; a stable sort keeps a
  * segment's pixels in ascending index, the order of the reference's torch.where).  Position q of the sorted batch holds pixel order[q].  N < 2^31 - 64.

@@ -68,6 +68,8 @@ PROTOTYPES = {
     "iris_ngp_backward_workspace_bytes": [_I64],
     "iris_ngp_backward": [_P, _P, _I64, _P, _P, _P, _F, _P, _P, C.c_uint64, _P],
     "iris_ngp_destroy": [_P],
+    "iris_adam_step": [_P, _P, _P, _P, _I64, _I64, _D, _D, _D, _D, _D, _P],
+    "iris_ngp_adam_step": [_P, _P, _P, _P, _P, _I64, _I64, _D, _D, _D, _D, _D, _P],
     "iris_debug_ngp_encode": [_P, _P, _I64, _P, _P],
     "iris_sample_emitter": [_P, _P, _P, _P, _I64, _P, _P, _P, _P],
     "iris_eval_brdf": [_P, _P, _P, _P, _P, _P, _I64, _P, _P, _P],

@@ -31,6 +31,7 @@
 #include "iris_render.h"
 #include "iris_deflate.h"
 #include "iris_batch.h"
+#include "iris_optim.h"
 
 using namespace iris;
 
@@ -420,6 +421,63 @@ extern "C" IRIS_API int iris_ngp_set_params_dev(iris_ngp* g, const float* params
     const int64_t n8 = n_params / 8;
     hipLaunchKernelGGL(ngp_params_cast_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, (const float4*)params_dev, n8, (_Float16*)g->d_w.p, (_Float16*)g->d_grid.p);
     HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->last_use.ev, st));
+    g->last_stream = st; g->used = true;
+    return IRIS_OK;
+    API_END
+}
+// ---- the optimizer step (iris_optim.h): torch.optim.Adam's arithmetic, the scalars formed in double and rounded to float once
+static int adam_scalars(const char* who, int64_t n, int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay, AdamScalars& s) {
+    const std::string w(who);
+    if (n < 0) return fail(IRIS_ERR_ARG, w + ": n must not be negative");
+    if (step < 1) return fail(IRIS_ERR_ARG, w + ": step counts from 1 (got " + std::to_string(step) + ")");
+    if (!std::isfinite(lr) || !(lr > 0.0)) return fail(IRIS_ERR_ARG, w + ": lr must be positive and finite");
+    if (!std::isfinite(eps) || !(eps > 0.0)) return fail(IRIS_ERR_ARG, w + ": eps must be positive and finite");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(IRIS_ERR_ARG, w + ": the betas must lie in [0, 1)");
+    if (!std::isfinite(weight_decay) || !(weight_decay >= 0.0)) return fail(IRIS_ERR_ARG, w + ": weight_decay must be finite and not negative");
+    s.w1 = (float)(1.0 - beta1);
+    s.w2 = (float)(1.0 - beta2);
+    s.beta2 = (float)beta2;
+    s.step_size = (float)(lr / (1.0 - std::pow(beta1, (double)step)));
+    s.bc2 = (float)std::sqrt(1.0 - std::pow(beta2, (double)step));
+    s.eps = (float)eps;
+    s.wd = (float)weight_decay;
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t step, double lr, double beta1,
+                                       double beta2, double eps, double weight_decay, iris_stream_t stream) {
+    API_BEGIN
+    AdamScalars s{};
+    if (int rc = adam_scalars("iris_adam_step", n, step, lr, beta1, beta2, eps, weight_decay, s)) return rc;
+    if (n == 0) return IRIS_OK;
+    if (!param || !grad || !exp_avg || !exp_avg_sq) return fail(IRIS_ERR_ARG, "iris_adam_step: null pointer");
+    const uintptr_t bits = (uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq;
+    if (bits % 4) return fail(IRIS_ERR_ARG, "iris_adam_step: the buffers must be 4-byte aligned");
+    const int64_t n4 = bits % 16 ? 0 : n / 4;            // the 16-byte body; the scalar kernel takes the rest (everything when a buffer is not 16-byte aligned)
+    if (n4 > 0)
+        if (int rc = launch1d(adam_vec4_kernel, n4, 2048, stream, (float4*)param, (const float4*)grad, (float4*)exp_avg, (float4*)exp_avg_sq, n4, s)) return rc;
+    if (n4 * 4 < n)
+        if (int rc = launch1d(adam_scalar_kernel, n - n4 * 4, 2048, stream, param, grad, exp_avg, exp_avg_sq, n4 * 4, n, s)) return rc;
+    return IRIS_OK;
+    API_END
+}
+extern "C" IRIS_API int iris_ngp_adam_step(iris_ngp* g, float* params_dev, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n_params, int64_t step,
+                                           double lr, double beta1, double beta2, double eps, double weight_decay, iris_stream_t stream) {
+    API_BEGIN
+    if (!g || !params_dev || !grad || !exp_avg || !exp_avg_sq) return fail(IRIS_ERR_ARG, "iris_ngp_adam_step: bad arguments");
+    if (n_params != (int64_t)kNgpMlpParams + (int64_t)g->n_entries * 2)
+        return fail(IRIS_ERR_ARG, "iris_ngp_adam_step: mlp.params has " + std::to_string(n_params) + " entries, the NGPBRDF configuration has " + std::to_string(iris_ngp_n_params()));
+    AdamScalars s{};
+    if (int rc = adam_scalars("iris_ngp_adam_step", n_params, step, lr, beta1, beta2, eps, weight_decay, s)) return rc;
+    if (((uintptr_t)params_dev | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16)
+        return fail(IRIS_ERR_ARG, "iris_ngp_adam_step: params_dev, grad, exp_avg and exp_avg_sq must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(g->device));
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lock(g->mu);
+    if (g->used && g->last_stream != st) HIP_TRY(hipStreamWaitEvent(st, g->last_use.ev, 0));      // a forward in flight on another stream still reads the old half copy
+    const int64_t n8 = n_params / 8;
+    if (int rc = launch1d(ngp_adam_kernel, n8, 2048, stream, (float4*)params_dev, (const float4*)grad, (float4*)exp_avg, (float4*)exp_avg_sq, n8, s,
+                          (_Float16*)g->d_w.p, (_Float16*)g->d_grid.p)) return rc;
     HIP_TRY(hipEventRecord(g->last_use.ev, st));
     g->last_stream = st; g->used = true;
     return IRIS_OK;

@@ -252,6 +252,28 @@ class NGPBRDF(BaseBRDF):
         self._native = L.Native(h, L.lib().iris_ngp_destroy, idx, (L.tensor_key(),))      # (the empty key: the parameters are not in yet)
         return self._native
 
+    def adam_step_(self, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        """One torch.optim.Adam step of `mlp.params`, in place, which also writes the handle's half copy of the new parameters in the same pass
+        (iris_ngp_adam_step): the next forward neither runs the cast kernel nor re-creates the handle.  grad, exp_avg, exp_avg_sq: float32, contiguous, on
+        the parameters' device, of their length (exp_avg and exp_avg_sq are updated in place); step counts from 1.  What iris_amd.utils.optim.FusedAdam
+        calls for a parameter of one of its `networks`; the refresh path (torch.optim.Adam, then a forward) stays as it is."""
+        p = self.mlp.params
+        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+            raise L.IrisError("NGPBRDF.adam_step_: mlp.params must be float32, contiguous and on a HIP device (net.to(device))")
+        for name, t in (("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+            if not torch.is_tensor(t) or t.device != p.device or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
+                raise L.IrisError(f"NGPBRDF.adam_step_: {name} must be a contiguous float32 tensor of {p.numel()} entries on {p.device}")
+        idx = p.device.index
+        n = self._native
+        if n.ptr is None or n.device != idx:
+            n = self._create(None, p.numel(), idx)
+        with torch.cuda.device(idx):
+            L.check(L.lib().iris_ngp_adam_step(n.ptr, L.ptr(p), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), p.numel(), int(step), float(lr),
+                                               float(betas[0]), float(betas[1]), float(eps), float(weight_decay), L.stream()))
+        torch.autograd.graph.increment_version(p)              # an in-place write, as far as autograd and every tensor_key are concerned
+        n.keys[0] = L.tensor_key(p)                            # ... and the handle already holds the new values
+        return self
+
     def _run(self, pos):
         N, dev = pos.shape[0], pos.device
         albedo = torch.empty(N, 3, device=dev); rough = torch.empty(N, device=dev); metal = torch.empty(N, device=dev)
