@@ -236,6 +236,10 @@ static inline v3 angle2xyz_spec(float theta, float phi) {
     if (g_undo & 4) { sp = sinf(phi); cp = cosf(phi); } else spec_sincos(phi, &sp, &cp);
     return t_normalize(v3_make(st * cp, st * sp, ct));
 }
+/* angle2xyz on its own (tests/test_brdf_ref64_cpu.py): mode 0 the libm form, mode 1 the samplers' specified sincos (theta in [0, pi/2], phi in [0, 2 pi]) */
+ORC_API void orc_angle2xyz(const float *theta, const float *phi, int64_t B, float *out) {
+    for (int64_t i = 0; i < B; ++i) v3_st(out + i * 3, g_mode == 1 ? angle2xyz_spec(theta[i], phi[i]) : angle2xyz(theta[i], phi[i]));
+}
 
 /* utils/ops.py:85-96 double_sided(V,N) (in place on N) */
 ORC_API void orc_double_sided(const float *V, float *N, int64_t B) {
@@ -343,7 +347,10 @@ ORC_API void orc_lerp_specular(const float *spec, const float *rough, int64_t B,
         /* (roughness-r_min)/(r_max-r_min)*(r_num-1); r_max-r_min is a python double 0.98 cast to f32 */
         float r = (rough[i] - 0.02f) / (float)(1.0 - 0.02) * (float)(R - 1);
         int64_t r1 = (int64_t)ceilf(r), r0 = (int64_t)floorf(r);
-        float w = r - (float)r0;
+        float w = r - floorf(r);
+        /* a roughness outside [0.02, 1] makes the reference's gather raise; the HIP kernel keeps both indices inside the table (the end level), and so does this */
+        r1 = r1 < 0 ? 0 : r1 > R - 1 ? R - 1 : r1;
+        r0 = r0 < 0 ? 0 : r0 > R - 1 ? R - 1 : r0;
         for (int c = 0; c < 3; ++c) {
             float s0 = spec[(i * R + r0) * 3 + c], s1 = spec[(i * R + r1) * 3 + c];
             out[i * 3 + c] = s0 * (1.f - w) + s1 * w;

@@ -101,6 +101,20 @@ def get_normal_space(normal):
     return out
 
 
+def angle2xyz(theta, phi):
+    theta = _f32(theta).reshape(-1); phi = _f32(phi).reshape(-1); B = theta.shape[0]
+    out = np.empty((B, 3), np.float32)
+    lib().orc_angle2xyz(_p(theta), _p(phi), C.c_int64(B), _p(out))
+    return out
+
+
+def spec_asin_acos(x, acos=False):
+    """the kernels' specified asin / acos on [0, 1] (the same in both modes)"""
+    x = _f32(x).reshape(-1); out = np.empty_like(x)
+    lib().orc_spec_asin_acos(_p(x), C.c_int64(x.shape[0]), C.c_int(int(acos)), _p(out))
+    return out
+
+
 def double_sided(V, N):
     V = _f32(V); N = _f32(N).copy()
     lib().orc_double_sided(_p(V), _p(N), C.c_int64(N.shape[0]))
