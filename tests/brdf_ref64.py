@@ -31,6 +31,8 @@ TWO_PI_F = F32(2 * np.pi)
 PIO2_F = F32(np.pi / 2)
 TOP = F32(1.0 - 2.0 ** -24)                       # the largest value torch.rand returns
 CLAMP = F32(1e-4)
+F0 = F32(0.04)
+ALPHA_T = F32                                     # the dtype alpha^2 = r^4 is formed in (float32: what everybody forms it in)
 ROUGH_LEVELS = tuple(F32(r) for r in (0.02, 0.03, 0.05, 0.1, 0.216, 0.412, 0.608, 0.804, 1.0))
 B = 1 << 15
 GRID = (0.0, 2.0 ** -40, 2.0 ** -24, 0.125, float(np.nextafter(F32(0.25), F32(0))), 0.25, 0.375, 0.5, 0.625, 0.75, 0.875, float(TOP))
@@ -70,7 +72,7 @@ def _to_world(l, t, b, n):
 
 def alpha2(rough32):
     """alpha^2 = r^4 of D_GGX and of the sampler, in the float32 products everybody forms it with"""
-    r = np.asarray(rough32, F32)
+    r = np.asarray(rough32, ALPHA_T)
     a = r * r
     return a * a
 
@@ -120,7 +122,7 @@ def _lobe(c, rough32, T, dden):
     """utils/ops.py:46-82 on relu(c): D_GGX (its denominator shifted by dden), the GGX pdf, G_Smith, (1 - VoH)^5"""
     c = np.maximum(c, T(0))
     NoL, NoV, VoH, NoH = c[:, 0], c[:, 1], c[:, 2], c[:, 3]
-    r, a2, pi = np.asarray(rough32, F32).astype(T), alpha2(rough32).astype(T), T(PI_F)
+    r, a2, pi = np.asarray(rough32, ALPHA_T).astype(T), alpha2(rough32).astype(T), T(PI_F)
     den = NoH * NoH * (a2 - T(1)) + T(1) + np.asarray(dden, T)
     with np.errstate(divide="ignore", invalid="ignore"):       # (a float32 den can round to 0 at r = 0.02: D = inf, as in the reference)
         D = a2 / (pi * den * den)
@@ -152,7 +154,7 @@ def f_brdf(c, rough32, albedo32, metal32, T=np.float64, dden=0.0):
     albedo, metal = albedo32.astype(T), metal32.astype(T)[:, None]
     om = T(1) - metal
     kd = albedo * om
-    ks = T(F32(0.04)) * om + albedo * metal
+    ks = T(F0) * om + albedo * metal
     pdf = T(0.5) * pdf_spec + T(0.5) * (NoL / pi)
     F = ks + (T(1) - ks) * x5[:, None]
     brdf = kd / pi * NoL[:, None] + (D * G)[:, None] * F / T(4) * NoL[:, None]
@@ -202,6 +204,20 @@ def lerp_specular(spec32, rough32, T=np.float64):
     i = np.arange(spec32.shape[0])
     a, b, w = spec32[i, r0].astype(T), spec32[i, r1].astype(T), w.astype(T)[:, None]
     return a * (T(1) - w) + b * w, 3 * U * (np.abs(a).astype(np.float64) * (1 - w) + np.abs(b) * w)
+
+
+class float64_constants:
+    """with float64_constants(): the formulas above with pi, 0.04, the 1e-4 clamp and alpha^2 in double -- what the reference's own Python computes when it
+    is run in float64 (tests/test_pt_stage_ref64_cpu.py holds the restatement to such a run); outside it they are the float32 constants of a float32 run"""
+
+    def __enter__(self):
+        global PI_F, CLAMP, F0, ALPHA_T
+        self.prev = (PI_F, CLAMP, F0, ALPHA_T)
+        PI_F, CLAMP, F0, ALPHA_T = np.pi, 1e-4, 0.04, np.float64
+
+    def __exit__(self, *a):
+        global PI_F, CLAMP, F0, ALPHA_T
+        PI_F, CLAMP, F0, ALPHA_T = self.prev
 
 
 # ============================================================================================================ the float32 run of the restatement
