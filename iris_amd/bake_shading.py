@@ -5,7 +5,6 @@ kernel launch each: uniforms, BRDF sampling, secondary-ray traversal, emitter / 
 mean over spp never leave the chip.  ``bake_view`` is one iteration of the reference's per-view loops
 (:93-131 and :149-204) and returns the 13 pre-denoise maps; ``main`` keeps the reference's CLI.
 """
-import math
 import os
 import time
 
@@ -339,11 +338,9 @@ class MapWriter:
         self.pool.shutdown()
 
 
-def main(argv=None):
+def build_parser():
     from argparse import ArgumentParser
-    from .model.emitter import SLFEmitter
-    from .utils import cameras, exr
-    from .utils.path_tracing import load_scene
+    from .utils import stage
     parser = ArgumentParser(description="bake diffuse / specular shading maps (MI355X)")
     parser.add_argument("--dataset_root", type=str, help="dataset root")
     parser.add_argument("--scene", type=str, required=True, help="dataset folder")
@@ -354,57 +351,35 @@ def main(argv=None):
     parser.add_argument("--ldr_img_dir", type=str, default=None)       # accepted for compatibility; bake never reads images
     parser.add_argument("--res_scale", type=float, default=1.0)
     # additions (defaults reproduce the reference)
-    parser.add_argument("--cameras", type=str, default=None, help="generic camera JSON instead of the dataset's own camera files")
+    stage.add_common_options(parser, "cameras")
     parser.add_argument("--img_hw", type=int, nargs=2, default=None)
     parser.add_argument("--spp_diffuse", type=int, default=SPP_DIFFUSE)
     parser.add_argument("--spps_specular", type=int, nargs=N_ROUGHNESS, default=SPPS_SPECULAR)
-    parser.add_argument("--seed", type=int, default=0)
-    parser.add_argument("--compression", type=str, default="zip", choices=["none", "zips", "zip"])
-    parser.add_argument("--exr_encoder", type=str, default="host", choices=["host", "device"],
-                        help="where ZIP / ZIPS deflate runs: host (zlib on the writer threads) or device (GPU kernels); the pixels are the same")
+    stage.add_common_options(parser, "seed", "compression", "exr_encoder",
+                             exr_encoder="where ZIP / ZIPS deflate runs: host (zlib on the writer threads) or device (GPU kernels); the pixels are the same")
     parser.add_argument("--overwrite", action="store_true", help="re-bake views whose 13 files already exist")
-    parser.add_argument("--denoise", type=str, default="atrous", choices=["atrous", "none"],
-                        help="atrous: guided a-trous filter in place of the reference's OptiX denoiser (:129, :198-200); none: raw Monte-Carlo maps")
-    args = parser.parse_args(argv)
+    stage.add_common_options(parser, "denoise", denoise="atrous: guided a-trous filter in place of the reference's OptiX denoiser (:129, :198-200); none: raw Monte-Carlo maps")
+    return parser
+
+
+def main(argv=None):
+    from .model.emitter import SLFEmitter
+    from .utils import cameras, stage
+    from .utils.path_tracing import load_scene
+    args = build_parser().parse_args(argv)
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if not torch.cuda.is_available():
-        raise L.IrisError("bake_shading needs a HIP device; there is no CPU path")
-    torch.cuda.set_device(local_rank)
-    device = torch.device("cuda", local_rank)
-
-    if args.dataset in ("synthetic", "real"):
-        mesh_path = os.path.join(args.scene, "scene.obj")
-    elif args.dataset == "scannetpp":
-        mesh_path = os.path.join(args.dataset_root, "data", args.scene, "scans", "scene.ply")
-    else:
-        mesh_path = os.path.join(args.scene, "scene.obj") if os.path.exists(os.path.join(args.scene, "scene.obj")) else os.path.join(args.scene, "scene.ply")
-    assert os.path.exists(mesh_path), "mesh not found: " + mesh_path
-    scene = load_scene(mesh_path, device=device)
-
-    hw = tuple(args.img_hw) if args.img_hw else None
-    if args.cameras:
-        img_hw, views = cameras.load_generic(args.cameras, args.res_scale)
-    elif args.dataset == "synthetic":
-        img_hw, views = cameras.load_synthetic(args.scene, args.res_scale, hw)
-    elif args.dataset == "real":
-        img_hw, views = cameras.load_real(args.scene, args.res_scale, hw)
-    elif args.dataset == "scannetpp":                      # Scannetpp(args.dataset_root, args.scene, split='train', pixel=False, res_scale=args.res_scale)
-        img_hw, views = cameras.load_scannetpp(args.dataset_root, args.scene, args.res_scale)
-    else:
-        raise L.IrisError("--dataset {!r}: synthetic | real | scannetpp, or --cameras cameras.json".format(args.dataset))
+    device = stage.open_device(int(os.environ.get("LOCAL_RANK", "0")), "bake_shading")
+    root = args.dataset_root if args.dataset == "scannetpp" else args.scene       # the reference's flags: --scene is the scene's folder, but for scannetpp its id under --dataset_root
+    scene = load_scene(stage.mesh_path(args.dataset, root, args.scene), device=device)
+    img_hw, views = stage.load_views(args.dataset, root, args.scene, args.res_scale, cameras_json=args.cameras, img_hw=tuple(args.img_hw) if args.img_hw else None)
 
     emitter = SLFEmitter(args.emitter_path, args.slf_path)
-    for p in emitter.parameters():
-        p.requires_grad = False
+    stage.freeze(emitter)
     os.makedirs(os.path.join(args.output, "diffuse"), exist_ok=True)
     os.makedirs(os.path.join(args.output, "specular"), exist_ok=True)
 
-    denoiser = None
-    if args.denoise == "atrous":
-        from .utils.denoise import Denoiser
-        denoiser = Denoiser(img_hw[::-1], device)          # denoiser = mitsuba.OptixDenoiser(img_hw[::-1])   (:81)
+    denoiser = stage.make_denoiser(args.denoise, img_hw, device)
     writer = MapWriter(device, img_hw, args.compression, encoder=args.exr_encoder)
     start_time = time.time()
     rays = 0
@@ -422,7 +397,7 @@ def main(argv=None):
         rays += out["rays"]
         # 13 maps -> pinned host buffer on a side stream -> compressed and written by threads while the next view bakes (a 1080p ZIP map
         # costs ~1 s of CPU, the bake of the whole view 0.3 s of GPU)
-        writer.submit(files, torch.stack([out["diffuse"]] + [out[k][r] for r in range(N_ROUGHNESS) for k in ("specular0", "specular1")]).reshape(13, *img_hw, 3))
+        writer.submit(files, stage.stack_maps(out, img_hw))
     writer.close()
     torch.cuda.synchronize()
     dt = time.time() - start_time

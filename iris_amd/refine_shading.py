@@ -9,7 +9,6 @@ inference as HIP kernels (hash-grid gathers + the perceptron on the matrix cores
 a library call, `--material pkg.module:factory` on the command line (the factory is called with the (voxel_min, voxel_max) pair `NGPBRDF` is
 constructed from, and `--ckpt` is handed to it when given).
 """
-import importlib
 import math
 import os
 import time
@@ -83,31 +82,9 @@ def refine_view(scene, emitter, material_net, xs, ds, spp_diffuse=SPP_DIFFUSE, s
     return out
 
 
-def _load_material(spec, slf_path, ckpt):
-    """The material network: by default the reference's own -- NGPBRDF(mask['voxel_min'], mask['voxel_max']) with the checkpoint's 'material.' weights
-    (refine_shading.py:82-92) --, or, with --material pkg.module:factory, any callable position -> {'albedo','roughness','metallic'}."""
-    if not spec:
-        from .model.brdf import load_ngpbrdf
-        if not ckpt:
-            raise L.IrisError("refine_shading: --ckpt (the checkpoint holding the NGPBRDF weights, refine_shading.py:36,84) or --material pkg.module:factory is required")
-        mask = torch.load(slf_path, map_location="cpu")
-        return load_ngpbrdf(mask["voxel_min"], mask["voxel_max"], ckpt)
-    mod, _, attr = spec.partition(":")
-    factory = getattr(importlib.import_module(mod), attr or "material")
-    mask = torch.load(slf_path, map_location="cpu")
-    try:
-        return factory(mask["voxel_min"], mask["voxel_max"], ckpt) if ckpt else factory(mask["voxel_min"], mask["voxel_max"])
-    except TypeError:
-        return factory()
-
-
-def main(argv=None):
-    """python -m iris_amd.refine_shading --scene S --slf_path vslf.npz --emitter_path emitter.pth --output OUT --dataset synthetic|real|generic
-       --ckpt last.ckpt [--material pkg.module:factory]          (the reference's flags; --material replaces the NGPBRDF the reference hard-wires)"""
+def build_parser():
     import argparse
-    from .model.emitter import SLFEmitter
-    from .utils import cameras, exr
-    from .utils.path_tracing import load_scene
+    from .utils import stage
     parser = argparse.ArgumentParser(description=main.__doc__)
     parser.add_argument("--dataset_root", type=str, help="dataset root")
     parser.add_argument("--scene", type=str, required=True, help="dataset folder")
@@ -119,60 +96,43 @@ def main(argv=None):
     parser.add_argument("--ldr_img_dir", type=str, default=None)
     parser.add_argument("--res_scale", type=float, default=1.0)
     # additions (defaults reproduce the reference)
-    parser.add_argument("--material", type=str, default=None, help="pkg.module:factory returning material_net(position) -> {'albedo','roughness','metallic'} "
-                        "(default: the reference's NGPBRDF, loaded from --ckpt)")
-    parser.add_argument("--cameras", type=str, default=None, help="generic camera JSON instead of the dataset's own camera files")
+    stage.add_common_options(parser, "material", "cameras", material="pkg.module:factory returning material_net(position) -> {'albedo','roughness','metallic'} "
+                             "(default: the reference's NGPBRDF, loaded from --ckpt)")
     parser.add_argument("--img_hw", type=int, nargs=2, default=None)
     parser.add_argument("--spp_diffuse", type=int, default=SPP_DIFFUSE)
     parser.add_argument("--spp_specular", type=int, default=SPP_SPECULAR)
     parser.add_argument("--indir_depth", type=int, default=INDIR_DEPTH)
     parser.add_argument("--batch_rays", type=int, default=BATCH_RAYS, help="paths per integrator call (the reference: 10240*128)")
-    parser.add_argument("--seed", type=int, default=0)
-    parser.add_argument("--compression", type=str, default="zip", choices=["none", "zips", "zip"])
-    parser.add_argument("--exr_encoder", type=str, default="host", choices=["host", "device"],
-                        help="where ZIP / ZIPS deflate runs: host (zlib) or device (GPU kernels); the pixels are the same, so --resume does not key on it")
+    stage.add_common_options(parser, "seed", "compression", "exr_encoder",
+                             exr_encoder="where ZIP / ZIPS deflate runs: host (zlib) or device (GPU kernels); the pixels are the same, so --resume does not key on it")
     parser.add_argument("--overwrite", action="store_true", help="(accepted for symmetry with bake_shading; refining always overwrites, as the reference does)")
     parser.add_argument("--resume", action="store_true", help="skip the views a previous refine run with the same settings has completed (marked by a .refined sidecar)")
-    parser.add_argument("--denoise", type=str, default="atrous", choices=["atrous", "none"])
-    args = parser.parse_args(argv)
+    stage.add_common_options(parser, "denoise")
+    return parser
+
+
+def main(argv=None):
+    """python -m iris_amd.refine_shading --scene S --slf_path vslf.npz --emitter_path emitter.pth --output OUT --dataset synthetic|real|generic
+       --ckpt last.ckpt [--material pkg.module:factory]          (the reference's flags; --material replaces the NGPBRDF the reference hard-wires)"""
+    from .model.emitter import SLFEmitter
+    from .utils import cameras, stage
+    from .utils.path_tracing import load_scene
+    args = build_parser().parse_args(argv)
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if not torch.cuda.is_available():
-        raise L.IrisError("refine_shading needs a HIP device; there is no CPU path")
-    torch.cuda.set_device(local_rank)
-    device = torch.device("cuda", local_rank)
-    if args.dataset in ("synthetic", "real"):
-        mesh_path = os.path.join(args.scene, "scene.obj")
-    elif args.dataset == "scannetpp":
-        mesh_path = os.path.join(args.dataset_root, "data", args.scene, "scans", "scene.ply")
-    else:
-        mesh_path = os.path.join(args.scene, "scene.obj") if os.path.exists(os.path.join(args.scene, "scene.obj")) else os.path.join(args.scene, "scene.ply")
-    assert os.path.exists(mesh_path), "mesh not found: " + mesh_path
+    device = stage.open_device(int(os.environ.get("LOCAL_RANK", "0")), "refine_shading")
+    root = args.dataset_root if args.dataset == "scannetpp" else args.scene       # the reference's flags: --scene is the scene's folder, but for scannetpp its id under --dataset_root
+    mesh_path = stage.mesh_path(args.dataset, root, args.scene)
     scene = load_scene(mesh_path, device=device)
-    hw = tuple(args.img_hw) if args.img_hw else None
-    if args.cameras:
-        img_hw, views = cameras.load_generic(args.cameras, args.res_scale)
-    elif args.dataset == "synthetic":
-        img_hw, views = cameras.load_synthetic(args.scene, args.res_scale, hw)
-    elif args.dataset == "real":
-        img_hw, views = cameras.load_real(args.scene, args.res_scale, hw)
-    elif args.dataset == "scannetpp":                      # Scannetpp(args.dataset_root, args.scene, split='train', pixel=False, res_scale=args.res_scale)
-        img_hw, views = cameras.load_scannetpp(args.dataset_root, args.scene, args.res_scale)
-    else:
-        raise L.IrisError("--dataset {!r}: synthetic | real | scannetpp, or --cameras cameras.json".format(args.dataset))
+    img_hw, views = stage.load_views(args.dataset, root, args.scene, args.res_scale, cameras_json=args.cameras, img_hw=tuple(args.img_hw) if args.img_hw else None)
     emitter = SLFEmitter(args.emitter_path, args.slf_path)
-    material_net = _load_material(args.material, args.slf_path, args.ckpt)
+    material_net = stage.load_material(args.material, args.slf_path, args.ckpt)
     if isinstance(material_net, torch.nn.Module):
         material_net.to(device)
-        for p in material_net.parameters():
-            p.requires_grad = False
+    stage.freeze(material_net)
     os.makedirs(os.path.join(args.output, "diffuse"), exist_ok=True)
     os.makedirs(os.path.join(args.output, "specular"), exist_ok=True)
-    denoiser = None
-    if args.denoise == "atrous":
-        from .utils.denoise import Denoiser
-        denoiser = Denoiser(img_hw[::-1], device)
+    denoiser = stage.make_denoiser(args.denoise, img_hw, device)
     writer = MapWriter(device, img_hw, args.compression, encoder=args.exr_encoder)
     start_time = time.time()
     # The reference runs bake_shading and refine_shading on the SAME --output: the refined maps replace the bake's 13 files of every view in place
@@ -211,7 +171,7 @@ def main(argv=None):
             continue
         if os.path.exists(marker):
             os.remove(marker)
-        torch.manual_seed(args.seed * 1000003 + im_id); torch.cuda.manual_seed(args.seed * 1000003 + im_id)     # the integrators draw with torch.rand
+        stage.view_seed_torch(args.seed, im_id)
         xs, ds = cameras.view_rays(views[im_id], img_hw, device)
         out = refine_view(scene, emitter, material_net, xs, ds, args.spp_diffuse, args.spp_specular, args.indir_depth, batch_rays=args.batch_rays, denoiser=denoiser)
 
@@ -220,7 +180,7 @@ def main(argv=None):
             with open(tmp, "w") as fh:
                 json.dump({"run_key": run_key, "files": files_state(files)}, fh)
             os.replace(tmp, marker)
-        writer.submit(files, torch.stack([out["diffuse"]] + [out[k][r] for r in range(N_ROUGHNESS) for k in ("specular0", "specular1")]).reshape(13, *img_hw, 3), on_written=mark)
+        writer.submit(files, stage.stack_maps(out, img_hw), on_written=mark)
     writer.close()                                             # every file and every marker is on disk from here on
     torch.cuda.synchronize()
     print("[refine_shading] rank {}: {:.2f} s".format(rank, time.time() - start_time))

@@ -162,6 +162,7 @@ def write_metrics(path, psnr_list, ssim_list=None):
 def build_parser():
     """The reference's render.py arguments (render.py:57-71 + configs/config.py) that matter here; the trainers' options it also registers are accepted and ignored."""
     import argparse
+    from .utils import stage
     parser = argparse.ArgumentParser(description="python -m iris_amd.render: the reference's render.py on MI355X")
     parser.add_argument("--experiment_name", type=str, required=True)
     parser.add_argument("--checkpoint_path", type=str, default="./checkpoints")
@@ -180,131 +181,46 @@ def build_parser():
     parser.add_argument("--res_scale", type=float, default=1.0)
     parser.add_argument("--ldr_img_dir", type=str, default=None)
     parser.add_argument("--log_path", type=str, default="./logs")
-    for name, typ in (("batch_size", int), ("voxel_path", str), ("num_workers", int), ("dir_val", str), ("val_step", int), ("has_part", int), ("load_crf", int)):
-        parser.add_argument("--" + name, type=typ, default=None, help="(a trainer option of configs/config.py: accepted, unused)")
+    stage.add_ignored_trainer_options(parser)
     # additions (defaults reproduce the reference)
-    parser.add_argument("--material", type=str, default=None, help="pkg.module:factory returning material_net(position) -> {'albedo','roughness','metallic'} "
-                        "(default: the reference's NGPBRDF, loaded from the checkpoint's 'material.' entries)")
-    parser.add_argument("--cameras", type=str, default=None, help="generic camera JSON instead of the dataset's own camera files; a view may carry \"image\" (an EXR "
-                        "or, with PIL, PNG photograph in [0,1]) and \"exposure\"")
-    parser.add_argument("--emor_path", type=str, default=None, help="the EMoR basis file (default: crf/emor.txt under the working directory, as the reference)")
-    parser.add_argument("--denoise", type=str, default="atrous", choices=["atrous", "none"])
-    parser.add_argument("--compression", type=str, default="zip", choices=["none", "zips", "zip"])
+    stage.add_common_options(parser, "material", "cameras", "emor_path", "denoise", "compression", cameras=stage.COMMON_OPTIONS["cameras"]["help"] + "; a view may carry "
+                             "\"image\" (an EXR or, with PIL, PNG photograph in [0,1]) and \"exposure\"")
     parser.add_argument("--metrics", type=str, default="psnr", choices=["psnr", "psnr,ssim"], metavar="psnr | psnr,ssim", help="columns of rgb/metrics.txt: psnr (default), or psnr,ssim -- the "
                         "reference's Name, PSNR, SSIM file, SSIM evaluated on the device")
-    parser.add_argument("--seed", type=int, default=0)
-    parser.add_argument("--max_views", type=int, default=None)
+    stage.add_common_options(parser, "seed", "max_views")
     return parser
 
 
-def _load_state(path):
-    try:
-        return torch.load(path, map_location="cpu")["state_dict"]
-    except Exception:     # noqa  (a Lightning checkpoint: see model.brdf.load_ngpbrdf)
-        return torch.load(path, map_location="cpu", weights_only=False)["state_dict"]
-
-
-def _views(args):
-    """(img_hw, views) of the split; every view: camera + optional 'image' / 'exposure'"""
-    from .utils import cameras
-    name, path = args.dataset
-    if args.cameras:
-        import json
-        img_hw, views = cameras.load_generic(args.cameras, args.res_scale)
-        with open(args.cameras) as fh:
-            meta = json.load(fh)["views"]
-        for v, m in zip(views, meta):
-            v["image"], v["exposure"] = m.get("image"), float(m.get("exposure", 1.0))
-            if v["image"] and not os.path.isabs(v["image"]):
-                v["image"] = os.path.join(os.path.dirname(os.path.abspath(args.cameras)), v["image"])
-        return img_hw, views
-    if name == "real":
-        return cameras.load_real(path, args.res_scale, split=args.split)
-    if name == "scannetpp":
-        return cameras.load_scannetpp(path, args.scene, args.res_scale, split=args.split)
-    if name == "synthetic":
-        import json
-        with open(os.path.join(path, args.split, "transforms.json")) as fh:
-            meta = json.load(fh)
-        img_hw = cameras._img_hw_from_exr(os.path.join(path, args.split, "Image", "000_0001.exr"), args.res_scale)
-        focal = float(0.5 * img_hw[1] / np.tan(0.5 * meta["camera_angle_x"]))
-        return img_hw, [{"kind": "synthetic", "focal": focal, "c2w": np.asarray(f["transform_matrix"], np.float32)[:3, :4]} for f in meta["frames"]]
-    raise L.IrisError("--dataset {!r}: synthetic | real | scannetpp, or --cameras cameras.json".format(name))
-
-
-def _view_rays(view, img_hw, device):
-    """rays with differentials, as the reference's datasets give them with ray_diff=True"""
-    from .utils.dataset import real_ldr, synthetic_ldr
-    if view["kind"] == "synthetic":
-        return synthetic_ldr.get_rays(synthetic_ldr.get_ray_directions(img_hw[0], img_hw[1], view["focal"]), view["c2w"], focal=view["focal"], device=device)
-    return real_ldr.to_world(real_ldr.get_direction(view["K"], img_hw), view["c2w"], True, view["K"], device=device)
-
-
-def _read_image(path, img_hw):
-    if path.lower().endswith(".exr"):
-        from .utils.exr import read_exr
-        a = read_exr(path)
-    else:
-        from PIL import Image
-        a = np.asarray(Image.open(path).convert("RGB"), np.float32) / 255.0
-    if a.shape[:2] != tuple(img_hw):
-        raise L.IrisError(f"{path}: {a.shape[:2]} pixels, the view has {tuple(img_hw)}")
-    return a
-
-
 def main(argv=None):
-    from .model.crf import EmorCRF
     from .model.emitter import SLFEmitter
-    from .refine_shading import _load_material
+    from .utils import cameras, stage
     from .utils.path_tracing import load_scene
     args = build_parser().parse_args(argv)
     if args.light_type != "slf":
         raise L.IrisError("--light_type area (AreaEmitter, relighting) is not part of this stage: only slf")
-    if not torch.cuda.is_available():
-        raise L.IrisError("render needs a HIP device; there is no CPU path")
-    torch.cuda.set_device(args.device)
-    device = torch.device("cuda", args.device)
+    device = stage.open_device(args.device, "render")
     print("==========================\nExp: {}\nOutput: {}\nSplit: {}\n==========================".format(args.experiment_name, args.output_path, args.split))
     name, path = args.dataset
-    if name == "scannetpp":
-        mesh_path = os.path.join(path, "data", args.scene, "scans", "scene.ply")
-    else:
-        mesh_path = os.path.join(path, "scene.obj")
-        if not os.path.exists(mesh_path) and os.path.exists(os.path.join(path, "scene.ply")):
-            mesh_path = os.path.join(path, "scene.ply")
-    assert os.path.exists(mesh_path), "mesh not found: " + mesh_path
-    scene = load_scene(mesh_path, device=device)
-    img_hw, views = _views(args)
+    scene = load_scene(stage.mesh_path(name, path, args.scene), device=device)
+    img_hw, views = stage.load_views(name, path, args.scene, args.res_scale, split=args.split, cameras_json=args.cameras, extras=True)
     if args.max_views is not None:
         views = views[:args.max_views]
 
     ckpt = os.path.join(args.checkpoint_path, args.experiment_name, args.ckpt)
-    material_net = _load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), ckpt)        # NGPBRDF(mask['voxel_min'], mask['voxel_max']) + 'material.' (:110-119)
+    material_net = stage.load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), ckpt)        # NGPBRDF(mask['voxel_min'], mask['voxel_max']) + 'material.' (:110-119)
     if isinstance(material_net, torch.nn.Module):
         material_net.to(device)
     emitter_net = SLFEmitter(os.path.join(args.emitter_path, "emitter.pth"), os.path.join(args.emitter_path, "vslf_0.npz")).to(device)      # :123-124
-    crf_state = {k.replace("model_crf.", ""): v for k, v in _load_state(ckpt).items() if "model_crf." in k}                            # :130-135
-    if args.emor_path is None and not os.path.isfile(os.path.join(os.getcwd(), "crf", "emor.txt")) and "f0" in crf_state and "basis" in crf_state:
-        model_crf = EmorCRF.from_arrays(crf_state["f0"][0], crf_state["basis"])      # no EMoR file at hand: the curves are buffers of the module, so the checkpoint carries them
-    else:
-        model_crf = EmorCRF(args.crf_basis, emor_path=args.emor_path)
-    model_crf.load_state_dict(crf_state)
-    model_crf.to(device)
-    for m in (material_net, emitter_net, model_crf):
-        if isinstance(m, torch.nn.Module):
-            for p in m.parameters():
-                p.requires_grad = False
-    denoiser = None
-    if args.denoise == "atrous":
-        from .utils.denoise import Denoiser
-        denoiser = Denoiser(img_hw[::-1], device)
+    model_crf = stage.load_crf(stage.read_checkpoint(ckpt)["model_crf"], args.crf_basis, args.emor_path, device)                            # :130-135
+    stage.freeze(material_net, emitter_net, model_crf)
+    denoiser = stage.make_denoiser(args.denoise, img_hw, device)
     metrics = tuple(args.metrics.split(","))
     psnr_list, ssim_list = [], []
     t0 = time.time()
     for i, view in enumerate(views):
-        torch.manual_seed(args.seed * 1000003 + i); torch.cuda.manual_seed(args.seed * 1000003 + i)
-        rays = _view_rays(view, img_hw, device)
-        gt = _read_image(view["image"], img_hw) if view.get("image") else None
+        stage.view_seed_torch(args.seed, i)
+        rays = cameras.view_rays(view, img_hw, device, ray_diff=True)
+        gt = stage.read_image(view["image"], img_hw) if view.get("image") else None
         out = render_view(scene, emitter_net, material_net, model_crf, rays, img_hw, args.SPP, args.spp, args.indir_depth, exposure=float(view.get("exposure", 1.0)),
                           gt=gt, denoise=denoiser is not None, denoiser=denoiser, metrics=metrics)
         write_view(args.output_path, args.split, i, out, args.compression)

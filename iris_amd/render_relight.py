@@ -101,6 +101,7 @@ def save_image(image, path):
 def build_parser():
     """The reference's render_relight.py arguments (render_relight.py:117-131 + configs/config.py); the trainers' options are accepted and ignored."""
     import argparse
+    from .utils import stage
     parser = argparse.ArgumentParser(description="python -m iris_amd.render_relight: the reference's render_relight.py on MI355X")
     parser.add_argument("--experiment_name", type=str, required=True)
     parser.add_argument("--mode", type=str, default="train_val", choices=["train_val", "traj"])
@@ -121,77 +122,46 @@ def build_parser():
     parser.add_argument("--crf_basis", type=int, default=3)
     parser.add_argument("--res_scale", type=float, default=1.0)
     parser.add_argument("--ldr_img_dir", type=str, default=None)
-    for name, typ in (("batch_size", int), ("voxel_path", str), ("num_workers", int), ("dir_val", str), ("val_step", int), ("has_part", int), ("load_crf", int)):
-        parser.add_argument("--" + name, type=typ, default=None, help="(a trainer option of configs/config.py: accepted, unused)")
+    stage.add_ignored_trainer_options(parser)
     # additions (defaults reproduce the reference)
-    parser.add_argument("--material", type=str, default=None, help="pkg.module:factory returning material_net(position) -> {'albedo','roughness','metallic'} "
-                        "(default: the reference's NGPBRDF, loaded from the checkpoint's 'material.' entries)")
-    parser.add_argument("--cameras", type=str, default=None, help="generic camera JSON instead of the dataset's own camera files (needed for --mode traj)")
-    parser.add_argument("--emor_path", type=str, default=None, help="the EMoR basis file (default: crf/emor.txt under the working directory, as the reference)")
-    parser.add_argument("--denoise", type=str, default="atrous", choices=["atrous", "none"])
-    parser.add_argument("--compression", type=str, default="zip", choices=["none", "zips", "zip"])
-    parser.add_argument("--seed", type=int, default=0)
-    parser.add_argument("--max_views", type=int, default=None)
+    stage.add_common_options(parser, "material", "cameras", "emor_path", "denoise", "compression", "seed", "max_views",
+                             cameras=stage.COMMON_OPTIONS["cameras"]["help"] + " (needed for --mode traj)")
     parser.add_argument("--keep_lights", type=float, default=0.0, help="0: the room's own lamps are switched off (absorbers); s > 0: they stay, their radiance times s")
     parser.add_argument("--sphere_subdiv", type=int, default=2, help="icosphere subdivisions of inserted spheres (2: 320 triangles)")
     return parser
 
 
 def main(argv=None):
-    from .model.crf import EmorCRF
-    from .refine_shading import _load_material
-    from .render import _load_state, _view_rays, _views
+    from .utils import cameras, stage
     from .utils.exr import write_exr
     args = build_parser().parse_args(argv)
     if args.mode == "traj" and not args.cameras:
         raise L.IrisError("--mode traj: the dataset's render trajectory (render_traj_c2w) is not loaded by this package; pass the views with --cameras cameras.json")
-    if not torch.cuda.is_available():
-        raise L.IrisError("render_relight needs a HIP device; there is no CPU path")
-    torch.cuda.set_device(args.device)
-    device = torch.device("cuda", args.device)
+    device = stage.open_device(args.device, "render_relight")
     print("==========================\nExp: {}\nMode: {}\nOutput: {}\nSplit: {}\n==========================".format(args.experiment_name, args.mode, args.output_path, args.split))
     name, path = args.dataset
-    if name == "scannetpp":
-        mesh_path = os.path.join(path, "data", args.scene, "scans", "scene.ply")
-    else:
-        mesh_path = os.path.join(path, "scene.obj")
-        if not os.path.exists(mesh_path) and os.path.exists(os.path.join(path, "scene.ply")):
-            mesh_path = os.path.join(path, "scene.ply")
-    assert os.path.exists(mesh_path), "mesh not found: " + mesh_path
-    verts, faces = load_mesh(mesh_path)
+    verts, faces = load_mesh(stage.mesh_path(name, path, args.scene))
     emitter_state = torch.load(os.path.join(args.emitter_path, "emitter.pth"), map_location="cpu")
     lights = LT.load_light_config(args.light_cfg)
-    img_hw, views = _views(args)
+    img_hw, views = stage.load_views(name, path, args.scene, args.res_scale, split=args.split, cameras_json=args.cameras, extras=True)
     if args.max_views is not None:
         views = views[:args.max_views]
     ckpt = os.path.join(args.checkpoint_path, args.experiment_name, args.ckpt)
-    material_net = _load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), ckpt)
+    material_net = stage.load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), ckpt)
     if isinstance(material_net, torch.nn.Module):
         material_net.to(device)
-    crf_state = {k.replace("model_crf.", ""): v for k, v in _load_state(ckpt).items() if "model_crf." in k}
-    if args.emor_path is None and not os.path.isfile(os.path.join(os.getcwd(), "crf", "emor.txt")) and "f0" in crf_state and "basis" in crf_state:
-        model_crf = EmorCRF.from_arrays(crf_state["f0"][0], crf_state["basis"])
-    else:
-        model_crf = EmorCRF(args.crf_basis, emor_path=args.emor_path)
-    model_crf.load_state_dict(crf_state)
-    model_crf.to(device)
-    for mod in (material_net, model_crf):
-        if isinstance(mod, torch.nn.Module):
-            for p in mod.parameters():
-                p.requires_grad = False
+    model_crf = stage.load_crf(stage.read_checkpoint(ckpt)["model_crf"], args.crf_basis, args.emor_path, device)
+    stage.freeze(material_net, model_crf)
     a = int(args.anti_aliasing)
     hw_aa = (img_hw[0] * a, img_hw[1] * a)
-    denoiser = None
-    if args.denoise == "atrous":
-        from .utils.denoise import Denoiser
-        denoiser = Denoiser(hw_aa[::-1], device)
+    denoiser = stage.make_denoiser(args.denoise, hw_aa, device)
     os.makedirs(args.output_path, exist_ok=True)
     relit, t0 = None, time.time()
     for i, view in enumerate(views):
-        torch.manual_seed(args.seed * 1000003 + i); torch.cuda.manual_seed(args.seed * 1000003 + i)
+        stage.view_seed_torch(args.seed, i)
         if relit is None or lights.disco is not None:                   # the scene is recomposed per view only for the disco ball (timestep = i)
             relit = RelitScene(LT.compose(verts, faces, emitter_state, lights.at(i), args.keep_lights, args.sphere_subdiv), device)
-        rays = _view_rays(scaled_view(view, a), hw_aa, device)
+        rays = cameras.view_rays(scaled_view(view, a), hw_aa, device, ray_diff=True)
         out = relight_view(relit, material_net, model_crf, rays, img_hw, args.SPP, args.spp, args.indir_depth, anti_aliasing=a, exposure=1.0,
                            denoise=denoiser is not None, denoiser=denoiser)
         save_image(out["rgb_ldr"], os.path.join(args.output_path, "{:0>5d}_rgb.png".format(i)))

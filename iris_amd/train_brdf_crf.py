@@ -22,6 +22,7 @@ import os
 import torch
 
 from . import _lib as L
+from .utils.stage import read_checkpoint, write_checkpoint          # (the checkpoint's layout lives with its other readers)
 
 # configs/config.py, option by option
 DEFAULT_OPTIONS = {
@@ -91,34 +92,6 @@ def make_optimizer(name, params, lr, weight_decay, networks):
     if name == "Ranger":
         raise L.IrisError("--optimizer Ranger is not built (the reference lists it but constructs only SGD and Adam): use Adam or SGD")
     raise L.IrisError(f"--optimizer {name}: expected Adam or SGD")
-
-
-# ---- checkpoints: plain functions over tensors and dicts
-def write_checkpoint(path, material_state, crf_state, optimizer_state, *, epoch, global_step, hyper_parameters):
-    """torch.save of {'state_dict': material.* and model_crf.* entries, 'optimizer_states': [optimizer_state], 'epoch', 'global_step',
-    'hyper_parameters'}: the part of a Lightning checkpoint the reference's loaders read (refine_shading.py:84-89, slf_refine.py:74-79,
-    train_brdf_crf.py:72-97 all take ['state_dict'] and filter on the two prefixes).  epoch: the number of completed epochs.  Emitter tensors are not
-    written: no consumer reads them from this file.  Written beside the target and renamed: a run that dies mid-write keeps the previous file."""
-    state = {"material." + k: v.detach().cpu() for k, v in material_state.items()}
-    state.update({"model_crf." + k: v.detach().cpu() for k, v in crf_state.items()})
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    tmp = str(path) + ".tmp"
-    torch.save({"state_dict": state, "optimizer_states": [optimizer_state], "epoch": int(epoch), "global_step": int(global_step),
-                "hyper_parameters": dict(hyper_parameters)}, tmp)
-    os.replace(tmp, path)
-
-
-def read_checkpoint(path):
-    """-> the saved dict plus 'material' and 'model_crf': the entries of 'state_dict' under each prefix, the prefix stripped (the reference's idiom).
-    Everything on the CPU.  A Lightning checkpoint of the reference loads too (its other entries are ignored by the callers here)."""
-    try:
-        ck = torch.load(path, map_location="cpu")
-    except Exception:     # noqa  (hyper-parameters and optimizer groups are plain Python objects: recent torch's tensors-only unpickler may refuse them)
-        ck = torch.load(path, map_location="cpu", weights_only=False)
-    out = dict(ck)
-    for prefix in ("material", "model_crf"):
-        out[prefix] = {k.replace(prefix + ".", ""): v for k, v in ck["state_dict"].items() if prefix + "." in k}
-    return out
 
 
 class BRDFCRFTrainer:
@@ -234,18 +207,11 @@ def parser():
     return ap
 
 
-def _voxel_range(path):
-    try:
-        mask = torch.load(path, map_location="cpu")
-    except Exception:     # noqa  (the file is a pickled dict with python floats beside its tensors)
-        mask = torch.load(path, map_location="cpu", weights_only=False)
-    return float(mask["voxel_min"]), float(mask["voxel_max"])
-
-
 def main(argv=None):
     args = parser().parse_args(argv)
     from .model.brdf import NGPBRDF
     from .model.crf import EmorCRF
+    from .utils import stage
     from .utils.dataset import PixelSet
     from .utils.dataset.files import load_training_files
     from .utils.path_tracing import load_scene
@@ -259,12 +225,10 @@ def main(argv=None):
         raise L.IrisError("--cache_dir is needed: the stage trains on the baked shadings (python -m iris_amd.bake_shading --output DIR)")
     print("train_brdf_crf: --val_step and --num_workers are accepted and ignored (no in-training validation images, no loader workers: the batches are "
           "made on the device)", flush=True)
-    device = torch.device("cuda", args.device)
-    torch.cuda.set_device(device)
+    device = stage.open_device(args.device, "train_brdf_crf")
     files = load_training_files(dataset, root, args.ldr_img_dir, has_part=args.has_part, res_scale=args.res_scale, cache_dir=args.cache_dir, device=device)
     scene = load_scene(files["mesh_path"], device=device)
-    vmin, vmax = _voxel_range(args.voxel_path)
-    material = NGPBRDF(vmin, vmax).init_parameters()
+    material = NGPBRDF(*stage.voxel_range(args.voxel_path)).init_parameters()
     model_crf = EmorCRF(dim=args.crf_basis)
     if args.ckpt_path:
         ck = read_checkpoint(args.ckpt_path)

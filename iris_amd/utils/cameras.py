@@ -1,11 +1,11 @@
-"""Camera lists (intrinsics + camera-to-world) of the train views for the bake CLI.
+"""Camera lists (intrinsics + camera-to-world) of a split's views for the command-line stages (utils/stage.py: load_views).
 
 Only the pose / intrinsics part of the reference's dataset classes is needed by bake_shading (images are never read there):
-  synthetic : {scene}/train/transforms.json, focal = 0.5 w / tan(0.5 camera_angle_x)          (utils/dataset/synthetic_ldr.py:129-150)
-  real      : {scene}/cam.txt (origin, lookat, up per view) + K_list.txt, train split          (utils/dataset/real_ldr.py:25-34,85-166)
+  synthetic : {scene}/{split}/transforms.json, focal = 0.5 w / tan(0.5 camera_angle_x)          (utils/dataset/synthetic_ldr.py:129-150)
+  real      : {scene}/cam.txt (origin, lookat, up per view) + K_list.txt, train or val split   (utils/dataset/real_ldr.py:25-34,85-166)
   scannetpp : {dataset_root}/data/{scene}/psdf/train_test_lists.json + transforms_all.json (nerfstudio layout: one shared
-              fl_x fl_y cx cy h w, per frame an OpenGL camera-to-world), train split                 (utils/dataset/scannetpp/dataset.py:78-141)
-  generic   : a JSON file {"img_hw":[H,W], "views":[{"K":3x3, "c2w":3x4}, ...]} (OpenCV convention)
+              fl_x fl_y cx cy h w, per frame an OpenGL camera-to-world), the split's list            (utils/dataset/scannetpp/dataset.py:78-141)
+  generic   : a JSON file {"img_hw":[H,W], "views":[{"K":3x3, "c2w":3x4}, ...]} (OpenCV convention); a view may carry "image" and "exposure"
 """
 import json
 import os
@@ -19,12 +19,12 @@ def _img_hw_from_exr(path, res_scale):
     return int(h["height"] * res_scale), int(h["width"] * res_scale)
 
 
-def load_synthetic(scene_dir, res_scale=1.0, img_hw=None):
-    root = os.path.join(scene_dir, "train")
+def load_synthetic(scene_dir, res_scale=1.0, img_hw=None, split="train"):
+    root = os.path.join(scene_dir, split)
     with open(os.path.join(root, "transforms.json")) as fh:
         meta = json.load(fh)
     if img_hw is None:
-        img_hw = _img_hw_from_exr(os.path.join(scene_dir, "train", "Image", "000_0001.exr"), res_scale)
+        img_hw = _img_hw_from_exr(os.path.join(root, "Image", "000_0001.exr"), res_scale)
     h, w = img_hw
     focal = float(0.5 * w / np.tan(0.5 * meta["camera_angle_x"]))
     views = [{"kind": "synthetic", "focal": focal, "c2w": np.asarray(f["transform_matrix"], np.float32)[:3, :4]} for f in meta["frames"]]
@@ -90,7 +90,8 @@ def load_scannetpp(dataset_root, scene_id, res_scale=1.0, split="train"):
     return img_hw, views
 
 
-def load_generic(json_path, res_scale=1.0):
+def load_generic(json_path, res_scale=1.0, extras=False):
+    """extras: every view also gets 'image' (the photograph's path or None; a relative one is taken from the JSON file's folder) and 'exposure' (default 1.0)"""
     with open(json_path) as fh:
         meta = json.load(fh)
     h, w = meta["img_hw"]
@@ -98,12 +99,19 @@ def load_generic(json_path, res_scale=1.0):
     for v in meta["views"]:
         K = np.asarray(v["K"], np.float32).reshape(3, 3).copy(); K[:2, :] *= res_scale
         views.append({"kind": "real", "K": K, "c2w": np.asarray(v["c2w"], np.float32).reshape(-1)[:12].reshape(3, 4)})
+        if extras:
+            image = v.get("image")
+            if image and not os.path.isabs(image):
+                image = os.path.join(os.path.dirname(os.path.abspath(json_path)), image)
+            views[-1].update(image=image, exposure=float(v.get("exposure", 1.0)))
     return (int(h * res_scale), int(w * res_scale)), views
 
 
-def view_rays(view, img_hw, device):
-    """Pixel-centre rays of one view on the GPU: (H*W,3) origins and unit directions."""
+def view_rays(view, img_hw, device, ray_diff=False):
+    """Pixel-centre rays of one view on the GPU: (H*W,3) origins and unit directions; with ray_diff the four tensors (origin, direction, dxdu, dydv) the
+    reference's datasets give with ray_diff=True."""
     from .dataset import real_ldr, synthetic_ldr
     if view["kind"] == "synthetic":
-        return synthetic_ldr.get_rays(synthetic_ldr.get_ray_directions(img_hw[0], img_hw[1], view["focal"]), view["c2w"], device=device)
-    return real_ldr.to_world(real_ldr.get_direction(view["K"], img_hw), view["c2w"], False, device=device)
+        return synthetic_ldr.get_rays(synthetic_ldr.get_ray_directions(img_hw[0], img_hw[1], view["focal"]), view["c2w"], focal=view["focal"] if ray_diff else None,
+                                      device=device)
+    return real_ldr.to_world(real_ldr.get_direction(view["K"], img_hw), view["c2w"], ray_diff, device=device)

@@ -17,6 +17,7 @@ import numpy as np
 from ... import _lib as L
 from .. import cameras
 from ..exr import read_exr, read_exr_header
+from ..stage import mesh_path
 
 
 def _open_png(path, img_hw):
@@ -96,4 +97,4 @@ def load_training_files(dataset, root, ldr_img_dir, *, has_part=0, res_scale=1.0
         if len(cache) != hw * len(views):
             raise L.IrisError(f"{cache_dir}: the maps hold {len(cache) // len(views)} pixels per view, the images {hw}")
     return dict(img_hw=img_hw, views=views, synthetic=synthetic, rgb=rgb, int_albedo=albedo, segmentation=seg, exposure=exposures, cache=cache,
-                mesh_path=os.path.join(root, "scene.obj"))
+                mesh_path=mesh_path(dataset, root))

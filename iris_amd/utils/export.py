@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from . import texture as T
+from . import stage, texture as T
 
 
 def build_parser():
@@ -36,8 +36,7 @@ def build_parser():
     parser.add_argument("--tex_res", type=int, default=2048)
     parser.add_argument("--chunk_size", type=int, default=160000)
     # additions
-    parser.add_argument("--material", type=str, default=None, help="pkg.module:factory returning material_net(position) -> {'albedo','roughness','metallic'} "
-                        "(default: the reference's NGPBRDF, loaded from the checkpoint's 'material.' entries)")
+    stage.add_common_options(parser, "material")
     parser.add_argument("--atlas", type=str, default="auto", choices=["auto", "files", "grid"],
                         help="files: <dir_save>/ft.npy + vt.npy; grid: the grid stand-in, saved there; auto: the files when both exist, else an error")
     parser.add_argument("--write_obj", action="store_true", help="also write mesh.obj and mesh.mtl (map_Kd albedo.png)")
@@ -62,7 +61,6 @@ def load_atlas(mode, dir_save, n_faces, tex_res):
 
 
 def main(argv=None):
-    from ..refine_shading import _load_material
     from .path_tracing import load_mesh
     args = build_parser().parse_args(argv)
     for name in ("mesh", "emitter_path", "dir_save"):
@@ -72,12 +70,8 @@ def main(argv=None):
     v_np, f_np = load_mesh(args.mesh)
     vt_np, ft_np = load_atlas(args.atlas, args.dir_save, f_np.shape[0], args.tex_res)
     T.check_inputs(vt_np, ft_np, v_np, f_np, args.tex_res)                 # before the device is touched
-    if not torch.cuda.is_available():
-        raise L.IrisError("export needs a HIP device; there is no CPU path")
-    device = torch.device(args.device)
-    device = torch.device("cuda", L.device_index(device))
-    torch.cuda.set_device(device)
-    material_net = _load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), args.ckpt)
+    device = stage.open_device(args.device, "export")
+    material_net = stage.load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), args.ckpt)
     if isinstance(material_net, torch.nn.Module):
         material_net.to(device)
     print(f"[INFO] mesh v={v_np.shape} f={f_np.shape} vt={vt_np.shape} ft={ft_np.shape}, texture {args.tex_res} x {args.tex_res}")

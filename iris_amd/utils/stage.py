@@ -1,0 +1,192 @@
+"""What the six command-line stages (bake_shading, refine_shading, render, render_relight, train_brdf_crf, utils.export) do before their first kernel
+launches: find the mesh, list the views, read checkpoints and the material network, build their parsers' shared options, open the device.  Plain functions;
+a stage's main() stays a linear script that calls them.  Everything down to the parser helpers is host code and imports without a GPU; the last five functions need one.
+"""
+import importlib
+import os
+
+import numpy as np
+import torch
+
+from .. import _lib as L
+from . import cameras
+
+
+# ---- pure host
+def mesh_path(dataset, root, scene=None):
+    """The mesh file of a scene.  root: for scannetpp the dataset root, for every other dataset the scene's own folder; scene: the scannetpp scene id.
+        scannetpp -> <root>/data/<scene>/scans/scene.ply
+        else      -> <root>/scene.obj, or <root>/scene.ply when there is no scene.obj
+    and IrisError when that file does not exist.  A superset of the rules the stages used to carry: bake and refine did not look for scene.ply under `synthetic`
+    and `real`, the training files named scene.obj unseen; the only inputs that behave differently are ones that failed before."""
+    if dataset == "scannetpp":
+        path = os.path.join(root, "data", scene, "scans", "scene.ply")
+    else:
+        path = os.path.join(root, "scene.obj")
+        if not os.path.exists(path):
+            path = os.path.join(root, "scene.ply")
+    if not os.path.exists(path):
+        raise L.IrisError("mesh not found: " + path)
+    return path
+
+
+def load_views(dataset, root, scene, res_scale, split="train", cameras_json=None, img_hw=None, extras=False):
+    """-> (img_hw, views) of a split.  root, scene: as mesh_path takes them.  cameras_json: a generic camera file that replaces the dataset's own (extras: its
+    views also carry 'image' and 'exposure', utils.cameras.load_generic); img_hw: the size of a synthetic / real scene that has no Image/000_0001.exr."""
+    if cameras_json:
+        return cameras.load_generic(cameras_json, res_scale, extras=extras)
+    if dataset == "synthetic":
+        return cameras.load_synthetic(root, res_scale, img_hw, split=split)
+    if dataset == "real":
+        return cameras.load_real(root, res_scale, img_hw, split=split)
+    if dataset == "scannetpp":                             # Scannetpp(dataset_root, scene, split=split, pixel=False, res_scale=res_scale)
+        return cameras.load_scannetpp(root, scene, res_scale, split=split)
+    raise L.IrisError("--dataset {!r}: synthetic | real | scannetpp, or --cameras cameras.json".format(dataset))
+
+
+def read_image(path, img_hw):
+    """a view's photograph, (H, W, 3) float32: an EXR as stored, anything else through PIL as RGB / 255"""
+    if path.lower().endswith(".exr"):
+        from .exr import read_exr
+        a = read_exr(path)
+    else:
+        from PIL import Image
+        a = np.asarray(Image.open(path).convert("RGB"), np.float32) / 255.0
+    if a.shape[:2] != tuple(img_hw):
+        raise L.IrisError(f"{path}: {a.shape[:2]} pixels, the view has {tuple(img_hw)}")
+    return a
+
+
+def load_pickled(path):
+    """torch.load on the CPU.  Recent torch's tensors-only unpickler refuses the plain Python objects a Lightning checkpoint carries (hyper-parameters, callback
+    states, optimizer groups); the reference loads its own files with the full unpickler, and so does the second attempt."""
+    try:
+        return torch.load(path, map_location="cpu")
+    except Exception:     # noqa
+        return torch.load(path, map_location="cpu", weights_only=False)
+
+
+def write_checkpoint(path, material_state, crf_state, optimizer_state, *, epoch, global_step, hyper_parameters):
+    """torch.save of {'state_dict': material.* and model_crf.* entries, 'optimizer_states': [optimizer_state], 'epoch', 'global_step',
+    'hyper_parameters'}: the part of a Lightning checkpoint the reference's loaders read (refine_shading.py:84-89, slf_refine.py:74-79,
+    train_brdf_crf.py:72-97 all take ['state_dict'] and filter on the two prefixes).  epoch: the number of completed epochs.  Emitter tensors are not
+    written: no consumer reads them from this file.  Written beside the target and renamed: a run that dies mid-write keeps the previous file."""
+    state = {"material." + k: v.detach().cpu() for k, v in material_state.items()}
+    state.update({"model_crf." + k: v.detach().cpu() for k, v in crf_state.items()})
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = str(path) + ".tmp"
+    torch.save({"state_dict": state, "optimizer_states": [optimizer_state], "epoch": int(epoch), "global_step": int(global_step),
+                "hyper_parameters": dict(hyper_parameters)}, tmp)
+    os.replace(tmp, path)
+
+
+def read_checkpoint(path):
+    """-> the saved dict plus 'material' and 'model_crf': the entries of 'state_dict' under each prefix, the prefix stripped (the reference's idiom).
+    Everything on the CPU.  A Lightning checkpoint of the reference loads too (its other entries are ignored by the callers here)."""
+    ck = load_pickled(path)
+    out = dict(ck)
+    for prefix in ("material", "model_crf"):
+        out[prefix] = {k.replace(prefix + ".", ""): v for k, v in ck["state_dict"].items() if prefix + "." in k}
+    return out
+
+
+def voxel_range(slf_path):
+    """(voxel_min, voxel_max) of a vslf.npz, the pair NGPBRDF is constructed from (refine_shading.py:82-83)"""
+    mask = load_pickled(slf_path)
+    return float(mask["voxel_min"]), float(mask["voxel_max"])
+
+
+def load_material(spec, slf_path, ckpt):
+    """The material network: by default the reference's own -- NGPBRDF(mask['voxel_min'], mask['voxel_max']) with the checkpoint's 'material.' weights
+    (refine_shading.py:82-92) --, or, with --material pkg.module:factory, any callable position -> {'albedo','roughness','metallic'}: the factory is called
+    as factory(voxel_min, voxel_max, ckpt) when a checkpoint is given, as factory(voxel_min, voxel_max) otherwise, and as factory() if it takes neither."""
+    if not spec:
+        from ..model.brdf import load_ngpbrdf
+        if not ckpt:
+            raise L.IrisError("refine_shading: --ckpt (the checkpoint holding the NGPBRDF weights, refine_shading.py:36,84) or --material pkg.module:factory is required")
+        return load_ngpbrdf(*voxel_range(slf_path), ckpt)
+    mod, _, attr = spec.partition(":")
+    factory = getattr(importlib.import_module(mod), attr or "material")
+    vmin, vmax = voxel_range(slf_path)
+    try:
+        return factory(vmin, vmax, ckpt) if ckpt else factory(vmin, vmax)
+    except TypeError:
+        return factory()
+
+
+def view_seed_torch(seed, i):
+    """seeds torch's CPU and GPU generators for view i of a run seeded with `seed`: the integrators draw with torch.rand.  (The bake's Philox key is
+    bake_shading.view_seed, a different thing.)"""
+    torch.manual_seed(seed * 1000003 + i)
+    torch.cuda.manual_seed(seed * 1000003 + i)
+
+
+# ---- parser helpers: the option groups more than one stage registers
+IGNORED_TRAINER_OPTIONS = (("batch_size", int), ("voxel_path", str), ("num_workers", int), ("dir_val", str), ("val_step", int), ("has_part", int), ("load_crf", int))
+COMMON_OPTIONS = {
+    "material": dict(type=str, default=None, help="pkg.module:factory returning material_net(position) -> {'albedo','roughness','metallic'} "
+                     "(default: the reference's NGPBRDF, loaded from the checkpoint's 'material.' entries)"),
+    "cameras": dict(type=str, default=None, help="generic camera JSON instead of the dataset's own camera files"),
+    "emor_path": dict(type=str, default=None, help="the EMoR basis file (default: crf/emor.txt under the working directory, as the reference)"),
+    "denoise": dict(type=str, default="atrous", choices=["atrous", "none"]),
+    "compression": dict(type=str, default="zip", choices=["none", "zips", "zip"]),
+    "seed": dict(type=int, default=0),
+    "max_views": dict(type=int, default=None),
+    "exr_encoder": dict(type=str, default="host", choices=["host", "device"]),
+}
+
+
+def add_ignored_trainer_options(parser):
+    """the options of configs/config.py that the reference's render scripts register and never read"""
+    for name, typ in IGNORED_TRAINER_OPTIONS:
+        parser.add_argument("--" + name, type=typ, default=None, help="(a trainer option of configs/config.py: accepted, unused)")
+
+
+def add_common_options(parser, *names, **help_texts):
+    """the named options of COMMON_OPTIONS, in the order given; help_texts[name] replaces that option's help text"""
+    for name in names:
+        parser.add_argument("--" + name, **dict(COMMON_OPTIONS[name], **({"help": help_texts[name]} if name in help_texts else {})))
+
+
+# ---- needs a device
+def open_device(index, stage):
+    """makes HIP device `index` (an ordinal, or a device name such as 'cuda' or 'cuda:1') the current one and returns it"""
+    if not torch.cuda.is_available():
+        raise L.IrisError(f"{stage} needs a HIP device; there is no CPU path")
+    if not isinstance(index, int):
+        index = L.device_index(index)
+    torch.cuda.set_device(index)
+    return torch.device("cuda", index)
+
+
+def load_crf(crf_state, crf_basis, emor_path, device):
+    """EmorCRF with the checkpoint's 'model_crf.' entries (render.py:130-135), on the device.  With no EMoR file at hand (no --emor_path, no crf/emor.txt under the
+    working directory) the curves come from the checkpoint: they are buffers of the module, so it carries them."""
+    from ..model.crf import EmorCRF
+    if emor_path is None and not os.path.isfile(os.path.join(os.getcwd(), "crf", "emor.txt")) and "f0" in crf_state and "basis" in crf_state:
+        model_crf = EmorCRF.from_arrays(crf_state["f0"][0], crf_state["basis"])
+    else:
+        model_crf = EmorCRF(crf_basis, emor_path=emor_path)
+    model_crf.load_state_dict(crf_state)
+    return model_crf.to(device)
+
+
+def freeze(*modules):
+    """requires_grad = False on every parameter; a material network that is a plain callable has none"""
+    for m in modules:
+        if isinstance(m, torch.nn.Module):
+            for p in m.parameters():
+                p.requires_grad = False
+
+
+def make_denoiser(kind, img_hw, device):
+    """--denoise: the a-trous filter for (H, W) images, or None"""
+    if kind != "atrous":
+        return None
+    from .denoise import Denoiser
+    return Denoiser(img_hw[::-1], device)                  # denoiser = mitsuba.OptixDenoiser(img_hw[::-1])   (bake_shading.py:81)
+
+
+def stack_maps(out, img_hw):
+    """the 13 maps of bake_view / refine_view as the (13, H, W, 3) tensor MapWriter.submit takes: diffuse, then specular0 and specular1 of each roughness level"""
+    return torch.stack([out["diffuse"]] + [out[k][r] for r in range(len(out["specular0"])) for k in ("specular0", "specular1")]).reshape(13, *img_hw, 3)

@@ -140,6 +140,45 @@ def test_refine_cli_writes_the_bake_file_set(tmp_path):
     assert len(m["files"]) == 13 and m["run_key"]
 
 
+def test_refine_cli_resume_renders_no_view(tmp_path, monkeypatch):
+    """The refine command line of test_refine_cli_writes_the_bake_file_set (same scene, cameras, material and arguments; no bake first: refining needs none),
+    then the same command with --resume: the markers of the first run are honoured through the shared stage setup (utils/stage.py), so refine_view is not
+    called once and none of the 13 files of either view is touched."""
+    from iris_amd import bake_shading as bs, refine_shading as rs
+    from iris_amd.model.slf import VoxelSLF
+    g = golden("bake_box.npz")
+    p = golden("pt_single.npz")
+    scene_dir = tmp_path / "scene"; scene_dir.mkdir()
+    with open(scene_dir / "scene.obj", "w") as fh:
+        for v in g["verts"]:
+            fh.write("v {} {} {}\n".format(*v))
+        for f in g["faces"]:
+            fh.write("f {} {} {}\n".format(*(f + 1)))
+    H, W = 12, 16
+    K = np.array([[0.8 * W, 0, W / 2.0], [0, 0.8 * W, H / 2.0], [0, 0, 1]], np.float32)
+    json.dump({"img_hw": [H, W], "views": [{"K": K.tolist(), "c2w": g["c2w"].tolist()}] * 2}, open(tmp_path / "cams.json", "w"))
+    slf = VoxelSLF(torch.from_numpy(g["slf_mask"]), float(g["voxel_min"]), float(g["voxel_max"]))
+    slf.radiance[:] = torch.from_numpy(g["slf_radiance"])
+    ep, sp = str(tmp_path / "emitter.pth"), str(tmp_path / "vslf.npz")
+    torch.save({"is_emitter": torch.from_numpy(g["is_emitter"]), "emitter_vertices": torch.from_numpy(p["emitter_vertices"]), "emitter_area": torch.from_numpy(g["emitter_area"]),
+                "emitter_normal": torch.zeros(int(g["is_emitter"].sum()), 3), "emitter_radiance": torch.from_numpy(g["emitter_radiance"])}, ep)
+    torch.save({"mask": torch.from_numpy(g["slf_mask"]), "voxel_min": float(g["voxel_min"]), "voxel_max": float(g["voxel_max"]), "weight": slf.state_dict()}, sp)
+    out = str(tmp_path / "out")
+    argv = ["--scene", str(scene_dir), "--slf_path", sp, "--emitter_path", ep, "--output", out, "--dataset", "generic", "--cameras", str(tmp_path / "cams.json"),
+            "--material", "stub_material:material", "--spp_diffuse", "8", "--spp_specular", "4", "--indir_depth", "2", "--seed", "2"]
+    calls = []
+    refine_view = rs.refine_view
+    monkeypatch.setattr(rs, "refine_view", lambda *a, **k: calls.append(1) or refine_view(*a, **k))
+    rs.main(argv)
+    assert len(calls) == 2
+    files = [f for im_id in (0, 1) for f in bs.output_files(out, im_id)]
+    assert len(files) == 26 and all(os.path.exists(os.path.join(out, "diffuse", "{:03d}.refined".format(i))) for i in (0, 1))
+    mtimes = [os.stat(f).st_mtime_ns for f in files]
+    rs.main(argv + ["--resume"])
+    assert len(calls) == 2                                 # no view rendered
+    assert [os.stat(f).st_mtime_ns for f in files] == mtimes
+
+
 def test_refine_cli_runs_from_a_checkpoint(tmp_path):
     """`python -m iris_amd.refine_shading --ckpt last.ckpt` WITHOUT --material: the material network is the reference's NGPBRDF, built from the SLF file's
     (voxel_min, voxel_max) and the checkpoint's 'material.' weights exactly as refine_shading.py:82-92 does.  (Random parameters: no checkpoint of the reference

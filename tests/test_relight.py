@@ -538,7 +538,7 @@ def test_cli_main_writes_the_views(tmp_path):
     import json
     from iris_amd import render_relight as RR
     from iris_amd.model.crf import EmorCRF
-    from iris_amd.render import _view_rays
+    from iris_amd.utils.cameras import view_rays
     from iris_amd.utils import lights as LT
     from iris_amd.utils.exr import read_exr
     from iris_amd.utils.relight import RelitScene
@@ -583,7 +583,7 @@ def test_cli_main_writes_the_views(tmp_path):
     lights = LT.load_light_config(str(data / "relight.json"))
     relit = RelitScene(LT.compose(g["verts"], g["faces"], _state(g, p), lights.at(1), 0.0, 0), dev)
     assert relit.n_spots == 3 and relit.n_emitters == 2 + 3 * 20
-    rays = _view_rays(RR.scaled_view({"kind": "real", "K": K, "c2w": c2w}, a), (h * a, w * a), dev)
+    rays = view_rays(RR.scaled_view({"kind": "real", "K": K, "c2w": c2w}, a), (h * a, w * a), dev, ray_diff=True)
     torch.manual_seed(3 * 1000003 + 1); torch.cuda.manual_seed(3 * 1000003 + 1)
     out = RR.relight_view(relit, StubMaterial(), crf.to(dev), rays, (h, w), 4, 2, 1, anti_aliasing=a)
     np.testing.assert_array_equal(exr[1], out["rgb_full"].cpu().numpy())

@@ -235,6 +235,7 @@ def test_render_view_and_cli(tmp_path, monkeypatch):
     EXR files read back equal what render_view returns for the same seed, metrics.txt parses; a round count of 2 halves what two single rounds sum to"""
     from iris_amd import render as R
     from iris_amd.model.crf import EmorCRF
+    from iris_amd.utils.cameras import view_rays
     from iris_amd.utils.exr import read_exr
     from stub_material import StubMaterial
     f, scene, em = setup()
@@ -275,7 +276,7 @@ def test_render_view_and_cli(tmp_path, monkeypatch):
     assert lines[0] == "Name, PSNR" and lines[1].startswith("00000, ") and lines[2].startswith("mean ")
     assert float(lines[1].split(", ")[1]) == float(lines[2].split(", ")[1]) > 0
     # the same view through render_view with the CLI's seed: the files hold the returned maps
-    rays = R._view_rays({"kind": "real", "K": f["K"], "c2w": f["c2w"]}, (H, W), torch.device(DEV))
+    rays = view_rays({"kind": "real", "K": f["K"], "c2w": f["c2w"]}, (H, W), torch.device(DEV), ray_diff=True)
     torch.manual_seed(3 * 1000003); torch.cuda.manual_seed(3 * 1000003)
     out = R.render_view(scene, em, StubMaterial(), crf.to(DEV), rays, (H, W), 4, 2, 2, exposure=1.2, gt=gt)
     assert out["rounds"] == 2 and abs(out["psnr"] - float(lines[1].split(", ")[1])) < 1e-4

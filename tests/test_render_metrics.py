@@ -18,7 +18,9 @@ def test_cli_writes_the_ssim_column(tmp_path, capsys):
     the CLI's seed to 1e-5 (the file's precision; the kernel's own bound is tests/test_metrics.py's); without "ssim" render_view returns None for it"""
     from iris_amd import render as R
     from iris_amd.model.crf import EmorCRF
+    from iris_amd.utils.cameras import view_rays
     from iris_amd.utils.exr import write_exr
+    from iris_amd.utils.stage import read_image
     from stub_material import StubMaterial
     f, scene, em = setup()
     H, W = int(f["H"]), int(f["W"])
@@ -51,8 +53,8 @@ def test_cli_writes_the_ssim_column(tmp_path, capsys):
     assert row[0] == "00000" and mean[0] == "mean " and len(row) == 3 and len(mean) == 3
     assert row[1:] == mean[1:] and all(len(v.split(".")[1]) == 5 for v in row[1:])
     # the same view through render_view with the CLI's seed
-    gt_read = R._read_image(str(data / "gt.exr"), (H, W))
-    rays = R._view_rays({"kind": "real", "K": f["K"], "c2w": f["c2w"]}, (H, W), torch.device(DEV))
+    gt_read = read_image(str(data / "gt.exr"), (H, W))
+    rays = view_rays({"kind": "real", "K": f["K"], "c2w": f["c2w"]}, (H, W), torch.device(DEV), ray_diff=True)
     torch.manual_seed(3 * 1000003); torch.cuda.manual_seed(3 * 1000003)
     out = R.render_view(scene, em, StubMaterial(), crf.to(DEV), rays, (H, W), 4, 2, 2, exposure=1.2, gt=gt_read, metrics=("psnr", "ssim"))
     _, m64 = ssim_ref64(gt_read, out["rgb_ldr"].cpu().numpy(), 1.0)
