@@ -542,6 +542,45 @@ IRIS_API int iris_philox_u2(uint64_t seed, uint64_t idx0, uint32_t stream_id, in
 IRIS_API const char *iris_last_error(void);
 IRIS_API const char *iris_version(void);
 
+/* ---- 5c-11: one view's primary hits pooled where they land (slf_bake.py, slf_refine.py, extract_emitter_ldr.py) -------- */
+/* One launch per view and pass: per pixel a primary ray, its closest hit (iris_intersect's traversal and position, bit for bit) and, for a hit, any subset
+ * of four sinks, selected by which pointers are non-NULL (none: the launch only traces).  A miss contributes to nothing.  No intermediate tensors, no
+ * host synchronisation.  Float sums are float atomics: equal to a sequential scatter up to summation order; counts, histogram and bounds are exact. */
+typedef struct {
+    /* rays.  camera != NULL: HOST pointer to 24 floats K[9] | c2w[12] | focal | 2 pad (a row of the trainers' camera table); the rays are those of
+     * iris_raygen_real / iris_raygen_synthetic (ray_diff = 0) for pixel i = y W + x of an H x W view, and B is H W.  camera == NULL: B explicit rays,
+     * ray i at rays_o + i ray_stride and rays_d + i ray_stride floats (device; ray_stride >= 3; an (N,6) tensor: rays_d = rays_o + 3, ray_stride = 6). */
+    const float *camera;
+    int32_t H, W, synthetic;
+    const float *rays_o, *rays_d;
+    int64_t ray_stride, B;
+    /* radiance of ray i: row i of a (B,3) store, uint8 decoded as float(double(u) / 255) or float32 as stored; NULL when no pooling sink is given.
+     * crf_grid != NULL: passed through the inverse response, interp(crf_grid, crf_inv_table[c], clip(v, 0, 1)) / exposure -- iris_crf_lookup_inv's
+     * arithmetic and its exposure convention (exposure NULL: exposure_value; else n_exposure = 1 or B device values). */
+    const void *rgb;
+    int32_t rgb_is_u8;
+    const float *crf_grid, *crf_inv_table;
+    int32_t crf_n;
+    const float *exposure;
+    int64_t n_exposure;
+    float exposure_value;
+    /* sink 1, bounds: 2 device floats [min, max] over all three coordinates of all hit positions; the caller initialises them (the reference: 1000, 0).
+     * Reduced per wave and workgroup, two integer atomics per workgroup; a zero's sign is not kept. */
+    float *bounds;
+    /* sink 2, occupancy: hist (hist_H^3) f32 [z][y][x] += 1, iris_voxel_histogram's voxel of the position */
+    float *hist;
+    double voxel_min, voxel_max;
+    int32_t hist_H;
+    /* sink 3, voxel pool: iris_slf_scatter_add of (position, radiance); a position in an empty voxel is dropped */
+    const iris_slf *slf;
+    float *slf_acc;
+    int64_t *slf_count;
+    /* sink 4, triangle pool: tri_sum (n_tri,3) += radiance and tri_count (n_tri) f32 += 1 (nullable) at the hit triangle: iris_scatter_add_rows */
+    float *tri_sum, *tri_count;
+    int64_t n_tri;
+} iris_pool_view_args;
+IRIS_API int iris_pool_view(const iris_scene *, const iris_pool_view_args *, iris_stream_t);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@
 #include "iris_deflate.h"
 #include "iris_batch.h"
 #include "iris_optim.h"
+#include "iris_prebake.h"
 
 using namespace iris;
 
@@ -73,7 +74,7 @@ struct DevEvent {
 };
 
 // ---- diagnostics options (iris_hip_debug.h): process-wide, set by tests / experiments only; -1 = the built-in default
-static long long g_opt_bvh_tri_cost_x100 = -1, g_opt_bvh_max_leaf = -1, g_opt_phase_min = -1, g_opt_tile_target_rays = -1, g_opt_tiles_per_block = -1, g_opt_pt_tile_min = -1, g_opt_bvh_presplit_x10 = -1, g_opt_joint_max_rays = -1, g_opt_prop_bwd_targets = -1, g_opt_prop_lds_members = -1;
+static long long g_opt_bvh_tri_cost_x100 = -1, g_opt_bvh_max_leaf = -1, g_opt_phase_min = -1, g_opt_tile_target_rays = -1, g_opt_tiles_per_block = -1, g_opt_pt_tile_min = -1, g_opt_bvh_presplit_x10 = -1, g_opt_joint_max_rays = -1, g_opt_prop_bwd_targets = -1, g_opt_prop_lds_members = -1, g_opt_pool_combine = -1;
 extern "C" IRIS_API int iris_debug_set(const char* key, long long value) {
     if (!key) return fail(IRIS_ERR_ARG, "iris_debug_set: null key");
     const std::string k(key);
@@ -87,6 +88,7 @@ extern "C" IRIS_API int iris_debug_set(const char* key, long long value) {
     else if (k == "joint_max_rays") g_opt_joint_max_rays = value;
     else if (k == "prop_bwd_targets") g_opt_prop_bwd_targets = value;
     else if (k == "prop_lds_members") g_opt_prop_lds_members = value;
+    else if (k == "pool_combine") g_opt_pool_combine = value;
     else return fail(IRIS_ERR_ARG, "iris_debug_set: unknown option " + k);
     return IRIS_OK;
 }
@@ -1905,10 +1907,7 @@ extern "C" IRIS_API int iris_exr_zip_encode(const uint8_t* full, const uint8_t* 
 __global__ void slf_scatter_add_kernel(SlfDev s, const float* __restrict__ x, const float* __restrict__ rgb, int64_t B, float* __restrict__ acc,
                                        unsigned long long* __restrict__ count) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < B; i += (int64_t)gridDim.x * blockDim.x) {
-        const int j = slf_index(s, ld3(x + i * 3));
-        if (j < 0) continue;
-        atomicAdd(acc + (int64_t)j * 3, rgb[i * 3]); atomicAdd(acc + (int64_t)j * 3 + 1, rgb[i * 3 + 1]); atomicAdd(acc + (int64_t)j * 3 + 2, rgb[i * 3 + 2]);
-        atomicAdd(count + j, 1ull);
+        pool_voxel(s, ld3(x + i * 3), ld3(rgb + i * 3), acc, count);      // iris_prebake.h: shared with pool_view_kernel
     }
 }
 extern "C" IRIS_API int iris_slf_scatter_add(const iris_slf* s, const float* x, const float* rgb, int64_t B, float* radiance_acc, int64_t* count,
@@ -1921,8 +1920,7 @@ extern "C" IRIS_API int iris_slf_scatter_add(const iris_slf* s, const float* x, 
 __global__ void voxel_histogram_kernel(const float* __restrict__ x, int64_t B, float vmin, float den, int H, float* __restrict__ hist) {
     SlfDev s{}; s.H = H; s.vmin = vmin; s.den = den;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < B; i += (int64_t)gridDim.x * blockDim.x) {
-        const int cx = voxel_coord(x[i * 3], s), cy = voxel_coord(x[i * 3 + 1], s), cz = voxel_coord(x[i * 3 + 2], s);
-        atomicAdd(hist + ((int64_t)cz * H + cy) * H + cx, 1.0f);
+        pool_hist(hist, s, ld3(x + i * 3));
     }
 }
 extern "C" IRIS_API int iris_voxel_histogram(const float* x, int64_t B, double voxel_min, double voxel_max, int H, float* hist, iris_stream_t stream) {
@@ -1934,14 +1932,50 @@ extern "C" IRIS_API int iris_voxel_histogram(const float* x, int64_t B, double v
 __global__ void scatter_add_rows_kernel(const float* __restrict__ values, const int64_t* __restrict__ idx, int64_t B, int64_t F, float* __restrict__ out,
                                         float* __restrict__ count) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < B; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t j = idx[i];
-        if (j < 0 || j >= F) continue;
-        atomicAdd(out + j * 3, values[i * 3]); atomicAdd(out + j * 3 + 1, values[i * 3 + 1]); atomicAdd(out + j * 3 + 2, values[i * 3 + 2]);
-        if (count) atomicAdd(count + j, 1.0f);
+        pool_triangle(idx[i], F, ld3(values + i * 3), out, count);
     }
 }
 extern "C" IRIS_API int iris_scatter_add_rows(const float* values, const int64_t* idx, int64_t B, int64_t F, float* out, float* count, iris_stream_t stream) {
     if (B < 0 || F < 0 || (B > 0 && (!values || !idx || !out))) return fail(IRIS_ERR_ARG, "iris_scatter_add_rows: bad arguments");
     if (B == 0) return IRIS_OK;
     return launch1d(scatter_add_rows_kernel, B, 8192, stream, values, idx, B, F, out, count);
+}
+
+// 5c-11: a view's primary hits pooled where they land (iris_prebake.h)
+extern "C" IRIS_API int iris_pool_view(const iris_scene* s, const iris_pool_view_args* v, iris_stream_t stream) {
+    if (!s || !v) return fail(IRIS_ERR_ARG, "iris_pool_view: bad arguments");
+    PoolViewArgs a{};
+    a.from_camera = v->camera != nullptr;
+    if (a.from_camera) {
+        if (v->H <= 0 || v->W <= 0) return fail(IRIS_ERR_ARG, "iris_pool_view: a camera needs a positive image size");
+        std::memcpy(a.camera, v->camera, sizeof(a.camera));
+        a.H = v->H; a.W = v->W; a.synthetic = v->synthetic != 0;
+        a.B = (int64_t)v->H * v->W;
+    } else {
+        if (v->B < 0 || (v->B > 0 && (!v->rays_o || !v->rays_d || v->ray_stride < 3))) return fail(IRIS_ERR_ARG, "iris_pool_view: bad rays");
+        a.rays_o = v->rays_o; a.rays_d = v->rays_d; a.ray_stride = v->ray_stride; a.B = v->B;
+    }
+    const bool pools = v->slf || v->tri_sum;
+    if (pools && !v->rgb && a.B > 0) return fail(IRIS_ERR_ARG, "iris_pool_view: a pooling sink without a radiance store");
+    if (v->slf && (!v->slf_acc || !v->slf_count)) return fail(IRIS_ERR_ARG, "iris_pool_view: the voxel pool needs its sum and count buffers");
+    if (v->tri_sum && v->n_tri < 0) return fail(IRIS_ERR_ARG, "iris_pool_view: negative triangle count");
+    if (v->hist && v->hist_H <= 0) return fail(IRIS_ERR_ARG, "iris_pool_view: the histogram needs a positive resolution");
+    if (v->crf_grid && (!v->crf_inv_table || v->crf_n < 2 || v->crf_n > kCrfMaxKnots || (v->exposure && v->n_exposure != 1 && v->n_exposure != a.B)))
+        return fail(IRIS_ERR_ARG, "iris_pool_view: bad response tables or exposure count");
+    if (a.B == 0) return IRIS_OK;
+    a.rgb = v->rgb; a.rgb_u8 = v->rgb_is_u8 != 0;
+    a.crf.grid = v->crf_grid; a.crf.table = v->crf_inv_table; a.crf.n = v->crf_n;
+    a.crf.exposure = v->exposure; a.crf.n_exposure = v->n_exposure; a.crf.exposure_value = v->exposure_value; a.crf.B = a.B;
+    a.bounds = v->bounds;
+    a.hist = v->hist;
+    a.hist_grid.H = v->hist_H; a.hist_grid.vmin = (float)v->voxel_min; a.hist_grid.den = (float)(v->voxel_max - v->voxel_min);      // as iris_voxel_histogram
+    if (v->slf) { a.has_slf = 1; a.slf = v->slf->dev; a.slf_acc = v->slf_acc; a.slf_count = (unsigned long long*)v->slf_count; }
+    a.tri_sum = v->tri_sum; a.tri_count = v->tri_count; a.n_tri = v->n_tri;
+    a.combine = g_opt_pool_combine >= 0 ? g_opt_pool_combine != 0 : 1;      // iris_debug_set("pool_combine", 0): per-lane atomics, the comparison arm of tools/bench_prebake.py
+    with_trace(s->dev, a.B, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pool_view_kernel<T::layout, T::joint>), dim3(grid_for(a.B, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, s->dev, a);
+    });
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
 }

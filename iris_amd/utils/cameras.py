@@ -39,15 +39,22 @@ def _read_cam_params(path):
     return np.split(a, n, axis=0)
 
 
+def real_split_ids(n_views, split="train"):
+    """capture ids of a split of the real layout (get_split_ids, real_ldr.py:85-91): views 0, 10, .. 150 validate, every other view trains.  The ONE
+    statement of the rule: the camera list, the training files and the photographs' paths (files named by capture id) all take it from here."""
+    val_ids = {i * 10 for i in range(16)}
+    return [i for i in range(int(n_views)) if (i in val_ids) != (split == "train")]
+
+
 def load_real(scene_dir, res_scale=1.0, img_hw=None, split="train"):
     if img_hw is None:
         img_hw = _img_hw_from_exr(os.path.join(scene_dir, "Image", "000_0001.exr"), res_scale)
     views = []
     cams = _read_cam_params(os.path.join(scene_dir, "cam.txt"))
     Ks = _read_cam_params(os.path.join(scene_dir, "K_list.txt"))
-    val_ids = {i * 10 for i in range(16)}                              # get_split_ids, real_ldr.py:85-91
+    keep = set(real_split_ids(len(cams), split))
     for i, (cam, K) in enumerate(zip(cams, Ks)):
-        if (i in val_ids) == (split == "train"):
+        if i not in keep:
             continue
         origin, lookat, up = cam[0], cam[1], cam[2]
         at = (lookat - origin) / np.linalg.norm(lookat - origin)

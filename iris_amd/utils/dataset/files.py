@@ -67,8 +67,7 @@ def load_training_files(dataset, root, ldr_img_dir, *, has_part=0, res_scale=1.0
     else:
         with open(os.path.join(root, "cam.txt")) as fh:
             n_total = int(fh.readline())
-        val_ids = {i * 10 for i in range(16)}                         # get_split_ids, real_ldr.py:85-91
-        file_ids = [i for i in range(n_total) if i not in val_ids]
+        file_ids = cameras.real_split_ids(n_total, "train")
         if not file_ids:
             raise L.IrisError(f"{root}: no training views ({n_total} views, all in the validation split)")
         img_hw = _image_size(data_root, os.path.join(data_root, ldr_img_dir, "%03d_0001.png" % file_ids[0]))

@@ -1,6 +1,7 @@
-"""What the six command-line stages (bake_shading, refine_shading, render, render_relight, train_brdf_crf, utils.export) do before their first kernel
-launches: find the mesh, list the views, read checkpoints and the material network, build their parsers' shared options, open the device.  Plain functions;
-a stage's main() stays a linear script that calls them.  Everything down to the parser helpers is host code and imports without a GPU; the last five functions need one.
+"""What the nine command-line stages (slf_bake, extract_emitter_ldr, slf_refine, bake_shading, refine_shading, render, render_relight, train_brdf_crf,
+utils.export) do before their first kernel launches: find the mesh, list the views and their photographs, read checkpoints and the material network, build
+their parsers' shared options, open the device.  Plain functions; a stage's main() stays a linear script that calls them.  Everything down to the parser
+helpers is host code and imports without a GPU; the last six functions need one.
 """
 import importlib
 import os
@@ -55,6 +56,81 @@ def read_image(path, img_hw):
     if a.shape[:2] != tuple(img_hw):
         raise L.IrisError(f"{path}: {a.shape[:2]} pixels, the view has {tuple(img_hw)}")
     return a
+
+
+def check_photograph_size(path, img_hw):
+    """IrisError when the photograph's size (read from its header: nothing is decoded) is not the view's: resizing is not built, so --res_scale != 1 against
+    full-size files ends here; FileNotFoundError when there is no such file"""
+    if not os.path.isfile(path):
+        raise FileNotFoundError(path)
+    if path.lower().endswith(".exr"):
+        from .exr import read_exr_header
+        h = read_exr_header(path)
+        size = (int(h["height"]), int(h["width"]))
+    else:
+        from PIL import Image
+        with Image.open(path) as im:
+            size = (int(im.size[1]), int(im.size[0]))
+    if size != tuple(img_hw):
+        raise L.IrisError(f"{path}: the photograph is {size[0]} x {size[1]}, the view {img_hw[0]} x {img_hw[1]}: resizing photographs is not built (--res_scale 1 only)")
+
+
+def read_photograph(path, img_hw):
+    """a view's photograph as the pre-bake stages pool it: a PNG or JPEG through PIL as (H, W, 3) uint8 -- it stays 8-bit on its way to the device, where the
+    kernel decodes it as u / 255 --, an .exr through read_image as float32.  IrisError when its size is not the view's."""
+    check_photograph_size(path, img_hw)
+    if path.lower().endswith(".exr"):
+        return np.ascontiguousarray(read_image(path, img_hw)[..., :3], dtype=np.float32)
+    from PIL import Image
+    return np.array(Image.open(path).convert("RGB"))
+
+
+def load_photographs(dataset, root, scene, res_scale, ldr_img_dir=None, cameras_json=None, max_views=None):
+    """-> (img_hw, views, photographs) of the TRAIN split, for the stages that read the photographs (slf_bake, slf_refine, extract_emitter_ldr).
+    photographs[i] = (path, exposure) of views[i]; root, scene: as mesh_path takes them.
+        real       <root>/<ldr_img_dir or 'Image'>/%03d_0001.png by CAPTURE id (cameras.real_split_ids), <img_dir>/cam/exposure.npy[ids]
+        synthetic  the same under <root>/train, by frame index
+        scannetpp  <root>/data/<scene>/psdf/images/<view['name']>, exposure 1.0
+        cameras_json   each view's 'image' and 'exposure'
+    Without ldr_img_dir the real and synthetic layouts have no exposures (None), as in the reference.  The image size of a real / synthetic scene without
+    Image/000_0001.exr is its first photograph's."""
+    if cameras_json:
+        img_hw, views = load_views(dataset, root, scene, res_scale, cameras_json=cameras_json, extras=True)
+        photos = [(v["image"], v["exposure"]) for v in views]
+        missing = [i for i, (path, _) in enumerate(photos) if not path]
+        if missing:
+            raise L.IrisError(f"{cameras_json}: view {missing[0]} names no 'image'")
+    elif dataset in ("real", "synthetic"):
+        data_root = os.path.join(root, "train") if dataset == "synthetic" else root
+        img_dir = os.path.join(data_root, ldr_img_dir or "Image")
+        if dataset == "real":
+            with open(os.path.join(root, "cam.txt")) as fh:
+                n_total = int(fh.readline())
+            ids = cameras.real_split_ids(n_total, "train")
+        else:
+            ids = None
+        img_hw = None
+        if not os.path.isfile(os.path.join(data_root, "Image", "000_0001.exr")):
+            from .dataset.files import _image_size
+            h, w = _image_size(data_root, os.path.join(img_dir, "%03d_0001.png" % (ids[0] if ids else 0)))
+            img_hw = (int(h * res_scale), int(w * res_scale))
+        img_hw, views = load_views(dataset, root, scene, res_scale, img_hw=img_hw)
+        ids = list(range(len(views))) if ids is None else ids
+        if len(ids) != len(views):
+            raise L.IrisError(f"{root}: {len(views)} cameras for {len(ids)} training views")
+        exposures = [None] * len(ids)
+        if ldr_img_dir:
+            table = np.load(os.path.join(img_dir, "cam", "exposure.npy")).astype(np.float32).reshape(-1)
+            if table.shape[0] <= max(ids):
+                raise L.IrisError(f"{ldr_img_dir}/cam/exposure.npy holds {table.shape[0]} values, the training views reach id {max(ids)}")
+            exposures = [float(table[i]) for i in ids]
+        photos = [(os.path.join(img_dir, "%03d_0001.png" % i), e) for i, e in zip(ids, exposures)]
+    else:
+        img_hw, views = load_views(dataset, root, scene, res_scale)
+        photos = [(os.path.join(root, "data", scene, "psdf", "images", v["name"]), 1.0) for v in views]
+    if max_views is not None:
+        views, photos = views[:max_views], photos[:max_views]
+    return img_hw, views, photos
 
 
 def load_pickled(path):
@@ -169,6 +245,13 @@ def load_crf(crf_state, crf_basis, emor_path, device):
         model_crf = EmorCRF(crf_basis, emor_path=emor_path)
     model_crf.load_state_dict(crf_state)
     return model_crf.to(device)
+
+
+def photograph_batches(views, img_hw, photographs, device):
+    """the batch dicts iris_amd.slf_bake's functions take, one per view, made as they are asked for: {'camera', 'img_hw', 'image' on the device (8-bit
+    stays 8-bit), 'exposure'}"""
+    for view, (path, exposure) in zip(views, photographs):
+        yield {"camera": view, "img_hw": tuple(img_hw), "image": torch.from_numpy(read_photograph(path, img_hw)).to(device), "exposure": exposure}
 
 
 def freeze(*modules):
