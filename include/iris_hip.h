@@ -463,6 +463,22 @@ IRIS_API int iris_loss_albedo_fwd(const int32_t *runs, const int64_t *order, con
 IRIS_API int iris_loss_albedo_bwd(const int32_t *runs, const int64_t *order, const float *albedo, const float *seg_means, const float *k, int64_t N, float weight,
                          const float *g_loss, float *g_albedo, iris_stream_t);
 
+/* ---- the photometric step loss of the emitter and initialisation stages (train_emitter.py:189-195, initialize.py:180-184), response model frozen ------- */
+/* L_sum (B, 3) f32: the integrator's sum over n_calls calls; grid, table, n, exposure, n_exposure, exposure_value: as iris_crf_fwd takes them (below);
+ * rgbs_gt (B, 3) f32.  Per entry: L = L_sum / (float)n_calls (a division), rgb = the lookup of iris_crf_fwd (the same bits), d = rgb - gt.
+ *   loss[0]  = (sum d^2) / (3 B): squares and sums in double -- xor butterfly per wave, the waves of a workgroup in wave order, the workgroups' partials
+ *              in a fixed order by one workgroup --, rounded to f32 once
+ *   psnr[0]  = -10 log10(max(loss[0], 1e-5))
+ *   dL_sum (B, 3) = ((2 d) / (float)(3 B)) * s / (float)n_calls, s = what iris_crf_bwd gives as g_hdr for g_ldr = 1 (slope * e_i; 0 where hdr * e_i leaves [0, 1]
+ *              and on a flat segment): the gradient of loss[0] by L_sum.  Plain stores, every entry once.
+ * No gradient by the table or by rgbs_gt.  A pass over the pixels and a one-workgroup pass over its partials, whose number depends on B only; no atomics:
+ * two calls on the same inputs agree bit for bit.  workspace: iris_loss_photometric_workspace_bytes(B) bytes (8 * min(ceil(B / 256), 4096)), 8-byte aligned.
+ * B >= 1, 1 <= n_calls <= 2^24. */
+IRIS_API uint64_t iris_loss_photometric_workspace_bytes(int64_t B);
+IRIS_API int iris_loss_photometric(const float *L_sum, int n_calls, const float *grid, const float *table, int n, const float *exposure, int64_t n_exposure,
+                          float exposure_value, const float *rgbs_gt, int64_t B, float *loss, float *psnr, float *dL_sum, void *workspace,
+                          uint64_t workspace_bytes, iris_stream_t);
+
 /* ---- the camera response model EmorCRF (crf/model_crf.py:32-122) ---------------------------------------------------------------------- */
 /* The interpolator is this project's contract (the reference's torch_interpolations is third-party and has no ROCm build: parity unpinned).  Knots p[0..n)
  * non-decreasing, values v[0..n), query q:  r = first index with p[r] >= q, clamped to n - 1 (torch.bucketize);  l = max(r - 1, 0);  dl = max(q - p[l], 0);

@@ -118,6 +118,8 @@ PROTOTYPES = {
     "iris_prop_part_bwd": [_P, _P, _P, _P, _P, _I64, _F, _P, _P, _P, _P],
     "iris_loss_albedo_fwd": [_P, _P, _P, _P, _I64, _I32, _F, _P, _P, _P, _P, _P],
     "iris_loss_albedo_bwd": [_P, _P, _P, _P, _P, _I64, _F, _P, _P, _P],
+    "iris_loss_photometric_workspace_bytes": [_I64],
+    "iris_loss_photometric": [_P, _I32, _P, _P, _I32, _P, _I64, _F, _P, _I64, _P, _P, _P, _P, _U64, _P],
     "iris_crf_fwd": [_P, _P, _I32, _P, _P, _I64, _F, _I64, _P, _P],
     "iris_crf_lookup_inv": [_P, _P, _I32, _P, _P, _I64, _F, _I64, _P, _P],
     "iris_crf_bwd_workspace_bytes": [_I64, _I32],
@@ -141,6 +143,7 @@ PROTOTYPES = {
 _RESTYPE = {"iris_scene_destroy": None, "iris_slf_destroy": None, "iris_emitter_destroy": None,
             "iris_last_error": C.c_char_p, "iris_version": C.c_char_p, "iris_debug_build_flags": C.c_char_p, "iris_debug_source_hash": C.c_char_p, "iris_ngp_n_params": C.c_int64, "iris_ngp_destroy": None, "iris_bake_workspace_bytes": C.c_uint64, "iris_pt_compact_workspace_bytes": C.c_uint64, "iris_denoise_workspace_bytes": C.c_uint64,
             "iris_exr_zip_workspace_bytes": C.c_uint64, "iris_ngp_backward_workspace_bytes": C.c_uint64, "iris_crf_bwd_workspace_bytes": C.c_uint64,
+            "iris_loss_photometric_workspace_bytes": C.c_uint64,
             "iris_image_metrics_workspace_bytes": C.c_uint64, "iris_uv_raster_workspace_bytes": C.c_uint64}
 
 _lib = None

@@ -1106,6 +1106,30 @@ extern "C" IRIS_API int iris_crf_inv_table(const float* grid, const float* table
     return IRIS_OK;
 }
 
+// ---- the photometric step loss of the emitter and initialisation stages (iris_loss.h; train_emitter.py:189-195, initialize.py:180-184)
+extern "C" IRIS_API uint64_t iris_loss_photometric_workspace_bytes(int64_t B) {
+    if (B < 1) return 0;
+    return (uint64_t)loss_blocks(B) * sizeof(double);
+}
+extern "C" IRIS_API int iris_loss_photometric(const float* L_sum, int n_calls, const float* grid, const float* table, int n, const float* exposure,
+                                              int64_t n_exposure, float exposure_value, const float* rgbs_gt, int64_t B, float* loss, float* psnr, float* dL_sum,
+                                              void* workspace, uint64_t workspace_bytes, iris_stream_t stream) {
+    CrfArgs a;
+    if (!crf_args(grid, table, n, exposure, n_exposure, exposure_value, B, a) || B < 1 || B > (int64_t)1 << 40 || n_calls < 1 || n_calls > 1 << 24 || !L_sum ||
+        !rgbs_gt || !loss || !psnr || !dL_sum)
+        return fail(IRIS_ERR_ARG, "iris_loss_photometric: bad arguments (B >= 1, 1 <= n_calls <= 2^24, 2 <= n <= 1024, exposure holds 1 or B values)");
+    if (!workspace || workspace_bytes < iris_loss_photometric_workspace_bytes(B) || (uintptr_t)workspace % 8)
+        return fail(IRIS_ERR_ARG, "iris_loss_photometric: needs an 8-byte aligned workspace of " + std::to_string(iris_loss_photometric_workspace_bytes(B)) + " bytes");
+    const int blocks = loss_blocks(B);
+    const double three_b = 3.0 * (double)B;
+    hipLaunchKernelGGL(loss_photometric_kernel, dim3(blocks), dim3(kLossThreads), (size_t)n * 4 * sizeof(float), (hipStream_t)stream, a, L_sum, (float)n_calls, rgbs_gt,
+                       (float)three_b, (double*)workspace, dL_sum);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(loss_photometric_finish_kernel, dim3(1), dim3(kLossThreads), 0, (hipStream_t)stream, (const double*)workspace, blocks, three_b, loss, psnr);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
 // ---- 8(f)-4: denoiser substitute (iris_denoise.h)
 extern "C" IRIS_API uint64_t iris_denoise_workspace_bytes(int H, int W) {
     if (H < 1 || W < 1) return 0;

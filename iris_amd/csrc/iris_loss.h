@@ -16,10 +16,20 @@
 // The grids are functions of N alone and every reduction has a fixed order: no atomics, two calls on the same inputs agree bit for bit.
 // order, runs, the means' rows and the partials are read by consecutive lanes at consecutive positions; albedo, the prior and the gradient are the
 // 12-byte rows of pixel order[p] (96 KB each at the trainer's batch of 8192: resident in L2).
+//
+// The photometric step loss of the emitter and initialisation stages (train_emitter.py:189-195, initialize.py:180-184, 206) with the response model
+// frozen: L = L_sum / n_calls, rgb = crf(L, e) (iris_crf.h's lookup, the bits of iris_crf_fwd), d = rgb - gt,
+//     loss = sum d^2 / (3 B),   psnr = -10 log10(max(loss, 1e-5)),   dL_sum = ((2 d) / (3 B)) * (slope e) / n_calls
+// with `slope e` what iris_crf_bwd multiplies into its cotangent (0 outside the clip's closed interval and on a flat segment).
+//   terms    one thread per pixel (grid-stride beyond 4096 workgroups), the knots and the table in LDS; the gradient's three words go out as plain
+//            stores; d^2 is formed and summed in double: xor butterfly per wave, the four waves' sums added in wave order -> one double per workgroup
+//   finish   one workgroup adds the partials in a fixed order -> loss, psnr
+// The grid is a function of B alone and nothing is added atomically: loss and gradient are bitwise reproducible.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "iris_crf.h"
 #include "iris_prop.h"
 
 namespace iris {
@@ -117,6 +127,62 @@ __global__ void loss_albedo_bwd_kernel(const int2* __restrict__ runs, const int6
         g_albedo[i * 3] = g * (a.x - k * T.x);
         g_albedo[i * 3 + 1] = g * (a.y - k * T.y);
         g_albedo[i * 3 + 2] = g * (a.z - k * T.z);
+    }
+}
+
+// ---- the photometric step loss
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// the workgroup's sum: waves 0, 1, 2, 3 in that order; valid in thread 0
+__device__ __forceinline__ double loss_block_sum_f64(double v, double* part) {
+    v = wave_sum_f64(v);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < kLossThreads / 64; ++w) s += part[w];
+    return s;
+}
+
+// partials[block] = sum over the workgroup's pixels and channels of d^2; g[i][c] = ((2 d) / three_b) * (slope e) / n_calls
+__global__ __launch_bounds__(kLossThreads) void loss_photometric_kernel(CrfArgs a, const float* __restrict__ L_sum, float n_calls, const float* __restrict__ gt,
+                                                                        float three_b, double* __restrict__ partials, float* __restrict__ g) {
+    extern __shared__ float crf_lds[];
+    __shared__ double part[kLossThreads / 64];
+    float *sp = crf_lds, *sv = crf_lds + a.n;
+    crf_load_tables(a, sp, sv);
+    double sq = 0.0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < a.B; i += (int64_t)gridDim.x * blockDim.x) {
+        const float e = crf_exposure(a, i);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float x = (L_sum[i * 3 + c] / n_calls) * e;
+            const CrfSeg s = crf_segment_uniform(sp, a.n, crf_clip(x));
+            const float* v = sv + c * a.n;
+            const float d = crf_value(v, s) - gt[i * 3 + c];
+            sq += (double)d * (double)d;
+            const float slope = s.flat ? 0.f : (v[s.r] - v[s.l]) / (s.dl + s.dr);
+            const float se = (x >= 0.f && x <= 1.f) ? slope * e : 0.f;         // iris_crf_bwd's factor on a cotangent of one
+            g[i * 3 + c] = (((2.f * d) / three_b) * se) / n_calls;
+        }
+    }
+    sq = loss_block_sum_f64(sq, part);
+    if (threadIdx.x == 0) partials[blockIdx.x] = sq;
+}
+// out[0] = loss = sum partials / three_b, out[1] = psnr: one workgroup, fixed order
+__global__ __launch_bounds__(kLossThreads) void loss_photometric_finish_kernel(const double* __restrict__ partials, int n, double three_b, float* __restrict__ loss,
+                                                                               float* __restrict__ psnr) {
+    __shared__ double part[kLossThreads / 64];
+    double s = 0.0;
+    for (int t = threadIdx.x; t < n; t += kLossThreads) s += partials[t];
+    s = loss_block_sum_f64(s, part);
+    if (threadIdx.x == 0) {
+        const float l = (float)(s / three_b);
+        loss[0] = l;
+        psnr[0] = (float)(-10.0 * log10((double)fmaxf(l, 1e-5f)));
     }
 }
 

@@ -9,6 +9,7 @@ The reference builds the albedo term from a ``segmentation.unique``, three ``tor
                         voxel_min=material.voxel_min, voxel_max=material.voxel_max)
     out = initialize_loss(mat['albedo'], L, crf=model_crf, exposure=exposure, rgbs_gt=rgbs_gt, albedo_prior=int_albedo, segmentation=segmentation)
     out['loss'].backward()
+    out = photometric_loss(L_sum, SPP // spp, crf=model_crf, exposure=exposure, rgbs_gt=rgbs_gt)        # the response model frozen: loss_c, psnr
 
 A trainer stage is a data loader (``iris_amd.utils.dataset.PixelSet``), ``torch.optim.Adam`` and a checkpoint writer around one of these calls; the
 ``valid`` filtering of the batch is the caller's (``PixelSet.restrict_to_hits`` makes every batch all-valid).  Every returned entry is a device tensor: logging them is the caller's synchronisation, not the step's.
@@ -141,3 +142,64 @@ def initialize_loss(albedo, L, *, crf, exposure, rgbs_gt, albedo_prior, segmenta
     loss_c = torch.nn.functional.mse_loss(rgbs_ldr, rgbs_gt.reshape(rgbs_ldr.shape))
     loss_a = segment_albedo_loss(albedo, albedo_prior, segmentation, weight=1.0, scale_invariant=False)
     return dict(loss=loss_a + loss_c, loss_c=loss_c, loss_a=loss_a, psnr=_psnr(loss_c))
+
+
+class _Photometric(torch.autograd.Function):
+    """loss and psnr of iris_loss_photometric; the call also leaves d loss / d L_sum, which the backward scales by the incoming gradient"""
+
+    @staticmethod
+    def forward(ctx, L_sum, n_calls, table, grid, e, n_exposure, exposure_value, gt):
+        x = _lib.require_gpu(L_sum.detach(), torch.float32, "L_sum")
+        B, n, dev = x.shape[0], table.shape[1], x.device
+        lib = _lib.lib()
+        loss, psnr = torch.empty((), device=dev, dtype=torch.float32), torch.empty((), device=dev, dtype=torch.float32)
+        g = torch.empty(B, 3, device=dev, dtype=torch.float32)
+        ws_bytes = lib.iris_loss_photometric_workspace_bytes(B)
+        ws = torch.empty(ws_bytes // 8, device=dev, dtype=torch.float64)
+        with torch.cuda.device(dev):
+            _lib.check(lib.iris_loss_photometric(_lib.ptr(x), n_calls, _lib.ptr(grid), _lib.ptr(table), n, _lib.ptr(e), n_exposure, exposure_value, _lib.ptr(gt), B,
+                                                 _lib.ptr(loss), _lib.ptr(psnr), _lib.ptr(g), _lib.ptr(ws), ws_bytes, _lib.stream()))
+        ctx.save_for_backward(g)
+        ctx.mark_non_differentiable(psnr)
+        return loss, psnr
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, _g_psnr):
+        g, = ctx.saved_tensors
+        return (g_loss * g,) + (None,) * 7
+
+
+def photometric_loss(L_sum, n_calls, *, crf, exposure, rgbs_gt):
+    """The emitter and initialisation stages' photometric term (train_emitter.py:189-195, initialize.py:180-184, 206) with the response model frozen
+    -> {'loss_c', 'psnr'}, 0-d device tensors: loss_c = mse_loss(crf(L_sum / n_calls, exposure), rgbs_gt), psnr = -10 log10(max(loss_c, 1e-5)).
+
+    L_sum (B x 3): ``path_tracing_single_step(..., spp, n_calls)``, the integrator's sum before the reference's division by SPP // spp; exposure as
+    EmorCRF.forward takes it; rgbs_gt (B x 3).  One call (iris_loss_photometric) computes the loss, the psnr and d loss_c / d L_sum in one pass over the
+    batch, in place of the division, the lookup, the mse and their autograd nodes; differentiable in L_sum only (psnr carries no gradient), no atomics:
+    loss and gradient are bitwise reproducible.  A response model that trains needs the gradient by its weights, which this call does not compute:
+    IrisError -- use brdf_crf_loss / initialize_loss there."""
+    from ..model.crf import _check_tables, _exposure_args
+    if crf.weight.requires_grad:
+        raise _lib.IrisError("photometric_loss: the response model is trainable (crf.weight.requires_grad) and this loss computes no gradient for it: freeze "
+                             "it, or use brdf_crf_loss / initialize_loss for a trainable response model")
+    n_calls = int(n_calls)
+    if not 1 <= n_calls <= 1 << 24:
+        raise _lib.IrisError(f"photometric_loss: n_calls = {n_calls}, expected 1 <= n_calls <= 2^24 (SPP // spp)")
+    for name, t in (("L_sum", L_sum), ("rgbs_gt", rgbs_gt)):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3:
+            raise _lib.IrisError(f"photometric_loss: {name} has shape {tuple(getattr(t, 'shape', ()))}, expected (B, 3)")
+    B = L_sum.shape[0]
+    if B < 1 or rgbs_gt.shape[0] != B:
+        raise _lib.IrisError(f"photometric_loss: L_sum holds {B} rays and rgbs_gt {rgbs_gt.shape[0]}: expected the same number, at least 1")
+    if torch.is_tensor(exposure) and exposure.numel() not in (1, B):
+        raise _lib.IrisError(f"photometric_loss: exposure has {exposure.numel()} values, expected 1 or {B} (one per ray)")
+    _on_gpu(L_sum=(L_sum, torch.float32))
+    gt = _lib.require_gpu(rgbs_gt.detach(), torch.float32, "rgbs_gt")
+    if rgbs_gt.device != L_sum.device or crf.weight.device != L_sum.device:
+        raise _lib.IrisError(f"photometric_loss: L_sum ({L_sum.device}), rgbs_gt ({rgbs_gt.device}) and the response model ({crf.weight.device}) must share a HIP device")
+    with torch.no_grad():
+        table, grid = _check_tables(crf.get_crf(), crf.grid)
+    e, ne, ev = _exposure_args(exposure, B, L_sum.device)
+    loss_c, psnr = _Photometric.apply(L_sum, n_calls, table, grid, e, ne, ev, gt)
+    return dict(loss_c=loss_c, psnr=psnr)

@@ -319,6 +319,33 @@ def path_tracing_single_step(scene, emitter_net, material_net, rays_o, rays_d, d
     return out
 
 
+def jittered_primary_hit(scene, emitter_net, rays_o, rays_d, dx_du, dy_dv, dudv):
+    """The head of the integrators on its own (iris_pt_primary, one launch): wi = normalize(rays_d + dx_du * (u - 0.5) + dy_dv * (v - 0.5)) and its closest
+    hit.  rays_o, rays_d, dx_du, dy_dv Bx3; dudv (2, B, spp): the caller's torch.rand draws in [0, 1) -- the kernel subtracts the half, which is the
+    integrators' jitter (utils/path_tracing.py:338-340) and the initialisation stage's (initialize.py:158-160: du, dv = rand - 0.5).  Returns a dict of (B * spp)-row tensors, pixel-major: wi, position,
+    normal (ray_intersect's), e0 (int32: the hit's emitter ordinal or -1), valid_next (bool: a hit that is no emitter).  No gradient."""
+    rays_o = L.require_gpu(rays_o, torch.float32, "rays_o").reshape(-1, 3)
+    rays_d = L.require_gpu(rays_d, torch.float32, "rays_d").reshape(-1, 3)
+    dx_du = L.require_gpu(dx_du, torch.float32, "dx_du").reshape(-1, 3)
+    dy_dv = L.require_gpu(dy_dv, torch.float32, "dy_dv").reshape(-1, 3)
+    dudv = L.require_gpu(dudv, torch.float32, "dudv")
+    B, dev = rays_o.shape[0], rays_o.device
+    if rays_d.shape[0] != B or dx_du.shape[0] != B or dy_dv.shape[0] != B or dudv.dim() < 2 or dudv.shape[0] != 2 or dudv.numel() % (2 * max(B, 1)) or (B == 0 and dudv.numel()):
+        raise L.IrisError(f"jittered_primary_hit: {B} origins, rays_d {tuple(rays_d.shape)}, dx_du {tuple(dx_du.shape)}, dy_dv {tuple(dy_dv.shape)}, dudv "
+                          f"{tuple(dudv.shape)}: expected B x 3 each and dudv (2, B, spp)")
+    spp = dudv.numel() // (2 * B) if B else 1
+    N = B * spp
+    if spp < 1 or N >= 1 << 31:
+        raise L.IrisError(f"jittered_primary_hit: B * spp = {N} paths, expected 1 <= spp and fewer than 2^31 paths")
+    wi = torch.empty(N, 3, device=dev); wo = torch.empty(N, 3, device=dev); position = torch.empty(N, 3, device=dev); normal = torch.empty(N, 3, device=dev)
+    e0 = torch.empty(N, device=dev, dtype=torch.int32); valid_next = torch.empty(N, device=dev, dtype=torch.bool); path_of = torch.empty(N, device=dev, dtype=torch.int32)
+    if N:
+        with torch.cuda.device(dev):
+            L.check(L.lib().iris_pt_primary(scene.handle, emitter_net.handle(dev), L.ptr(rays_o), L.ptr(rays_d), L.ptr(dx_du), L.ptr(dy_dv), L.ptr(dudv), B, spp, L.ptr(wi),
+                                            L.ptr(wo), L.ptr(position), L.ptr(normal), L.ptr(e0), L.ptr(valid_next), L.ptr(path_of), L.stream()))
+    return dict(wi=wi, position=position, normal=normal, e0=e0, valid_next=valid_next)
+
+
 def path_tracing_single(scene, emitter_net, material_net, rays_o, rays_d, dx_du, dy_dv, spp, uniforms=None, compact=None, skip_unused_material=True):
     """Path trace the scene with one bounce and power-2 MIS (utils/path_tracing.py:320-407).
 

@@ -1,5 +1,5 @@
-"""What the nine command-line stages (slf_bake, extract_emitter_ldr, slf_refine, bake_shading, refine_shading, render, render_relight, train_brdf_crf,
-utils.export) do before their first kernel launches: find the mesh, list the views and their photographs, read checkpoints and the material network, build
+"""What the eleven command-line stages (slf_bake, extract_emitter_ldr, initialize, slf_refine, bake_shading, refine_shading, render, render_relight,
+train_brdf_crf, train_emitter, utils.export) do before their first kernel launches: find the mesh, list the views and their photographs, read checkpoints and the material network, build
 their parsers' shared options, open the device.  Plain functions; a stage's main() stays a linear script that calls them.  Everything down to the parser
 helpers is host code and imports without a GPU; the last six functions need one.
 """
@@ -142,13 +142,17 @@ def load_pickled(path):
         return torch.load(path, map_location="cpu", weights_only=False)
 
 
-def write_checkpoint(path, material_state, crf_state, optimizer_state, *, epoch, global_step, hyper_parameters):
+def write_checkpoint(path, material_state, crf_state, optimizer_state, *, epoch, global_step, hyper_parameters, emitter_state=None):
     """torch.save of {'state_dict': material.* and model_crf.* entries, 'optimizer_states': [optimizer_state], 'epoch', 'global_step',
     'hyper_parameters'}: the part of a Lightning checkpoint the reference's loaders read (refine_shading.py:84-89, slf_refine.py:74-79,
-    train_brdf_crf.py:72-97 all take ['state_dict'] and filter on the two prefixes).  epoch: the number of completed epochs.  Emitter tensors are not
-    written: no consumer reads them from this file.  Written beside the target and renamed: a run that dies mid-write keeps the previous file."""
+    train_brdf_crf.py:72-97 all take ['state_dict'] and filter on the two prefixes).  epoch: the number of completed epochs.  emitter_state: the tensors
+    of the emitter and initialisation stages' SLFEmitterLearn, written under 'emitter.' -- 'emitter.radiance' is what extract_emitter_ldr --mode update
+    reads (extract_emitter_ldr.py:117-122); None (the BRDF-CRF stage, which trains no emitter) writes no such key and the file is what it was before
+    the keyword existed.  Written beside the target and renamed: a run that dies mid-write keeps the previous file."""
     state = {"material." + k: v.detach().cpu() for k, v in material_state.items()}
     state.update({"model_crf." + k: v.detach().cpu() for k, v in crf_state.items()})
+    if emitter_state is not None:
+        state.update({"emitter." + k: v.detach().cpu() for k, v in emitter_state.items()})
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = str(path) + ".tmp"
     torch.save({"state_dict": state, "optimizer_states": [optimizer_state], "epoch": int(epoch), "global_step": int(global_step),
@@ -157,11 +161,11 @@ def write_checkpoint(path, material_state, crf_state, optimizer_state, *, epoch,
 
 
 def read_checkpoint(path):
-    """-> the saved dict plus 'material' and 'model_crf': the entries of 'state_dict' under each prefix, the prefix stripped (the reference's idiom).
-    Everything on the CPU.  A Lightning checkpoint of the reference loads too (its other entries are ignored by the callers here)."""
+    """-> the saved dict plus 'material', 'model_crf' and 'emitter': the entries of 'state_dict' under each prefix, the prefix stripped (the
+    reference's idiom); 'emitter' is empty for a file without such keys (the BRDF-CRF stage's).  Everything on the CPU.  A Lightning checkpoint of the reference loads too (its other entries are ignored by the callers here)."""
     ck = load_pickled(path)
     out = dict(ck)
-    for prefix in ("material", "model_crf"):
+    for prefix in ("material", "model_crf", "emitter"):
         out[prefix] = {k.replace(prefix + ".", ""): v for k, v in ck["state_dict"].items() if prefix + "." in k}
     return out
 
