@@ -552,6 +552,28 @@ IRIS_API uint64_t iris_exr_zip_workspace_bytes(int n_maps, int64_t n_full, int64
 IRIS_API int iris_exr_zip_encode(const uint8_t *full, const uint8_t *tail, int n_maps, int64_t n_full, int64_t block_bytes, int64_t tail_bytes,
                         int lines_per_block, uint8_t *records, int64_t *map_offsets, void *workspace, uint64_t workspace_bytes, iris_stream_t);
 
+/* ---- 8-bit PNG files, device half (render_video.py's eight files per frame; utils/png.py) ----------------- */
+/* iris_png_rows: n_images equal-size images (H, W, channels), channels 1 or 3, float32 or (is_u8) uint8, device pointers -> their PNG scanline bytes.  Per
+ * float value v = x / divisor (IEEE), NaN -> 0, clamp to [0,1], q = (uint8) trunc(v * 255): (np.clip(image, 0, 1) * 255).astype(np.uint8).  A magma image
+ * (channels 1) sends q through OpenCV's COLORMAP_MAGMA and is written as RGB.  The image is cropped to even height and width (H2, W2) and every row is
+ * written as [1][Sub-filtered bytes] (PNG filter type 1, bpp = output channels): rows (device) receives n_images blocks of
+ * iris_png_row_bytes(H, W, channels, magma) = H2 * (1 + W2 * output channels) bytes (0: such an image cannot be written -- an empty crop, channels not
+ * 1 or 3, magma with 3 channels).  `images`, `divisors` and `magma` are HOST arrays of n_images entries (they travel in the kernel arguments); the images
+ * of one call are all magma or none is.  One launch per 16 images.
+ * iris_png_encode: rows = n_images blocks of block_bytes (device) -> streams: the zlib stream (RFC 1950) of each block, back to back; offsets (device int64,
+ * n_images + 1): where each starts and, last, their total size.  The encoder is iris_exr_zip_encode's (segments of 16 KiB, one deflate block each, matches
+ * at distance 1, a stored block when that is not larger); every image is one chunk and its output is always the stream.  streams must hold n_images *
+ * iris_png_stream_bound(block_bytes) bytes (header 2 + at most block_bytes + 5 per segment + Adler-32 4); workspace: iris_png_workspace_bytes() bytes
+ * (0: unsupported size).  Four launches, no host round trip.  iris_png_magma_table: the 256 x 3 R,G,B table (HOST pointer, 768 bytes). */
+IRIS_API int64_t iris_png_row_bytes(int H, int W, int channels, int magma);
+IRIS_API int iris_png_rows(const void *const *images, const float *divisors, const uint8_t *magma, int n_images, int H, int W, int channels, int is_u8,
+                  uint8_t *rows, iris_stream_t);
+IRIS_API uint64_t iris_png_stream_bound(int64_t block_bytes);
+IRIS_API uint64_t iris_png_workspace_bytes(int n_images, int64_t block_bytes);
+IRIS_API int iris_png_encode(const uint8_t *rows, int n_images, int64_t block_bytes, uint8_t *streams, int64_t *offsets, void *workspace,
+                    uint64_t workspace_bytes, iris_stream_t);
+IRIS_API void iris_png_magma_table(uint8_t *rgb);
+
 /* ---- misc --------------------------------------------------------------------------------------------- */
 /* Philox uniforms exactly as the bake kernels draw them (for tests): u2[i] = U(seed, idx0+i, stream_id). */
 IRIS_API int iris_philox_u2(uint64_t seed, uint64_t idx0, uint32_t stream_id, int64_t n, float *u2, iris_stream_t);

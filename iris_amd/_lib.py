@@ -136,6 +136,12 @@ PROTOTYPES = {
     "iris_texture_quantize": [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P],
     "iris_exr_zip_workspace_bytes": [_I32, _I64, _I64, _I64],
     "iris_exr_zip_encode": [_P, _P, _I32, _I64, _I64, _I64, _I32, _P, _P, _P, _U64, _P],
+    "iris_png_row_bytes": [_I32, _I32, _I32, _I32],
+    "iris_png_rows": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P],
+    "iris_png_stream_bound": [_I64],
+    "iris_png_workspace_bytes": [_I32, _I64],
+    "iris_png_encode": [_P, _I32, _I64, _P, _P, _P, _U64, _P],
+    "iris_png_magma_table": [_P],
     "iris_bake_tile_max_spp": [],
     "iris_last_error": [],
     "iris_version": [],
@@ -144,6 +150,7 @@ _RESTYPE = {"iris_scene_destroy": None, "iris_slf_destroy": None, "iris_emitter_
             "iris_last_error": C.c_char_p, "iris_version": C.c_char_p, "iris_debug_build_flags": C.c_char_p, "iris_debug_source_hash": C.c_char_p, "iris_ngp_n_params": C.c_int64, "iris_ngp_destroy": None, "iris_bake_workspace_bytes": C.c_uint64, "iris_pt_compact_workspace_bytes": C.c_uint64, "iris_denoise_workspace_bytes": C.c_uint64,
             "iris_exr_zip_workspace_bytes": C.c_uint64, "iris_ngp_backward_workspace_bytes": C.c_uint64, "iris_crf_bwd_workspace_bytes": C.c_uint64,
             "iris_loss_photometric_workspace_bytes": C.c_uint64,
+            "iris_png_row_bytes": C.c_int64, "iris_png_stream_bound": C.c_uint64, "iris_png_workspace_bytes": C.c_uint64, "iris_png_magma_table": None,
             "iris_image_metrics_workspace_bytes": C.c_uint64, "iris_uv_raster_workspace_bytes": C.c_uint64}
 
 _lib = None

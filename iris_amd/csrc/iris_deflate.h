@@ -20,6 +20,7 @@
 //   5. packing   : per-thread bit counts, a block scan, atomicOr into LDS words (disjoint bit ranges: the result does not depend on the order)
 // Then, per chunk, segment sizes and Adler-32 partials are combined; one workgroup scans the record sizes of all maps; one workgroup per chunk
 // writes its record (the segments by copy, or the raw block by an un-predicting scan).  No allocation: the caller passes the workspace.
+// The segment and offsets kernels also serve the PNG writer (iris_png.h): one chunk per image, always the zlib stream, no record header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -46,6 +47,8 @@ struct ZipArgs {
     uint32_t* chunk_len;      // data bytes of each chunk (== its block size: raw)
     uint32_t* chunk_adler;
     int64_t* chunk_off;
+    uint32_t* seg_off;        // PNG mode (iris_png.h): where each segment starts inside its chunk's stream; NULL for EXR records
+    int record_header;        // bytes in front of each chunk's data: 8 (int32 y, int32 size) for EXR records, 0 for a bare zlib stream
 };
 
 // chunks: the M * n_full full blocks map by map, then the M tails
@@ -431,7 +434,7 @@ __global__ __launch_bounds__(kZipScanThreads) void zip_offsets_kernel(ZipArgs a)
     const int64_t per = (N + kZipScanThreads - 1) / kZipScanThreads, k0 = min<int64_t>(N, t * per), k1 = min<int64_t>(N, k0 + per);
     auto chunk_of = [&](int64_t k) { const int64_t m = k / nc, c = k - m * nc; return c < a.n_full ? m * a.n_full + c : (int64_t)a.M * a.n_full + m; };
     uint64_t sum = 0;
-    for (int64_t k = k0; k < k1; ++k) sum += 8 + a.chunk_len[chunk_of(k)];
+    for (int64_t k = k0; k < k1; ++k) sum += a.record_header + a.chunk_len[chunk_of(k)];
     s[t] = sum; __syncthreads();
     for (int o = 1; o < kZipScanThreads; o <<= 1) {
         const uint64_t w = t >= o ? s[t - o] : 0;
@@ -442,7 +445,7 @@ __global__ __launch_bounds__(kZipScanThreads) void zip_offsets_kernel(ZipArgs a)
         const int64_t ci = chunk_of(k);
         if (k % nc == 0) a.map_offsets[k / nc] = (int64_t)off;
         a.chunk_off[ci] = (int64_t)off;
-        off += 8 + a.chunk_len[ci];
+        off += a.record_header + a.chunk_len[ci];
     }
     if (t == kZipScanThreads - 1) a.map_offsets[a.M] = (int64_t)s[t];
 }

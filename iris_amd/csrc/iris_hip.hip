@@ -30,6 +30,7 @@
 #include "iris_crf.h"
 #include "iris_render.h"
 #include "iris_deflate.h"
+#include "iris_png.h"
 #include "iris_batch.h"
 #include "iris_optim.h"
 #include "iris_prebake.h"
@@ -1877,8 +1878,8 @@ extern "C" IRIS_API int iris_relight_shade(const iris_emitter* em, const int32_t
 // ======================================================================================================
 // OpenEXR ZIP / ZIPS scanline blocks deflated on the device (iris_deflate.h)
 // ======================================================================================================
-struct ZipLayout { int64_t n_segs, n_chunks, seg_data, seg_len, seg_adler, chunk_len, chunk_adler, chunk_off, total; int sf, st; };
-static bool zip_layout(int n_maps, int64_t n_full, int64_t block_bytes, int64_t tail_bytes, ZipLayout& z) {
+struct ZipLayout { int64_t n_segs, n_chunks, seg_data, seg_len, seg_adler, chunk_len, chunk_adler, chunk_off, seg_off, total; int sf, st; };
+static bool zip_layout(int n_maps, int64_t n_full, int64_t block_bytes, int64_t tail_bytes, ZipLayout& z, bool png = false) {
     if (n_maps <= 0 || n_full < 0 || tail_bytes < 0 || (n_full > 0 && block_bytes <= 0) || (n_full == 0 && tail_bytes == 0)) return false;
     if (block_bytes >= ((int64_t)1 << 31) - 64 || tail_bytes >= ((int64_t)1 << 31) - 64) return false;
     auto up = [](int64_t x) { return (x + 255) / 256 * 256; };
@@ -1893,7 +1894,8 @@ static bool zip_layout(int n_maps, int64_t n_full, int64_t block_bytes, int64_t 
     z.chunk_len = up(z.seg_adler + z.n_segs * 8);
     z.chunk_adler = up(z.chunk_len + z.n_chunks * 4);
     z.chunk_off = up(z.chunk_adler + z.n_chunks * 4);
-    z.total = up(z.chunk_off + z.n_chunks * 8);
+    z.seg_off = up(z.chunk_off + z.n_chunks * 8);
+    z.total = png ? up(z.seg_off + z.n_segs * 4) : z.seg_off;       // (the PNG streams also keep where each segment starts)
     return true;
 }
 extern "C" IRIS_API uint64_t iris_exr_zip_workspace_bytes(int n_maps, int64_t n_full, int64_t block_bytes, int64_t tail_bytes) {
@@ -1912,13 +1914,73 @@ extern "C" IRIS_API int iris_exr_zip_encode(const uint8_t* full, const uint8_t* 
     uint8_t* ws = (uint8_t*)workspace;
     ZipArgs a{};
     a.full = full; a.tail = tail; a.M = n_maps; a.lines = lines_per_block; a.sf = z.sf; a.st = z.st;
-    a.n_full = n_full; a.B = block_bytes; a.T = tail_bytes; a.records = records; a.map_offsets = map_offsets;
+    a.n_full = n_full; a.B = block_bytes; a.T = tail_bytes; a.records = records; a.map_offsets = map_offsets; a.record_header = 8;
     a.seg_data = ws + z.seg_data; a.seg_len = (uint32_t*)(ws + z.seg_len); a.seg_adler = (uint32_t*)(ws + z.seg_adler);
     a.chunk_len = (uint32_t*)(ws + z.chunk_len); a.chunk_adler = (uint32_t*)(ws + z.chunk_adler); a.chunk_off = (int64_t*)(ws + z.chunk_off);
     hipLaunchKernelGGL(zip_segment_kernel, dim3((unsigned)z.n_segs), dim3(kZipThreads), 0, (hipStream_t)stream, a);
     hipLaunchKernelGGL(zip_chunk_kernel, dim3((unsigned)std::min<int64_t>((z.n_chunks + 255) / 256, 8192)), dim3(256), 0, (hipStream_t)stream, a);
     hipLaunchKernelGGL(zip_offsets_kernel, dim3(1), dim3(kZipScanThreads), 0, (hipStream_t)stream, a);
     hipLaunchKernelGGL(zip_emit_kernel, dim3((unsigned)z.n_chunks), dim3(kZipThreads), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
+// ======================================================================================================
+// 8-bit PNG files on the device (iris_png.h): scanline bytes of a group of images, then one zlib stream per image
+// ======================================================================================================
+extern "C" IRIS_API void iris_png_magma_table(uint8_t* rgb) { std::memcpy(rgb, kPngMagmaHost, sizeof(kPngMagmaHost)); }
+extern "C" IRIS_API int64_t iris_png_row_bytes(int H, int W, int channels, int magma) {
+    const int64_t H2 = H - H % 2, W2 = W - W % 2;
+    if (H2 <= 0 || W2 <= 0 || (channels != 1 && channels != 3) || (magma && channels != 1)) return 0;
+    return H2 * (1 + W2 * (magma ? 3 : channels));
+}
+extern "C" IRIS_API int iris_png_rows(const void* const* images, const float* divisors, const uint8_t* magma, int n_images, int H, int W, int channels, int is_u8,
+                                    uint8_t* rows, iris_stream_t stream) {
+    if (!images || !divisors || !magma || !rows || n_images <= 0) return fail(IRIS_ERR_ARG, "iris_png_rows: bad arguments");
+    if (channels != 1 && channels != 3) return fail(IRIS_ERR_ARG, "iris_png_rows: images have 1 or 3 channels");
+    for (int m = 0; m < n_images; ++m) {
+        if (!images[m]) return fail(IRIS_ERR_ARG, "iris_png_rows: a NULL image");
+        if (magma[m] && channels != 1) return fail(IRIS_ERR_ARG, "iris_png_rows: a magma image has one channel");
+        if ((magma[m] != 0) != (magma[0] != 0)) return fail(IRIS_ERR_ARG, "iris_png_rows: the images of one call are all magma or none is (equal output sizes)");
+        if (!(divisors[m] > 0.f) || std::isinf(divisors[m])) return fail(IRIS_ERR_ARG, "iris_png_rows: a divisor is positive and finite");
+    }
+    const int64_t block = iris_png_row_bytes(H, W, channels, magma[0]);
+    if (block <= 0) return fail(IRIS_ERR_ARG, "iris_png_rows: the image cropped to even height and width is empty");
+    for (int m0 = 0; m0 < n_images; m0 += kPngMaxImages) {
+        PngRowsArgs a{};
+        a.M = std::min(kPngMaxImages, n_images - m0);
+        for (int m = 0; m < a.M; ++m) { a.img[m] = images[m0 + m]; a.div[m] = divisors[m0 + m]; a.magma |= (magma[m0 + m] ? 1u : 0u) << m; }
+        a.H = H; a.W = W; a.H2 = H - H % 2; a.W2 = W - W % 2; a.cout = magma[0] ? 3 : channels; a.block_bytes = block; a.rows = rows + (int64_t)m0 * block;
+        const int64_t n = (int64_t)a.H2 * a.W2;
+        const dim3 grid((unsigned)std::min<int64_t>((n + kPngThreads - 1) / kPngThreads, 2048), (unsigned)a.M);
+        if (channels == 3 && !is_u8) hipLaunchKernelGGL((png_rows_kernel<3, false>), grid, dim3(kPngThreads), 0, (hipStream_t)stream, a);
+        else if (channels == 3) hipLaunchKernelGGL((png_rows_kernel<3, true>), grid, dim3(kPngThreads), 0, (hipStream_t)stream, a);
+        else if (!is_u8) hipLaunchKernelGGL((png_rows_kernel<1, false>), grid, dim3(kPngThreads), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((png_rows_kernel<1, true>), grid, dim3(kPngThreads), 0, (hipStream_t)stream, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+extern "C" IRIS_API uint64_t iris_png_stream_bound(int64_t block_bytes) { return block_bytes > 0 ? (uint64_t)png_stream_bound(block_bytes) : 0; }
+extern "C" IRIS_API uint64_t iris_png_workspace_bytes(int n_images, int64_t block_bytes) {
+    ZipLayout z;
+    return zip_layout(n_images, 1, block_bytes, 0, z, true) ? (uint64_t)z.total : 0;
+}
+extern "C" IRIS_API int iris_png_encode(const uint8_t* rows, int n_images, int64_t block_bytes, uint8_t* streams, int64_t* offsets, void* workspace,
+                                      uint64_t workspace_bytes, iris_stream_t stream) {
+    ZipLayout z;
+    if (!zip_layout(n_images, 1, block_bytes, 0, z, true) || !rows || !streams || !offsets || !workspace) return fail(IRIS_ERR_ARG, "iris_png_encode: bad arguments");
+    if (workspace_bytes < (uint64_t)z.total) return fail(IRIS_ERR_ARG, "iris_png_encode: workspace smaller than iris_png_workspace_bytes()");
+    uint8_t* ws = (uint8_t*)workspace;
+    ZipArgs a{};
+    a.full = rows; a.M = n_images; a.lines = 1; a.sf = z.sf; a.st = 0; a.n_full = 1; a.B = block_bytes; a.T = 0; a.records = streams; a.map_offsets = offsets;
+    a.seg_data = ws + z.seg_data; a.seg_len = (uint32_t*)(ws + z.seg_len); a.seg_adler = (uint32_t*)(ws + z.seg_adler);
+    a.chunk_len = (uint32_t*)(ws + z.chunk_len); a.chunk_adler = (uint32_t*)(ws + z.chunk_adler); a.chunk_off = (int64_t*)(ws + z.chunk_off);
+    a.seg_off = (uint32_t*)(ws + z.seg_off); a.record_header = 0;
+    hipLaunchKernelGGL(zip_segment_kernel, dim3((unsigned)z.n_segs), dim3(kZipThreads), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(png_chunk_kernel, dim3((unsigned)n_images), dim3(kZipThreads), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(zip_offsets_kernel, dim3(1), dim3(kZipScanThreads), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(png_emit_kernel, dim3((unsigned)z.n_segs), dim3(kZipThreads), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }

@@ -9,8 +9,11 @@ HIP stages of this package.  Per view: SPP // spp rounds at (h a, w a) pixels (a
 composed scene's primary hits, the camera response model at exposure 1, the a x a box average (cv2.INTER_AREA for an integer factor), and
 {i:05d}_rgb.png (when PIL imports) + {i:05d}_rgb.exr (an addition) under --output_path.
 
-Not here: --mode traj from the dataset's own trajectory file (utils/cameras.py does not load render_traj_c2w: pass --cameras), relight.mp4, inserted obj / ply
-meshes, textures, environment maps, point lights.
+--mode traj takes its views from the scene's render trajectory (utils.cameras.load_trajectory; --cameras, when given, replaces it) and also writes
+relight.ffconcat: the frames forward and then reversed at 30 fps, the list `ffmpeg -f concat` turns into the reference's relight.mp4.  The trajectory's frames
+are used as camera-to-world matrices directly: the reference's c2w[:, :2] *= -1 only adapts them to Mitsuba's look_at and describes the same camera.
+
+Not here: relight.mp4 itself (no video encoder), inserted obj / ply meshes, textures, environment maps, point lights.
 """
 import os
 import time
@@ -135,15 +138,16 @@ def main(argv=None):
     from .utils import cameras, stage
     from .utils.exr import write_exr
     args = build_parser().parse_args(argv)
+    name, path = args.dataset
+    traj = None
     if args.mode == "traj" and not args.cameras:
-        raise L.IrisError("--mode traj: the dataset's render trajectory (render_traj_c2w) is not loaded by this package; pass the views with --cameras cameras.json")
+        traj = stage.load_trajectory(name, path, args.scene, args.res_scale, split=args.split)          # (before the device: a missing trajectory ends here)
     device = stage.open_device(args.device, "render_relight")
     print("==========================\nExp: {}\nMode: {}\nOutput: {}\nSplit: {}\n==========================".format(args.experiment_name, args.mode, args.output_path, args.split))
-    name, path = args.dataset
     verts, faces = load_mesh(stage.mesh_path(name, path, args.scene))
     emitter_state = torch.load(os.path.join(args.emitter_path, "emitter.pth"), map_location="cpu")
     lights = LT.load_light_config(args.light_cfg)
-    img_hw, views = stage.load_views(name, path, args.scene, args.res_scale, split=args.split, cameras_json=args.cameras, extras=True)
+    img_hw, views = traj or stage.load_views(name, path, args.scene, args.res_scale, split=args.split, cameras_json=args.cameras, extras=True)
     if args.max_views is not None:
         views = views[:args.max_views]
     ckpt = os.path.join(args.checkpoint_path, args.experiment_name, args.ckpt)
@@ -156,7 +160,7 @@ def main(argv=None):
     hw_aa = (img_hw[0] * a, img_hw[1] * a)
     denoiser = stage.make_denoiser(args.denoise, hw_aa, device)
     os.makedirs(args.output_path, exist_ok=True)
-    relit, t0 = None, time.time()
+    relit, t0, frames = None, time.time(), []
     for i, view in enumerate(views):
         stage.view_seed_torch(args.seed, i)
         if relit is None or lights.disco is not None:                   # the scene is recomposed per view only for the disco ball (timestep = i)
@@ -164,8 +168,11 @@ def main(argv=None):
         rays = cameras.view_rays(scaled_view(view, a), hw_aa, device, ray_diff=True)
         out = relight_view(relit, material_net, model_crf, rays, img_hw, args.SPP, args.spp, args.indir_depth, anti_aliasing=a, exposure=1.0,
                            denoise=denoiser is not None, denoiser=denoiser)
-        save_image(out["rgb_ldr"], os.path.join(args.output_path, "{:0>5d}_rgb.png".format(i)))
+        frames.append(os.path.join(args.output_path, "{:0>5d}_rgb.png".format(i)))
+        written = save_image(out["rgb_ldr"], frames[-1])
         write_exr(os.path.join(args.output_path, "{:0>5d}_rgb.exr".format(i)), out["rgb_full"].detach().cpu().numpy(), args.compression)
+    if args.mode == "traj" and frames and written:
+        stage.write_ffconcat(os.path.join(args.output_path, "relight.ffconcat"), frames)                # (render_relight.py:300-303: imgs += imgs[::-1], fps 30)
     torch.cuda.synchronize()
     print("[render_relight] {} views: {:.2f} s".format(len(views), time.time() - t0))
 

@@ -6,6 +6,7 @@ Only the pose / intrinsics part of the reference's dataset classes is needed by 
   scannetpp : {dataset_root}/data/{scene}/psdf/train_test_lists.json + transforms_all.json (nerfstudio layout: one shared
               fl_x fl_y cx cy h w, per frame an OpenGL camera-to-world), the split's list            (utils/dataset/scannetpp/dataset.py:78-141)
   generic   : a JSON file {"img_hw":[H,W], "views":[{"K":3x3, "c2w":3x4}, ...]} (OpenCV convention); a view may carry "image" and "exposure"
+and the render trajectory of the first three (load_trajectory: render_traj.npy seen through the split's camera; the datasets' load_traj=True).
 """
 import json
 import os
@@ -112,6 +113,42 @@ def load_generic(json_path, res_scale=1.0, extras=False):
                 image = os.path.join(os.path.dirname(os.path.abspath(json_path)), image)
             views[-1].update(image=image, exposure=float(v.get("exposure", 1.0)))
     return (int(h * res_scale), int(w * res_scale)), views
+
+
+def trajectory_path(dataset, root, scene=None):
+    """where a scene's render trajectory lies: <root>/render_traj.npy for synthetic (the scene folder, not the split's) and real,
+    <root>/data/<scene>/psdf/render_traj.npy for scannetpp (synthetic_ldr.py:187, real_ldr.py:205, scannetpp/dataset.py:176)"""
+    if dataset == "scannetpp":
+        return os.path.join(root, "data", scene, "psdf", "render_traj.npy")
+    return os.path.join(root, "render_traj.npy")
+
+
+def load_trajectory(dataset, root, scene, res_scale, img_hw=None, split="val"):
+    """The views of the datasets' load_traj=True (render_video.py, render_relight.py --mode traj): -> (img_hw, views), one view per frame of render_traj.npy.
+    The file holds (N,3,4) or (N,4,4) camera-to-world matrices (the top three rows are used, cast to float32 as torch.FloatTensor does); every frame is seen
+    through the loaded split's camera: the split's focal for synthetic, the FIRST view's K of the split (res_scale applied) for real and scannetpp; the image
+    size is the split's.  root, scene: as stage.mesh_path takes them.  A missing file is an IrisError naming the path, raised before anything else is read."""
+    from .. import _lib as L
+    if dataset not in ("synthetic", "real", "scannetpp"):
+        raise L.IrisError("load_trajectory: --dataset {!r}: synthetic | real | scannetpp".format(dataset))
+    path = trajectory_path(dataset, root, scene)
+    if not os.path.isfile(path):
+        raise L.IrisError("render trajectory not found: " + path)
+    traj = np.load(path)
+    if traj.ndim != 3 or tuple(traj.shape[1:]) not in ((3, 4), (4, 4)):
+        raise L.IrisError(f"{path}: expected (N,3,4) or (N,4,4) camera-to-world matrices, got {traj.shape}")
+    traj = np.ascontiguousarray(traj[:, :3, :], dtype=np.float32)
+    if dataset == "synthetic":
+        img_hw, views = load_synthetic(root, res_scale, img_hw, split=split)
+    elif dataset == "real":
+        img_hw, views = load_real(root, res_scale, img_hw, split=split)
+    else:
+        img_hw, views = load_scannetpp(root, scene, res_scale, split=split)
+    if not views:
+        raise L.IrisError(f"load_trajectory: split {split!r} has no view to take the camera from")
+    first = views[0]
+    camera = {"kind": "synthetic", "focal": first["focal"]} if dataset == "synthetic" else {"kind": "real", "K": first["K"]}
+    return img_hw, [dict(camera, c2w=c2w) for c2w in traj]
 
 
 def view_rays(view, img_hw, device, ray_diff=False):

@@ -1,7 +1,9 @@
-"""What the eleven command-line stages (slf_bake, extract_emitter_ldr, initialize, slf_refine, bake_shading, refine_shading, render, render_relight,
-train_brdf_crf, train_emitter, utils.export) do before their first kernel launches: find the mesh, list the views and their photographs, read checkpoints and the material network, build
-their parsers' shared options, open the device.  Plain functions; a stage's main() stays a linear script that calls them.  Everything down to the parser
-helpers is host code and imports without a GPU; the last six functions need one.
+"""What the twelve command-line stages (slf_bake, extract_emitter_ldr, initialize, slf_refine, bake_shading, refine_shading, render, render_video, render_relight,
+train_brdf_crf, train_emitter, utils.export) do before their first kernel launches: find the mesh, list the views and their photographs -- or the frames of the
+render trajectory (load_trajectory: render_video, render_relight --mode traj) --, read checkpoints and the material network, build their parsers' shared
+options, open the device; and, for the two stages whose frames become a video, the ffconcat list that stands where the reference's mp4 stands (write_ffconcat).
+Plain functions; a stage's main() stays a linear script that calls them.  Everything down to the parser helpers is host code and imports without a GPU; the
+last six functions need one.
 """
 import importlib
 import os
@@ -43,6 +45,30 @@ def load_views(dataset, root, scene, res_scale, split="train", cameras_json=None
     if dataset == "scannetpp":                             # Scannetpp(dataset_root, scene, split=split, pixel=False, res_scale=res_scale)
         return cameras.load_scannetpp(root, scene, res_scale, split=split)
     raise L.IrisError("--dataset {!r}: synthetic | real | scannetpp, or --cameras cameras.json".format(dataset))
+
+
+def load_trajectory(dataset, root, scene, res_scale, img_hw=None, split="val"):
+    """-> (img_hw, views) of the scene's render trajectory (utils.cameras.load_trajectory: render_traj.npy through the split's camera).  Host only: the
+    IrisError for a missing file comes before a stage opens its device."""
+    return cameras.load_trajectory(dataset, root, scene, res_scale, img_hw, split=split)
+
+
+def ffconcat_text(frames, fps=30):
+    """The list `ffmpeg -f concat` reads, standing where the reference's imageio.mimsave(..., fps=30) stands: the frames forward and then reversed
+    (imgs += imgs[::-1]: 2 N entries), each shown for 1 / fps seconds.  frames: the files' paths as the list names them (relative to the list's folder)."""
+    lines = ["ffconcat version 1.0"]
+    for f in list(frames) + list(frames)[::-1]:
+        lines += ["file '{}'".format(str(f).replace("'", "'\\''")), "duration {:.9f}".format(1.0 / fps)]
+    return "\n".join(lines) + "\n"
+
+
+def write_ffconcat(path, frames, fps=30):
+    """ffconcat_text(frames given as paths, written relative to the list's folder) -> path.  `ffmpeg -f concat -i <path> -vsync vfr -pix_fmt yuv420p out.mp4`
+    makes the reference's video on a machine that has ffmpeg; the frames' even sizes are what its encoders need."""
+    folder = os.path.dirname(os.path.abspath(path))
+    os.makedirs(folder, exist_ok=True)
+    with open(path, "w") as fh:
+        fh.write(ffconcat_text([os.path.relpath(os.path.abspath(f), folder) for f in frames], fps))
 
 
 def read_image(path, img_hw):
