@@ -10,7 +10,8 @@ import os
 import torch
 
 from . import _lib as L
-from .slf_bake import add_prebake_options, cli as _cli, extract_emitters, open_prebake
+from .slf_bake import add_prebake_options, extract_emitters, open_prebake
+from .utils.stage import exit_status
 
 
 def parser():
@@ -61,7 +62,7 @@ def main(argv=None):
 
 
 def cli(argv=None):
-    return _cli(argv, "extract_emitter_ldr", main)
+    return exit_status("extract_emitter_ldr", main, argv)
 
 
 if __name__ == "__main__":

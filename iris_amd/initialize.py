@@ -8,6 +8,7 @@ network trained towards the segment means of the albedo prior.  It writes the `i
 The stage is iris_amd.train_emitter.RadianceTrainer with mode='initialize'; what is built and what is not is said there.
 """
 from . import train_emitter as _stage
+from .utils.stage import exit_status
 
 
 def parser():
@@ -19,7 +20,7 @@ def main(argv=None):
 
 
 def cli(argv=None):
-    return _stage.cli(argv, "initialize", main)
+    return exit_status("initialize", main, argv)
 
 
 if __name__ == "__main__":

@@ -26,6 +26,7 @@ import torch.nn.functional as NF
 from . import _lib as L
 from .model.slf import VoxelSLF
 from .utils.gbuffer import pool_view
+from .utils.stage import exit_status
 
 
 def _view_args(batch, device, radiance=False, crf=None):
@@ -192,14 +193,8 @@ def main(argv=None):
     return 0
 
 
-def cli(argv=None, name="slf_bake", entry=None):
-    """main() as a process exit status: what is refused or missing is one line on stderr and status 2, not a traceback"""
-    import sys
-    try:
-        return (entry or main)(argv)
-    except (L.IrisError, FileNotFoundError) as err:
-        print(f"{name}: {err}", file=sys.stderr)
-        return 2
+def cli(argv=None):
+    return exit_status("slf_bake", main, argv)
 
 
 if __name__ == "__main__":

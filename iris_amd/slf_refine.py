@@ -5,7 +5,8 @@ import os
 import torch
 
 from . import _lib as L
-from .slf_bake import add_prebake_options, cli as _cli, open_prebake, refine_slf
+from .slf_bake import add_prebake_options, open_prebake, refine_slf
+from .utils.stage import exit_status
 
 
 def parser():
@@ -41,7 +42,7 @@ def main(argv=None):
 
 
 def cli(argv=None):
-    return _cli(argv, "slf_refine", main)
+    return exit_status("slf_refine", main, argv)
 
 
 if __name__ == "__main__":

@@ -16,62 +16,49 @@ takes the reference's arguments (configs/config.py and train_emitter.py:390-403)
 
 The batches come from a PixelSet(..., ray_diff=True) after restrict_to_hits(scene): all-valid and of a fixed size, in place of the reference's per-step
 `valid` filter (the BRDF-CRF stage's documented deviation).  The photometric term, with the response model frozen in both stages, is one
-call that returns the loss, the psnr and the gradient by L_sum (iris_amd.utils.losses.photometric_loss).  `<checkpoint_path>/<experiment_name>/last.ckpt` is
-written at the end of every epoch with `material.*` and `model_crf.*` (in the emitter mode: as loaded, so the file serves slf_refine, refine_shading and
-render as the reference's does) and `emitter.radiance`, the optimizer state, the epoch and the step.
+call that returns the loss, the psnr and the gradient by L_sum (iris_amd.utils.losses.photometric_loss).  The loop, the schedule, metrics.jsonl and
+last.ckpt are iris_amd/utils/trainer.py's; the checkpoint holds `material.*` and `model_crf.*` (in the emitter mode: as loaded, so the file serves
+slf_refine, refine_shading and render as the reference's does) and `emitter.radiance`.
 
 Not built: the in-training validation images (the reference's validation(); `python -m iris_amd.render --ckpt last.ckpt` shows the same thing), TensorBoard /
-W&B logging (the scalars go to `<log_path>/<experiment_name>/metrics.jsonl` under the reference's names), the `val/loss`-monitored best checkpoint, the
+W&B logging (the scalars go to metrics.jsonl under the reference's names), the `val/loss`-monitored best checkpoint, the
 synthetic layout's `albedo` / `roughness` ground-truth scalars, the `Ranger` optimizer, the scannetpp layout, `--res_scale` other than 1; `--val_step`,
 `--num_workers`, `--dir_val` and `--val_frame` are accepted and ignored.
 """
 import argparse
-import json
-import math
 import os
 
 import torch
 import torch.nn.functional as NF
 
 from . import _lib as L
-from .train_brdf_crf import DEFAULT_OPTIONS, make_optimizer, multistep_lr
-from .utils.stage import read_checkpoint, write_checkpoint
+from .utils import stage, trainer as base
+from .utils.stage import read_checkpoint
+from .utils.trainer import DEFAULT_OPTIONS, make_optimizer, multistep_lr          # noqa: F401  (where tools and tests look for them)
 
-# train_emitter.py:396-403, and what this trainer adds
-PROGRAM_DEFAULTS = dict(experiment_name=None, max_epochs=500, log_path="./logs", checkpoint_path="./checkpoints", resume=False, device=0, val_frame=0,
-                        log_every=50)
+PROGRAM_DEFAULTS = base.PROGRAM_DEFAULTS          # (--emor_path is the command line's, not a hyper-parameter)
 MODES = {"emitter": ("train", ("loss", "loss_c", "psnr")),                       # train_emitter.py:206-208
          "initialize": ("init", ("loss", "loss_c", "loss_a", "psnr"))}           # initialize.py:214-217
 
 
 def default_hparams(**changes):
     """a plain dict of every option with its default"""
-    hp = {name: (list(o["default"]) if isinstance(o["default"], list) else o["default"]) for name, o in DEFAULT_OPTIONS.items()}
-    hp.update(PROGRAM_DEFAULTS)
-    unknown = set(changes) - set(hp)
-    if unknown:
-        raise KeyError(f"unknown options {sorted(unknown)}")
-    hp.update(changes)
-    return hp
+    return base.default_hparams(PROGRAM_DEFAULTS, **changes)
 
 
-class RadianceTrainer:
+class RadianceTrainer(base.Trainer):
     """scene: the Scene of the mesh; emitter: an SLFEmitterLearn; material: an NGPBRDF (loaded, or init_parameters() in mode 'initialize'); model_crf: an
     EmorCRF; all on the pixel set's device (the emitter is moved there).  pixel_set: a PixelSet(ray_diff=True) with exposure (and, in mode 'initialize',
     segmentation and int_albedo) that has been through restrict_to_hits(scene).  hparams: a dict or Namespace of options (default_hparams()).
     mode: 'emitter' | 'initialize' (the module docstring).
-
-    training_step(batch) -> dict of 0-d device tensors under the names the mode logs; fit(max_epochs) runs the epochs: resample, then zero_grad / backward
-    / step per batch.  Logging, the non-finite check, checkpoints and --resume are BRDFCRFTrainer's: every `log_every` steps that step's scalars are read in
-    ONE synchronisation, appended to metrics.jsonl and to `self.history`; a non-finite loss at such a read raises FloatingPointError with the step number."""
+    training_step(batch) -> dict of 0-d device tensors under the names the mode logs; the checkpoint also holds `emitter.radiance`; everything else is
+    utils.trainer.Trainer's."""
 
     def __init__(self, scene, emitter, material, model_crf, pixel_set, hparams, mode):
         if mode not in MODES:
             raise L.IrisError(f"RadianceTrainer: mode {mode!r}, expected 'emitter' or 'initialize'")
-        hp = default_hparams()
-        given = vars(hparams) if isinstance(hparams, argparse.Namespace) else dict(hparams)
-        hp.update({k: v for k, v in given.items() if k in hp})
-        self.hparams, self.mode, self.scene, self.emitter, self.material, self.model_crf, self.ps = hp, mode, scene, emitter, material, model_crf, pixel_set
+        super().__init__(pixel_set, hparams, PROGRAM_DEFAULTS)
+        hp, self.mode, self.scene, self.emitter, self.material, self.model_crf = self.hparams, mode, scene, emitter, material, model_crf
         self.prefix, self.logged = MODES[mode]
         self.spp = int(hp["spp"])
         self.n_calls = int(hp["SPP"]) // max(self.spp, 1)
@@ -91,36 +78,16 @@ class RadianceTrainer:
         model_crf.weight.requires_grad_(False)                                   # train_emitter.py:94-95, initialize.py:86-87
         p.requires_grad_(mode == "initialize")                                   # train_emitter.py:75-76
         emitter.radiance.requires_grad_(True)
-        params = ([p] if mode == "initialize" else []) + [emitter.radiance]
-        self.optimizer = make_optimizer(hp["optimizer"], params, hp["learning_rate"], hp["weight_decay"], networks=[material] if mode == "initialize" else [])
-        self.epoch = self.global_step = 0
-        self.history = []
-        name = hp["experiment_name"]
-        self.ckpt_file = os.path.join(hp["checkpoint_path"], name, "last.ckpt") if name and hp["checkpoint_path"] else None
-        self.log_file = os.path.join(hp["log_path"], name, "metrics.jsonl") if name and hp["log_path"] else None
-        if hp["resume"] and self.ckpt_file and os.path.exists(self.ckpt_file):
-            self.load(self.ckpt_file)
+        self._start(([p] if mode == "initialize" else []) + [emitter.radiance], networks=[material] if mode == "initialize" else [])
 
-    def learning_rate(self, epoch):
-        hp = self.hparams
-        return multistep_lr(hp["learning_rate"], hp["milestones"], hp["scheduler_rate"], epoch)
+    def _extra_state(self):
+        return {"radiance": self.emitter.radiance}
 
-    def load(self, path):
-        """--resume: everything the checkpoint holds"""
-        ck = read_checkpoint(path)
+    def _load_extra(self, ck, path):
         if "radiance" not in ck["emitter"]:
             raise L.IrisError(f"{path}: the checkpoint's state_dict has no 'emitter.radiance': it was not written by this stage")
         with torch.no_grad():
-            self.material.mlp.params.copy_(ck["material"]["mlp.params"])         # (in place: the tensor the optimizer holds; the handle refreshes at the next forward)
             self.emitter.radiance.copy_(ck["emitter"]["radiance"])
-        self.model_crf.load_state_dict(ck["model_crf"])
-        self.optimizer.load_state_dict(ck["optimizer_states"][0])
-        self.epoch, self.global_step = int(ck["epoch"]), int(ck["global_step"])
-
-    def save(self, path=None):
-        hp = {k: v for k, v in self.hparams.items()}
-        write_checkpoint(path or self.ckpt_file, self.material.state_dict(), self.model_crf.state_dict(), self.optimizer.state_dict(), epoch=self.epoch,
-                         global_step=self.global_step, hyper_parameters=hp, emitter_state={"radiance": self.emitter.radiance})
 
     @staticmethod
     def _rays(batch):
@@ -157,56 +124,12 @@ class RadianceTrainer:
         loss_a = segment_albedo_loss(albedo, batch["int_albedo"], batch["segmentation"], weight=1.0, scale_invariant=False)
         return dict(loss=loss_a + out["loss_c"], loss_c=out["loss_c"], loss_a=loss_a, psnr=out["psnr"])
 
-    def _log(self, step, epoch, lr, out):
-        values = torch.stack([out[k].detach().reshape(()).to(torch.float32) for k in self.logged]).tolist()         # the one synchronisation
-        entry = {"step": step, "epoch": epoch, "lr": lr}
-        entry.update({self.prefix + "/" + k: v for k, v in zip(self.logged, values)})
-        loss = entry[self.prefix + "/loss"]
-        if not math.isfinite(loss):
-            raise FloatingPointError(f"the loss of step {step} (epoch {epoch}) is {loss}: " + json.dumps(entry))
-        self.history.append(entry)
-        if self.log_file:
-            os.makedirs(os.path.dirname(os.path.abspath(self.log_file)), exist_ok=True)
-            with open(self.log_file, "a") as fh:
-                fh.write(json.dumps(entry) + "\n")
-
-    def fit(self, max_epochs):
-        every = max(1, int(self.hparams["log_every"]))
-        for epoch in range(self.epoch, int(max_epochs)):
-            lr = self.learning_rate(epoch)
-            for group in self.optimizer.param_groups:
-                group["lr"] = lr
-            self.ps.resample()
-            for i in range(len(self.ps)):
-                out = self.training_step(self.ps[i], self.global_step)
-                self.optimizer.zero_grad(set_to_none=True)
-                out["loss"].backward()
-                self.optimizer.step()
-                self.global_step += 1
-                if self.global_step % every == 0:
-                    self._log(self.global_step - 1, epoch, lr, out)
-            self.epoch = epoch + 1
-            if self.ckpt_file:
-                self.save()
-        return self
-
 
 # ---- the command line (shared with iris_amd.initialize)
 def parser(prog="train_emitter", description="the emitter training stage"):
     ap = argparse.ArgumentParser(prog="python -m iris_amd." + prog, description=description)
-    for name, o in DEFAULT_OPTIONS.items():
-        ap.add_argument("--" + name, **o)
-    ap.add_argument("--experiment_name", type=str, required=True)
-    ap.add_argument("--max_epochs", type=int, default=PROGRAM_DEFAULTS["max_epochs"])
-    ap.add_argument("--log_path", type=str, default=PROGRAM_DEFAULTS["log_path"])
-    ap.add_argument("--ft", type=str, default=None)
-    ap.add_argument("--checkpoint_path", type=str, default=PROGRAM_DEFAULTS["checkpoint_path"])
-    ap.add_argument("--resume", dest="resume", action="store_true")
-    ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--val_frame", type=int, default=0)
-    ap.add_argument("--emor_path", type=str, default=None, help="the EMoR basis file (default: crf/emor.txt under the working directory, as the reference)")
-    ap.add_argument("--log_every", type=int, default=PROGRAM_DEFAULTS["log_every"], help="read and write the step's scalars every this many steps")
-    ap.set_defaults(resume=False)
+    base.add_trainer_options(ap)
+    stage.add_common_options(ap, "emor_path")
     return ap
 
 
@@ -215,16 +138,7 @@ def run(args, mode, stage_name):
     from .model.brdf import NGPBRDF
     from .model.crf import EmorCRF
     from .model.emitter import SLFEmitterLearn
-    from .utils import stage
-    from .utils.dataset import PixelSet
-    from .utils.dataset.files import load_training_files
-    from .utils.path_tracing import load_scene
-    dataset, root = args.dataset
-    # everything that can be refused is refused before the device is touched
-    if dataset == "scannetpp" or float(args.res_scale) != 1.0 or not args.ldr_img_dir:
-        load_training_files(dataset, root, args.ldr_img_dir, res_scale=args.res_scale)
-    if args.optimizer == "Ranger":
-        make_optimizer(args.optimizer, [], args.learning_rate, args.weight_decay, networks=())
+    stage.refuse_unbuilt_training(args)               # everything that can be refused is refused before the device is touched
     if not args.emitter_path:
         raise L.IrisError("--emitter_path is needed: the emitter.pth of python -m iris_amd.extract_emitter_ldr, whose radiance this stage trains")
     if not args.voxel_path or not os.path.isfile(args.voxel_path):
@@ -239,8 +153,7 @@ def run(args, mode, stage_name):
     print(f"{stage_name}: --val_step, --num_workers, --dir_val and --val_frame are accepted and ignored (no in-training validation images, no loader "
           "workers: the batches are made on the device)", flush=True)
     device = stage.open_device(args.device, stage_name)
-    files = load_training_files(dataset, root, args.ldr_img_dir, has_part=args.has_part, res_scale=args.res_scale, cache_dir=None, device=device)
-    scene = load_scene(files["mesh_path"], device=device)
+    files, scene, ps, n = stage.open_training_set(args, device, ray_diff=True)
     material = NGPBRDF(*stage.voxel_range(args.voxel_path))
     ck = read_checkpoint(args.ckpt_path) if args.ckpt_path else None
     if mode == "emitter":
@@ -253,11 +166,6 @@ def run(args, mode, stage_name):
         model_crf = EmorCRF(dim=args.crf_basis, emor_path=args.emor_path).to(device)        # at its defaults (initialize.py:85)
     material.to(device)
     emitter = SLFEmitterLearn(args.emitter_path, args.voxel_path).to(device)
-    ps = PixelSet(files["views"], files["img_hw"], files["rgb"], segmentation=files["segmentation"], int_albedo=files["int_albedo"], exposure=files["exposure"],
-                  synthetic=files["synthetic"], batch_size=args.batch_size, device=device, ray_diff=True)
-    n = ps.restrict_to_hits(scene)
-    if n == 0:
-        raise L.IrisError("no training pixel hits the mesh")
     trainer = RadianceTrainer(scene, emitter, material, model_crf, ps, args, mode)
     print(f"{stage_name}: {len(files['views'])} views of {files['img_hw'][0]} x {files['img_hw'][1]}, {n} pixels on the mesh, {len(ps)} steps per epoch of "
           f"{trainer.n_calls} x {trainer.spp} samples; starting at epoch {trainer.epoch}, step {trainer.global_step}", flush=True)
@@ -272,14 +180,8 @@ def main(argv=None):
     return run(parser().parse_args(argv), "emitter", "train_emitter")
 
 
-def cli(argv=None, stage_name="train_emitter", main_fn=None):
-    """main() as a process exit status: what is refused or not built is one line on stderr and status 2, not a traceback"""
-    import sys
-    try:
-        return (main_fn or main)(argv)
-    except (L.IrisError, FileNotFoundError) as err:
-        print(f"{stage_name}: {err}", file=sys.stderr)
-        return 2
+def cli(argv=None):
+    return stage.exit_status("train_emitter", main, argv)
 
 
 if __name__ == "__main__":

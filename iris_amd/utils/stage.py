@@ -1,9 +1,12 @@
 """What the twelve command-line stages (slf_bake, extract_emitter_ldr, initialize, slf_refine, bake_shading, refine_shading, render, render_video, render_relight,
 train_brdf_crf, train_emitter, utils.export) do before their first kernel launches: find the mesh, list the views and their photographs -- or the frames of the
 render trajectory (load_trajectory: render_video, render_relight --mode traj) --, read checkpoints and the material network, build their parsers' shared
-options, open the device; and, for the two stages whose frames become a video, the ffconcat list that stands where the reference's mp4 stands (write_ffconcat).
-Plain functions; a stage's main() stays a linear script that calls them.  Everything down to the parser helpers is host code and imports without a GPU; the
-last six functions need one.
+options, open the device; for the two stages whose frames become a video, the ffconcat list that stands where the reference's mp4 stands (write_ffconcat);
+for the three training stages (initialize, train_brdf_crf, train_emitter; their loop is utils/trainer.py) what their main() refuses before the device
+(refuse_unbuilt_training) and the pixel set it trains on (open_training_set); and for the six stages that end in a `cli` (the three pre-bake commands and
+the three trainers) the exit wrapper (exit_status).
+Plain functions; a stage's main() stays a linear script that calls them.  Everything down to exit_status is host code and imports without a GPU; the
+last seven functions need one.
 """
 import importlib
 import os
@@ -254,6 +257,29 @@ def add_common_options(parser, *names, **help_texts):
         parser.add_argument("--" + name, **dict(COMMON_OPTIONS[name], **({"help": help_texts[name]} if name in help_texts else {})))
 
 
+# ---- what a stage's main() opens and ends with
+def refuse_unbuilt_training(args):
+    """what every trainer's main() refuses first, before the device is touched: the dataset layouts that are not built (scannetpp, --res_scale != 1, no
+    --ldr_img_dir: load_training_files' own messages), then --optimizer Ranger (make_optimizer's)"""
+    from .dataset.files import load_training_files
+    from .trainer import make_optimizer
+    dataset, root = args.dataset
+    if dataset == "scannetpp" or float(args.res_scale) != 1.0 or not args.ldr_img_dir:
+        load_training_files(dataset, root, args.ldr_img_dir, res_scale=args.res_scale)
+    if args.optimizer == "Ranger":
+        make_optimizer(args.optimizer, [], args.learning_rate, args.weight_decay, networks=())
+
+
+def exit_status(name, main, argv=None):
+    """main(argv) as a process exit status: what is refused, missing or not built is one line on stderr and status 2, not a traceback"""
+    import sys
+    try:
+        return main(argv)
+    except (L.IrisError, FileNotFoundError) as err:
+        print(f"{name}: {err}", file=sys.stderr)
+        return 2
+
+
 # ---- needs a device
 def open_device(index, stage):
     """makes HIP device `index` (an ordinal, or a device name such as 'cuda' or 'cuda:1') the current one and returns it"""
@@ -263,6 +289,25 @@ def open_device(index, stage):
         index = L.device_index(index)
     torch.cuda.set_device(index)
     return torch.device("cuda", index)
+
+
+def open_training_set(args, device, ray_diff=True, cache_dir=None):
+    """-> (files, scene, pixel set, n): load_training_files' dict, the Scene of its mesh, and the PixelSet of its views restricted to the n pixels that hit
+    the mesh.  cache_dir: the baked shadings of the BRDF-CRF stage: attached to the pixel set, which then also keeps the hit positions."""
+    from .dataset import PixelSet
+    from .dataset.files import load_training_files
+    from .path_tracing import load_scene
+    dataset, root = args.dataset
+    files = load_training_files(dataset, root, args.ldr_img_dir, has_part=args.has_part, res_scale=args.res_scale, cache_dir=cache_dir, device=device)
+    scene = load_scene(files["mesh_path"], device=device)
+    ps = PixelSet(files["views"], files["img_hw"], files["rgb"], segmentation=files["segmentation"], int_albedo=files["int_albedo"], exposure=files["exposure"],
+                  synthetic=files["synthetic"], batch_size=args.batch_size, device=device, ray_diff=ray_diff)
+    if cache_dir is not None:
+        ps.attach_cache(files["cache"])
+    n = ps.restrict_to_hits(scene, store_positions=cache_dir is not None)
+    if n == 0:
+        raise L.IrisError("no training pixel hits the mesh")
+    return files, scene, ps, n
 
 
 def load_crf(crf_state, crf_basis, emor_path, device):

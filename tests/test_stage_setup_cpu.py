@@ -1,5 +1,5 @@
-"""The stage-setup module (iris_amd/utils/stage.py) on the CPU: the six parsers still register exactly the options they registered before the setup
-code was shared, and the one mesh rule, view loader, checkpoint reader and material loader return what the stages' own copies returned."""
+"""The stage-setup module (iris_amd/utils/stage.py) on the CPU: the eight parsers still register exactly the options they registered before the setup
+code was shared (the three trainers': before their options moved to iris_amd/utils/trainer.py), and the one mesh rule, view loader, checkpoint reader and material loader return what the stages' own copies returned."""
 import argparse
 import json
 import os
@@ -11,7 +11,8 @@ import torch
 from conftest import golden
 
 # {stage: {dest: (option strings, type, default, choices, required, nargs)}}, read off parser._actions at the commit BEFORE the parsers were rebuilt on
-# stage.add_common_options / add_ignored_trainer_options (bake_shading and refine_shading built theirs inside main() then: captured from parse_args)
+# stage.add_common_options / add_ignored_trainer_options (bake_shading and refine_shading built theirs inside main() then: captured from parse_args);
+# train_emitter and initialize: at the commit before the three trainers' parsers were rebuilt on trainer.add_trainer_options
 PARSERS = {'bake_shading': {'help': (('-h', '--help'), None, '==SUPPRESS==', None, False, 0),
                   'dataset_root': (('--dataset_root',), str, None, None, False, None),
                   'scene': (('--scene',), str, None, None, True, None),
@@ -166,6 +167,50 @@ PARSERS = {'bake_shading': {'help': (('-h', '--help'), None, '==SUPPRESS==', Non
                     'val_frame': (('--val_frame',), int, 0, None, False, None),
                     'cache_dir': (('--cache_dir',), str, None, None, False, None),
                     'log_every': (('--log_every',), int, 50, None, False, None)},
+ 'train_emitter': {'help': (('-h', '--help'), None, '==SUPPRESS==', None, False, 0),
+                   'batch_size': (('--batch_size',), int, 8192, None, False, None),
+                   'dataset': (('--dataset',), str, ['synthetic', '../data/indoor_synthetic/kitchen'], None, False, 2),
+                   'scene': (('--scene',), str, '', None, False, None),
+                   'voxel_path': (('--voxel_path',), str, 'outputs/kitchen/vslf.npz', None, False, None),
+                   'num_workers': (('--num_workers',), int, 12, None, False, None),
+                   'dir_val': (('--dir_val',), str, 'val', None, False, None),
+                   'val_step': (('--val_step',), int, 250, None, False, None),
+                   'has_part': (('--has_part',), int, 1, None, False, None),
+                   'res_scale': (('--res_scale',), float, 1.0, None, False, None),
+                   'optimizer': (('--optimizer',), str, 'Adam', ('SGD', 'Ranger', 'Adam'), False, None),
+                   'learning_rate': (('--learning_rate',), float, 0.001, None, False, None),
+                   'weight_decay': (('--weight_decay',), float, 0, None, False, None),
+                   'scheduler_rate': (('--scheduler_rate',), float, 0.5, None, False, None),
+                   'milestones': (('--milestones',), int, [1000], None, False, '*'),
+                   'le': (('--le',), float, 1.0, None, False, None),
+                   'ld': (('--ld',), float, 0.0005, None, False, None),
+                   'lp': (('--lp',), float, 0.005, None, False, None),
+                   'ls': (('--ls',), float, 0.001, None, False, None),
+                   'la': (('--la',), float, 0.0, None, False, None),
+                   'sigma_albedo': (('--sigma_albedo',), float, 0.016666666666666666, None, False, None),
+                   'sigma_pos': (('--sigma_pos',), float, 0.09999999999999999, None, False, None),
+                   'ckpt_path': (('--ckpt_path',), str, None, None, False, None),
+                   'emitter_path': (('--emitter_path',), str, None, None, False, None),
+                   'freeze_emitter': (('--freeze_emitter',), int, 0, None, False, None),
+                   'freeze_crf': (('--freeze_crf',), int, 0, None, False, None),
+                   'indir_depth': (('--indir_depth',), int, 5, None, False, None),
+                   'SPP': (('--SPP',), int, 512, None, False, None),
+                   'spp': (('--spp',), int, 8, None, False, None),
+                   'ldr_img_dir': (('--ldr_img_dir',), str, None, None, False, None),
+                   'crf_basis': (('--crf_basis',), int, 3, None, False, None),
+                   'load_crf': (('--load_crf',), int, 0, None, False, None),
+                   'l_crf_increasing': (('--l_crf_increasing',), float, 0.1, None, False, None),
+                   'l_crf_weight': (('--l_crf_weight',), float, 0.001, None, False, None),
+                   'experiment_name': (('--experiment_name',), str, None, None, True, None),
+                   'max_epochs': (('--max_epochs',), int, 500, None, False, None),
+                   'log_path': (('--log_path',), str, './logs', None, False, None),
+                   'ft': (('--ft',), str, None, None, False, None),
+                   'checkpoint_path': (('--checkpoint_path',), str, './checkpoints', None, False, None),
+                   'resume': (('--resume',), None, False, None, False, 0),
+                   'device': (('--device',), int, 0, None, False, None),
+                   'val_frame': (('--val_frame',), int, 0, None, False, None),
+                   'emor_path': (('--emor_path',), str, None, None, False, None),
+                   'log_every': (('--log_every',), int, 50, None, False, None)},
  'export': {'help': (('-h', '--help'), None, '==SUPPRESS==', None, False, 0),
             'mesh': (('--mesh',), None, None, None, False, None),
             'ckpt': (('--ckpt',), None, None, None, False, None),
@@ -177,20 +222,25 @@ PARSERS = {'bake_shading': {'help': (('-h', '--help'), None, '==SUPPRESS==', Non
             'material': (('--material',), str, None, None, False, None),
             'atlas': (('--atlas',), str, 'auto', ('auto', 'files', 'grid'), False, None),
             'write_obj': (('--write_obj',), None, False, None, False, 0)}}
+PARSERS['initialize'] = PARSERS['train_emitter']          # captured apart at the same commit: the two tables were equal option for option
 
 
 def _table(parser):
     return {a.dest: (tuple(a.option_strings), a.type, a.default, None if a.choices is None else tuple(a.choices), a.required, a.nargs) for a in parser._actions}
 
 
-def test_the_six_parsers_register_what_they_registered_before():
-    from iris_amd import bake_shading, refine_shading, render, render_relight, train_brdf_crf
+def test_the_eight_parsers_register_what_they_registered_before():
+    """the six stages of the setup module's first round, and train_emitter and initialize; option order is free, everything else is not"""
+    from iris_amd import bake_shading, initialize, refine_shading, render, render_relight, train_brdf_crf, train_emitter
     from iris_amd.utils import export
     built = {"bake_shading": bake_shading.build_parser(), "refine_shading": refine_shading.build_parser(), "render": render.build_parser(),
-             "render_relight": render_relight.build_parser(), "train_brdf_crf": train_brdf_crf.parser(), "export": export.build_parser()}
+             "render_relight": render_relight.build_parser(), "train_brdf_crf": train_brdf_crf.parser(), "train_emitter": train_emitter.parser(),
+             "initialize": initialize.parser(), "export": export.build_parser()}
     assert set(built) == set(PARSERS)
     for name, parser in built.items():
         assert _table(parser) == PARSERS[name], name
+    for name in ("train_brdf_crf", "train_emitter", "initialize"):
+        assert built[name].prog == "python -m iris_amd." + name
 
 
 # ---- mesh_path
