@@ -574,6 +574,23 @@ IRIS_API int iris_png_encode(const uint8_t *rows, int n_images, int64_t block_by
                     uint64_t workspace_bytes, iris_stream_t);
 IRIS_API void iris_png_magma_table(uint8_t *rgb);
 
+/* ---- baseline JPEG frames, device half (render_video.py --video mjpeg; utils/jpeg.py; the contract: DESIGN.md 5c-14) ----------------- */
+/* iris_jpeg_encode: n_images equal-size images as iris_png_rows takes them (the same quantiser, MAGMA table and even crop (H2, W2); magma per image) -> the
+ * entropy-coded data of one baseline JPEG each: Y Cb Cr at 2x2 1x1 1x1 whatever the input (a grey map has Cb = Cr = 128), integer colour conversion and DCT,
+ * the Annex K tables scaled by `quality` (1..100, the IJG rule), one restart interval per MCU row (byte-aligned with 1-bits, FF -> FF 00, RSTm after every
+ * interval but the last).  streams (device) receives the data back to back -- what stands between the SOS header and EOI --, offsets (device int64,
+ * n_images + 1) where each starts and, last, their total size.  streams must hold n_images * iris_jpeg_stream_bound(H, W) bytes: per MCU row twice the
+ * longest bit string the tables can produce (22 bits for a DC and 26 for each of 63 AC coefficients per block, six blocks per MCU) plus the marker -- many
+ * times the raw image, so copy offsets first and then the used bytes.  workspace: iris_jpeg_workspace_bytes() bytes.  Both return 0 for an unsupported size
+ * (an empty crop, more than 65535 pixels a side).  One launch per 16 images and four more on the stream, no host round trip.
+ * iris_jpeg_tables (HOST pointer, 604 bytes): the luma and chroma quantisation tables of Annex K in natural order (2 x 64), the natural index of every
+ * zigzag position (64), then BITS (16) and HUFFVAL of the tables DC luma (12), AC luma (162), DC chroma (12), AC chroma (162): what the file's headers hold. */
+IRIS_API uint64_t iris_jpeg_stream_bound(int H, int W);
+IRIS_API uint64_t iris_jpeg_workspace_bytes(int n_images, int H, int W);
+IRIS_API int iris_jpeg_encode(const void *const *images, const float *divisors, const uint8_t *magma, int n_images, int H, int W, int channels, int is_u8,
+                     int quality, uint8_t *streams, int64_t *offsets, void *workspace, uint64_t workspace_bytes, iris_stream_t);
+IRIS_API void iris_jpeg_tables(uint8_t *out);
+
 /* ---- misc --------------------------------------------------------------------------------------------- */
 /* Philox uniforms exactly as the bake kernels draw them (for tests): u2[i] = U(seed, idx0+i, stream_id). */
 IRIS_API int iris_philox_u2(uint64_t seed, uint64_t idx0, uint32_t stream_id, int64_t n, float *u2, iris_stream_t);

@@ -142,6 +142,10 @@ PROTOTYPES = {
     "iris_png_workspace_bytes": [_I32, _I64],
     "iris_png_encode": [_P, _I32, _I64, _P, _P, _P, _U64, _P],
     "iris_png_magma_table": [_P],
+    "iris_jpeg_stream_bound": [_I32, _I32],
+    "iris_jpeg_workspace_bytes": [_I32, _I32, _I32],
+    "iris_jpeg_encode": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _U64, _P],
+    "iris_jpeg_tables": [_P],
     "iris_bake_tile_max_spp": [],
     "iris_last_error": [],
     "iris_version": [],
@@ -151,6 +155,7 @@ _RESTYPE = {"iris_scene_destroy": None, "iris_slf_destroy": None, "iris_emitter_
             "iris_exr_zip_workspace_bytes": C.c_uint64, "iris_ngp_backward_workspace_bytes": C.c_uint64, "iris_crf_bwd_workspace_bytes": C.c_uint64,
             "iris_loss_photometric_workspace_bytes": C.c_uint64,
             "iris_png_row_bytes": C.c_int64, "iris_png_stream_bound": C.c_uint64, "iris_png_workspace_bytes": C.c_uint64, "iris_png_magma_table": None,
+            "iris_jpeg_stream_bound": C.c_uint64, "iris_jpeg_workspace_bytes": C.c_uint64, "iris_jpeg_tables": None,
             "iris_image_metrics_workspace_bytes": C.c_uint64, "iris_uv_raster_workspace_bytes": C.c_uint64}
 
 _lib = None

@@ -31,6 +31,7 @@
 #include "iris_render.h"
 #include "iris_deflate.h"
 #include "iris_png.h"
+#include "iris_jpeg.h"
 #include "iris_batch.h"
 #include "iris_optim.h"
 #include "iris_prebake.h"
@@ -1981,6 +1982,91 @@ extern "C" IRIS_API int iris_png_encode(const uint8_t* rows, int n_images, int64
     hipLaunchKernelGGL(png_chunk_kernel, dim3((unsigned)n_images), dim3(kZipThreads), 0, (hipStream_t)stream, a);
     hipLaunchKernelGGL(zip_offsets_kernel, dim3(1), dim3(kZipScanThreads), 0, (hipStream_t)stream, a);
     hipLaunchKernelGGL(png_emit_kernel, dim3((unsigned)z.n_segs), dim3(kZipThreads), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
+// ======================================================================================================
+// Baseline JPEG frames on the device (iris_jpeg.h): the entropy-coded data of a group of equal-size images
+// ======================================================================================================
+struct JpegLayout { int H2, W2, mx, my; int64_t n_blocks, n_intervals, cap, coef, slots, bit_len, bit_off, cat, ivl_bytes, ivl_len, ivl_off, total; };
+static bool jpeg_layout(int n_images, int H, int W, JpegLayout& z) {
+    z.H2 = H - H % 2; z.W2 = W - W % 2;
+    if (n_images <= 0 || z.H2 <= 0 || z.W2 <= 0 || z.H2 > 65535 || z.W2 > 65535) return false;        // (SOF0 holds the sizes in 16 bits)
+    z.mx = (z.W2 + 15) / 16; z.my = (z.H2 + 15) / 16;
+    z.cap = z.my * jpeg_interval_bound(z.mx);
+    z.n_intervals = (int64_t)n_images * z.my;
+    z.n_blocks = z.n_intervals * z.mx * 6;
+    if (z.cap >= ((int64_t)1 << 31) || z.n_blocks >= ((int64_t)1 << 31)) return false;
+    auto up = [](int64_t x) { return (x + 255) / 256 * 256; };
+    z.coef = 0;
+    z.slots = up(z.coef + z.n_blocks * 64 * 2);
+    z.bit_len = up(z.slots + z.n_blocks * kJpegSlotWords * 4);
+    z.bit_off = up(z.bit_len + z.n_blocks * 4);
+    z.cat = up(z.bit_off + z.n_blocks * 4);
+    z.ivl_bytes = up(z.cat + z.n_intervals * jpeg_interval_words(z.mx) * 4);
+    z.ivl_len = up(z.ivl_bytes + z.n_intervals * 4);
+    z.ivl_off = up(z.ivl_len + z.n_intervals * 4);
+    z.total = up(z.ivl_off + z.n_intervals * 8);
+    return true;
+}
+extern "C" IRIS_API void iris_jpeg_tables(uint8_t* out) {
+    std::memcpy(out, kJpegQuantHost, 128);
+    std::memcpy(out + 128, kJpegZigHost.nat, 64);
+    out += 192;
+    for (const JpegSpec* s : {&kJpegDcLuma, &kJpegAcLuma, &kJpegDcChroma, &kJpegAcChroma}) {
+        std::memcpy(out, s->bits, 16);
+        std::memcpy(out + 16, s->vals, s->n);
+        out += 16 + s->n;
+    }
+}
+extern "C" IRIS_API uint64_t iris_jpeg_stream_bound(int H, int W) {
+    JpegLayout z;
+    return jpeg_layout(1, H, W, z) ? (uint64_t)z.cap : 0;
+}
+extern "C" IRIS_API uint64_t iris_jpeg_workspace_bytes(int n_images, int H, int W) {
+    JpegLayout z;
+    return jpeg_layout(n_images, H, W, z) ? (uint64_t)z.total : 0;
+}
+extern "C" IRIS_API int iris_jpeg_encode(const void* const* images, const float* divisors, const uint8_t* magma, int n_images, int H, int W, int channels, int is_u8,
+                                       int quality, uint8_t* streams, int64_t* offsets, void* workspace, uint64_t workspace_bytes, iris_stream_t stream) {
+    JpegLayout z;
+    if (!images || !divisors || !magma || !streams || !offsets || !workspace || n_images <= 0) return fail(IRIS_ERR_ARG, "iris_jpeg_encode: bad arguments");
+    if (channels != 1 && channels != 3) return fail(IRIS_ERR_ARG, "iris_jpeg_encode: images have 1 or 3 channels");
+    if (quality < 1 || quality > 100) return fail(IRIS_ERR_ARG, "iris_jpeg_encode: the quality is 1..100");
+    for (int m = 0; m < n_images; ++m) {
+        if (!images[m]) return fail(IRIS_ERR_ARG, "iris_jpeg_encode: a NULL image");
+        if (magma[m] && channels != 1) return fail(IRIS_ERR_ARG, "iris_jpeg_encode: a magma image has one channel");
+        if (!(divisors[m] > 0.f) || std::isinf(divisors[m])) return fail(IRIS_ERR_ARG, "iris_jpeg_encode: a divisor is positive and finite");
+    }
+    if (!jpeg_layout(n_images, H, W, z)) return fail(IRIS_ERR_ARG, "iris_jpeg_encode: the image cropped to even height and width is empty, or too large");
+    if (workspace_bytes < (uint64_t)z.total) return fail(IRIS_ERR_ARG, "iris_jpeg_encode: workspace smaller than iris_jpeg_workspace_bytes()");
+    uint8_t* ws = (uint8_t*)workspace;
+    const int64_t per_image = (int64_t)z.my * z.mx * 6;
+    for (int m0 = 0; m0 < n_images; m0 += kPngMaxImages) {
+        JpegTransformArgs a{};
+        a.M = std::min(kPngMaxImages, n_images - m0);
+        for (int m = 0; m < a.M; ++m) { a.img[m] = images[m0 + m]; a.div[m] = divisors[m0 + m]; a.magma |= (magma[m0 + m] ? 1u : 0u) << m; }
+        a.H = H; a.W = W; a.H2 = z.H2; a.W2 = z.W2; a.mx = z.mx; a.my = z.my;
+        a.scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+        a.coef = (int16_t*)(ws + z.coef) + (int64_t)m0 * per_image * 64;
+        const dim3 grid((unsigned)((per_image + kJpegThreads / 64 - 1) / (kJpegThreads / 64)), (unsigned)a.M);
+        if (channels == 3 && !is_u8) hipLaunchKernelGGL((jpeg_transform_kernel<3, false>), grid, dim3(kJpegThreads), 0, (hipStream_t)stream, a);
+        else if (channels == 3) hipLaunchKernelGGL((jpeg_transform_kernel<3, true>), grid, dim3(kJpegThreads), 0, (hipStream_t)stream, a);
+        else if (!is_u8) hipLaunchKernelGGL((jpeg_transform_kernel<1, false>), grid, dim3(kJpegThreads), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((jpeg_transform_kernel<1, true>), grid, dim3(kJpegThreads), 0, (hipStream_t)stream, a);
+    }
+    JpegArgs a{};
+    a.mx = z.mx; a.my = z.my; a.n_blocks = z.n_blocks; a.n_intervals = z.n_intervals;
+    a.coef = (const int16_t*)(ws + z.coef); a.slots = (uint32_t*)(ws + z.slots); a.bit_len = (uint32_t*)(ws + z.bit_len); a.bit_off = (uint32_t*)(ws + z.bit_off);
+    a.cat = (uint32_t*)(ws + z.cat); a.ivl_bytes = (uint32_t*)(ws + z.ivl_bytes); a.ivl_len = (uint32_t*)(ws + z.ivl_len); a.ivl_off = (int64_t*)(ws + z.ivl_off);
+    a.streams = streams;
+    ZipArgs s{};                                                    // zip_offsets_kernel: an interval is a chunk, an image a map; no record header
+    s.M = n_images; s.n_full = z.my; s.T = 0; s.record_header = 0; s.chunk_len = a.ivl_len; s.chunk_off = a.ivl_off; s.map_offsets = offsets;
+    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((z.n_blocks + kJpegThreads - 1) / kJpegThreads)), dim3(kJpegThreads), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(jpeg_assemble_kernel, dim3((unsigned)z.n_intervals), dim3(kZipThreads), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(zip_offsets_kernel, dim3(1), dim3(kZipScanThreads), 0, (hipStream_t)stream, s);
+    hipLaunchKernelGGL(jpeg_emit_kernel, dim3((unsigned)z.n_intervals), dim3(kZipThreads), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }

@@ -12,8 +12,10 @@ composed scene's primary hits, the camera response model at exposure 1, the a x 
 --mode traj takes its views from the scene's render trajectory (utils.cameras.load_trajectory; --cameras, when given, replaces it) and also writes
 relight.ffconcat: the frames forward and then reversed at 30 fps, the list `ffmpeg -f concat` turns into the reference's relight.mp4.  The trajectory's frames
 are used as camera-to-world matrices directly: the reference's c2w[:, :2] *= -1 only adapts them to Mitsuba's look_at and describes the same camera.
+With --video mjpeg (default none; --video_quality, default 90) it also writes relight.avi, a Motion-JPEG file of the same frames in the same order, the JPEG
+frames encoded on the device (utils/jpeg.py, utils/avi.py; render_video.py does the same for its eight files).
 
-Not here: relight.mp4 itself (no video encoder), inserted obj / ply meshes, textures, environment maps, point lights.
+Not here: relight.mp4 itself (no H.264 encoder), inserted obj / ply meshes, textures, environment maps, point lights.
 """
 import os
 import time
@@ -134,10 +136,19 @@ def build_parser():
     return parser
 
 
+def build_video_parser():
+    """build_parser() and the two options of the video stage, --video and --video_quality: what main() parses.  They stand apart because build_parser()'s
+    option table is pinned entry for entry (tests/test_stage_setup_cpu.py) as the table of the options this stage had before it could write a video."""
+    from .utils import stage
+    parser = build_parser()
+    stage.add_common_options(parser, "video", "video_quality", video=stage.COMMON_OPTIONS["video"]["help"] + " (--mode traj: relight.avi beside relight.ffconcat)")
+    return parser
+
+
 def main(argv=None):
     from .utils import cameras, stage
     from .utils.exr import write_exr
-    args = build_parser().parse_args(argv)
+    args = build_video_parser().parse_args(argv)
     name, path = args.dataset
     traj = None
     if args.mode == "traj" and not args.cameras:
@@ -160,7 +171,7 @@ def main(argv=None):
     hw_aa = (img_hw[0] * a, img_hw[1] * a)
     denoiser = stage.make_denoiser(args.denoise, hw_aa, device)
     os.makedirs(args.output_path, exist_ok=True)
-    relit, t0, frames = None, time.time(), []
+    relit, t0, frames, video = None, time.time(), [], None
     for i, view in enumerate(views):
         stage.view_seed_torch(args.seed, i)
         if relit is None or lights.disco is not None:                   # the scene is recomposed per view only for the disco ball (timestep = i)
@@ -170,9 +181,17 @@ def main(argv=None):
                            denoise=denoiser is not None, denoiser=denoiser)
         frames.append(os.path.join(args.output_path, "{:0>5d}_rgb.png".format(i)))
         written = save_image(out["rgb_ldr"], frames[-1])
+        if args.mode == "traj" and args.video == "mjpeg":
+            from .utils import avi, jpeg
+            ldr = out["rgb_ldr"].detach()
+            if video is None:
+                video = avi.AviWriter(os.path.join(args.output_path, "relight.avi"), ldr.shape[1] - ldr.shape[1] % 2, ldr.shape[0] - ldr.shape[0] % 2, 30)
+            video.add_frame(jpeg.encode_frames_device([ldr], quality=args.video_quality)[0])
         write_exr(os.path.join(args.output_path, "{:0>5d}_rgb.exr".format(i)), out["rgb_full"].detach().cpu().numpy(), args.compression)
     if args.mode == "traj" and frames and written:
         stage.write_ffconcat(os.path.join(args.output_path, "relight.ffconcat"), frames)                # (render_relight.py:300-303: imgs += imgs[::-1], fps 30)
+    if video is not None:
+        video.close(reverse=True)
     torch.cuda.synchronize()
     print("[render_relight] {} views: {:.2f} s".format(len(views), time.time() - t0))
 

@@ -13,9 +13,12 @@ The PNG files are made on the device by default (--png_encoder device, utils/png
 equal-size maps, the EXR writer's deflate kernels in zlib-stream mode, one device-to-host copy); FrameWriter overlaps that copy, the CRC and the file writes of
 frame i with the render of frame i + 1.  --png_encoder host quantises in numpy and compresses with zlib on writer threads.  Both decode to the same pixels.
 
-The .mp4 files are NOT made: there is no video encoder here.  In their place the stage writes eight lists, <output_path>/<name>.ffconcat (rgb_full, kd, a_prime,
-roughness, roughness_color, metallic, metallic_color, emission): the frames forward and then reversed at 30 fps, as the reference's imgs += imgs[::-1] and
-mimsave(fps=30).  `ffmpeg -f concat -i rgb_full.ffconcat -pix_fmt yuv420p rgb_full.mp4` produces the reference's video on any machine that has ffmpeg.
+The videos are made with --video mjpeg: eight Motion-JPEG files <output_path>/<name>.avi (rgb_full, kd, a_prime, roughness, roughness_color, metallic,
+metallic_color, emission) where the reference's <name>.mp4 stand -- the frames forward and then reversed at 30 fps, as the reference's imgs += imgs[::-1] and
+mimsave(fps=30).  Each frame is a baseline JPEG of exactly the pixels of the frame's PNG file, encoded on the device (utils/jpeg.py, --video_quality, default
+90) and appended to its file as it arrives (utils/avi.py); ffmpeg, VLC and mpv play them.  The default, --video none, writes none of them.  Either way the
+stage writes eight lists, <output_path>/<name>.ffconcat, of the PNG frames in the same order: `ffmpeg -f concat -i rgb_full.ffconcat -pix_fmt yuv420p
+rgb_full.mp4` produces the reference's H.264 video on any machine that has ffmpeg (there is no H.264 encoder here).
 Not here either: --light_type area (AreaEmitter), as in the render stage.
 """
 import os
@@ -43,12 +46,21 @@ class FrameWriter:
     """A frame's eight maps -> eight PNG files, off the critical path.  encoder "device": submit() enqueues utils.png.enqueue_frames_device and one
     device-to-host copy into a pinned buffer on a side stream and returns; a writer thread waits for the copy's event, wraps the streams (CRC-32) and writes.
     encoder "host": submit() enqueues the copy of the float maps; the writer threads quantise (utils.png.quantize_host) and compress (zlib level 1).
-    Two buffer sets: a third frame waits for the first one's files.  Files appear under their final name only when complete."""
+    Two buffer sets: a third frame waits for the first one's files.  Files appear under their final name only when complete.
+    video "mjpeg": submit() also enqueues utils.jpeg.enqueue_frames_device and the copy of the stream offsets on the side stream; ONE video thread (frames
+    enter a file in order) waits for that copy, enqueues the copy of exactly the used bytes, waits for it and appends the eight JPEG files to
+    <output_path>/<name>.avi (utils.avi.AviWriter); close() finishes the eight files."""
 
-    def __init__(self, device, encoder="device", n_buffers=2, level=1):
+    def __init__(self, device, encoder="device", n_buffers=2, level=1, video="none", video_quality=90):
         from concurrent.futures import ThreadPoolExecutor
         if encoder not in ("host", "device"):
             raise L.IrisError(f"FrameWriter: encoder {encoder!r} is not 'host' or 'device'")
+        if video not in ("none", "mjpeg"):
+            raise L.IrisError(f"FrameWriter: video {video!r} is not 'none' or 'mjpeg'")
+        self.video, self.video_quality, self.device = video, video_quality, device
+        if video == "mjpeg":
+            self.video_pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="video")
+            self.video_busy, self.video_heads, self.video_data, self.avis = [None] * n_buffers, [None] * n_buffers, None, None
         self.encoder, self.level, self.n_buffers = encoder, level, n_buffers
         self.stream = torch.cuda.Stream(device=device)
         self.bufs = [None] * n_buffers
@@ -103,7 +115,46 @@ class FrameWriter:
                 done.synchronize()
                 replace(path, png.encode_png_host(png.quantize_host(maps[key], divisor, magma), self.level))
             self.busy[slot] = [self.pool.submit(write, p, key, d, m) for p, (_, _, key, d, m) in zip(paths, FRAME_FILES)]
+        if self.video == "mjpeg":
+            self._submit_video(output_path, slot, out)
         return paths
+
+    def _submit_video(self, output_path, slot, out):
+        from .utils import avi, jpeg
+        if self.video_busy[slot] is not None:
+            self.video_busy[slot].result()                  # this slot's offsets buffer is free again (re-raises the video thread's exception)
+        buf, layout = jpeg.enqueue_frames_device([out[key] for _, _, key, _, _ in FRAME_FILES], [d for _, _, _, d, _ in FRAME_FILES], [m for _, _, _, _, m in FRAME_FILES],
+                                                 self.video_quality)
+        if self.avis is None:
+            sizes = {i: (g["width"], g["height"]) for g in layout["groups"] for i in g["indices"]}
+            self.avis = [avi.AviWriter(os.path.join(output_path, name + ".avi"), *sizes[k], FPS) for k, (_, name, _, _, _) in enumerate(FRAME_FILES)]
+        if self.video_heads[slot] is None or self.video_heads[slot].numel() < layout["head"]:
+            self.video_heads[slot] = torch.empty(layout["head"], dtype=torch.uint8).pin_memory()
+        head = self.video_heads[slot][:layout["head"]]
+        ready = torch.cuda.Event(); ready.record()
+        head_done = torch.cuda.Event()
+        with torch.cuda.stream(self.stream):
+            self.stream.wait_event(ready)
+            head.copy_(buf[:layout["head"]], non_blocking=True)
+            buf.record_stream(self.stream)
+            head_done.record(self.stream)
+
+        def append():
+            head_done.synchronize()
+            sizes = jpeg.group_sizes(head.numpy(), layout)
+            if self.video_data is None or self.video_data.numel() < sum(sizes):
+                self.video_data = torch.empty(sum(sizes), dtype=torch.uint8).pin_memory()
+            data, o = [], 0
+            with torch.cuda.device(self.device), torch.cuda.stream(self.stream):      # (after the offsets' copy on that stream, so after the encoder)
+                for g, size in zip(layout["groups"], sizes):
+                    data.append(self.video_data[o:o + size])
+                    data[-1].copy_(buf[g["pos"]:g["pos"] + size], non_blocking=True)
+                    o += size
+                done = torch.cuda.Event(); done.record(self.stream)
+            done.synchronize()
+            for w, f in zip(self.avis, jpeg.files_from_host(head.numpy(), [d.numpy() for d in data], layout, len(FRAME_FILES))):
+                w.add_frame(f)
+        self.video_busy[slot] = self.video_pool.submit(append)
 
     def close(self):
         for fs in self.busy:
@@ -111,6 +162,15 @@ class FrameWriter:
                 f.result()
         self.busy = [[] for _ in range(self.n_buffers)]
         self.pool.shutdown()
+        if self.video == "mjpeg":
+            busy, self.video_busy = self.video_busy, [None] * self.n_buffers
+            for f in busy:
+                if f is not None:
+                    f.result()
+            self.video_pool.shutdown()
+            avis, self.avis = self.avis or [], None
+            for w in avis:
+                w.close(reverse=True)
 
 
 def write_lists(output_path, n_frames):
@@ -150,6 +210,7 @@ def build_parser():
     stage.add_common_options(parser, "material", "emor_path", "denoise", "seed", "max_views", max_views="render only the first N frames of the trajectory")
     parser.add_argument("--png_encoder", type=str, default="device", choices=["device", "host"], help="where the eight PNG files of a frame are encoded: on the GPU "
                         "(default; larger files, matches at distance 1 only) or with zlib on host threads; both decode to the same pixels")
+    stage.add_common_options(parser, "video", "video_quality")
     return parser
 
 
@@ -175,7 +236,7 @@ def main(argv=None):
     model_crf = stage.load_crf(stage.read_checkpoint(ckpt)["model_crf"], args.crf_basis, args.emor_path, device)
     stage.freeze(material_net, emitter_net, model_crf)
     denoiser = stage.make_denoiser(args.denoise, img_hw, device)
-    writer = FrameWriter(device, args.png_encoder)
+    writer = FrameWriter(device, args.png_encoder, video=args.video, video_quality=args.video_quality)
     t0 = time.time()
     try:
         for i, view in enumerate(views):

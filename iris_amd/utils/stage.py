@@ -242,6 +242,9 @@ COMMON_OPTIONS = {
     "seed": dict(type=int, default=0),
     "max_views": dict(type=int, default=None),
     "exr_encoder": dict(type=str, default="host", choices=["host", "device"]),
+    "video": dict(type=str, default="none", choices=["none", "mjpeg"], help="mjpeg: the trajectory's frames also as Motion-JPEG .avi files, the JPEG frames encoded "
+                  "on the GPU (utils/jpeg.py, utils/avi.py); none (default): the frames and the .ffconcat lists only"),
+    "video_quality": dict(type=int, default=90, choices=range(1, 101), metavar="Q", help="JPEG quality of --video mjpeg, 1..100 (the IJG scaling of the standard tables)"),
 }
 
 
