@@ -591,6 +591,24 @@ IRIS_API int iris_jpeg_encode(const void *const *images, const float *divisors, 
                      int quality, uint8_t *streams, int64_t *offsets, void *workspace, uint64_t workspace_bytes, iris_stream_t);
 IRIS_API void iris_jpeg_tables(uint8_t *out);
 
+/* ---- 8-bit image resize, device half (the scannetpp layout's --res_scale; utils/resize.py; the contract: DESIGN.md 5c-15) ----------------- */
+/* iris_resize_tables (HOST function, HOST pointers, no device needed): one axis of ns source and nd destination samples (1..65535 each) -> ofs (nd) the
+ * first source index of every destination sample and, for IRIS_RESIZE_LINEAR, coef (nd, 2) the int16 weights of that sample and the next (index
+ * min(s + 1, ns - 1)); IRIS_RESIZE_NEAREST fills ofs only (coef may be NULL).
+ *   linear: OpenCV's 8-bit INTER_LINEAR: scale = 1 / (nd / ns) in double, f = float32((d + 0.5) scale - 0.5), s = floor(f), f = float32(f - s); s < 0 -> s = 0,
+ *           f = 0; s >= ns - 1 -> s = ns - 1, f = 0; weights rint(float32(1 - f) 2048), rint(f 2048), half to even.
+ *   nearest: PIL's Image.NEAREST: a = ns / nd in double, x = a / 2, then per sample in order index min(floor(x), ns - 1) and x += a (accumulated addition).
+ * iris_resize_u8: n_images equal-size uint8 images (Hs, Ws, channels), channels 1 or 3 interleaved, device pointers in a HOST array (they travel in the
+ * kernel arguments, as iris_png_rows') -> out (device): n_images blocks of Ht * Wt * channels bytes.  The tables are DEVICE copies of
+ * iris_resize_tables' for (Ws, Wt) and (Hs, Ht).  Linear: horizontal R = S[s] w0 + S[s+1] w1 in int32, vertical
+ * (((b0 (R0 >> 4)) >> 16) + ((b1 (R1 >> 4)) >> 16) + 2) >> 2; when Hs == 2 Ht and Ws == 2 Wt (both) the library takes OpenCV's exact-2 path itself,
+ * (a + b + c + d + 2) >> 2 over each 2 x 2 block, and the tables are unused (may be NULL).  Nearest: out[y][x] = S[yofs[y]][xofs[x]]; the weights are
+ * unused.  All-integer and free of atomics: bitwise reproducible.  One launch per 16 images, no host round trip. */
+enum { IRIS_RESIZE_LINEAR = 0, IRIS_RESIZE_NEAREST = 1 };
+IRIS_API int iris_resize_tables(int mode, int ns, int nd, int32_t *ofs, int16_t *coef);
+IRIS_API int iris_resize_u8(const void *const *images, int n_images, int Hs, int Ws, int channels, int mode, const int32_t *xofs, const int16_t *xcoef,
+                   const int32_t *yofs, const int16_t *ycoef, uint8_t *out, int Ht, int Wt, iris_stream_t);
+
 /* ---- misc --------------------------------------------------------------------------------------------- */
 /* Philox uniforms exactly as the bake kernels draw them (for tests): u2[i] = U(seed, idx0+i, stream_id). */
 IRIS_API int iris_philox_u2(uint64_t seed, uint64_t idx0, uint32_t stream_id, int64_t n, float *u2, iris_stream_t);

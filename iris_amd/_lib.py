@@ -146,6 +146,8 @@ PROTOTYPES = {
     "iris_jpeg_workspace_bytes": [_I32, _I32, _I32],
     "iris_jpeg_encode": [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _U64, _P],
     "iris_jpeg_tables": [_P],
+    "iris_resize_tables": [_I32, _I32, _I32, _P, _P],
+    "iris_resize_u8": [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P],
     "iris_bake_tile_max_spp": [],
     "iris_last_error": [],
     "iris_version": [],

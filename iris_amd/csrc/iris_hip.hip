@@ -32,6 +32,7 @@
 #include "iris_deflate.h"
 #include "iris_png.h"
 #include "iris_jpeg.h"
+#include "iris_resize.h"
 #include "iris_batch.h"
 #include "iris_optim.h"
 #include "iris_prebake.h"
@@ -2067,6 +2068,50 @@ extern "C" IRIS_API int iris_jpeg_encode(const void* const* images, const float*
     hipLaunchKernelGGL(jpeg_assemble_kernel, dim3((unsigned)z.n_intervals), dim3(kZipThreads), 0, (hipStream_t)stream, a);
     hipLaunchKernelGGL(zip_offsets_kernel, dim3(1), dim3(kZipScanThreads), 0, (hipStream_t)stream, s);
     hipLaunchKernelGGL(jpeg_emit_kernel, dim3((unsigned)z.n_intervals), dim3(kZipThreads), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
+// ======================================================================================================
+// 8-bit image resize on the device (iris_resize.h): the scannetpp layout's --res_scale
+// ======================================================================================================
+extern "C" IRIS_API int iris_resize_tables(int mode, int ns, int nd, int32_t* ofs, int16_t* coef) {
+    if (mode != IRIS_RESIZE_LINEAR && mode != IRIS_RESIZE_NEAREST) return fail(IRIS_ERR_ARG, "iris_resize_tables: the mode is IRIS_RESIZE_LINEAR or IRIS_RESIZE_NEAREST");
+    if (ns < 1 || nd < 1 || ns > kResizeMaxSide || nd > kResizeMaxSide) return fail(IRIS_ERR_ARG, "iris_resize_tables: an axis has 1..65535 samples");
+    if (!ofs || (mode == IRIS_RESIZE_LINEAR && !coef)) return fail(IRIS_ERR_ARG, "iris_resize_tables: a NULL table");
+    resize_axis_table(mode == IRIS_RESIZE_NEAREST ? kResizeNearest : kResizeLinear, ns, nd, ofs, coef);
+    return IRIS_OK;
+}
+template <int C>
+static void resize_launch(int mode, dim3 grid, hipStream_t st, const ResizeArgs& a) {
+    if (mode == kResizeHalf) hipLaunchKernelGGL((resize_kernel<C, kResizeHalf>), grid, dim3(kResizeThreads), 0, st, a);
+    else if (mode == kResizeNearest) hipLaunchKernelGGL((resize_kernel<C, kResizeNearest>), grid, dim3(kResizeThreads), 0, st, a);
+    else hipLaunchKernelGGL((resize_kernel<C, kResizeLinear>), grid, dim3(kResizeThreads), 0, st, a);
+}
+extern "C" IRIS_API int iris_resize_u8(const void* const* images, int n_images, int Hs, int Ws, int channels, int mode, const int32_t* xofs, const int16_t* xcoef,
+                                     const int32_t* yofs, const int16_t* ycoef, uint8_t* out, int Ht, int Wt, iris_stream_t stream) {
+    if (!images || !out || n_images <= 0) return fail(IRIS_ERR_ARG, "iris_resize_u8: bad arguments");
+    if (channels != 1 && channels != 3) return fail(IRIS_ERR_ARG, "iris_resize_u8: images have 1 or 3 channels");
+    if (mode != IRIS_RESIZE_LINEAR && mode != IRIS_RESIZE_NEAREST) return fail(IRIS_ERR_ARG, "iris_resize_u8: the mode is IRIS_RESIZE_LINEAR or IRIS_RESIZE_NEAREST");
+    if (Hs < 1 || Ws < 1 || Ht < 1 || Wt < 1 || Hs > kResizeMaxSide || Ws > kResizeMaxSide || Ht > kResizeMaxSide || Wt > kResizeMaxSide)
+        return fail(IRIS_ERR_ARG, "iris_resize_u8: a side has 1..65535 pixels");
+    for (int m = 0; m < n_images; ++m)
+        if (!images[m]) return fail(IRIS_ERR_ARG, "iris_resize_u8: a NULL image");
+    int kernel_mode = mode == IRIS_RESIZE_NEAREST ? kResizeNearest : kResizeLinear;
+    if (mode == IRIS_RESIZE_LINEAR && Hs == 2 * Ht && Ws == 2 * Wt) kernel_mode = kResizeHalf;       // OpenCV's switch to the area path: BOTH axes exactly 2
+    if (kernel_mode != kResizeHalf && (!xofs || !yofs || (kernel_mode == kResizeLinear && (!xcoef || !ycoef)))) return fail(IRIS_ERR_ARG, "iris_resize_u8: a NULL table");
+    const int64_t block = (int64_t)Ht * Wt * channels;
+    for (int m0 = 0; m0 < n_images; m0 += kResizeMaxImages) {
+        ResizeArgs a{};
+        const int M = std::min(kResizeMaxImages, n_images - m0);
+        for (int m = 0; m < M; ++m) a.img[m] = static_cast<const uint8_t*>(images[m0 + m]);
+        a.xofs = xofs; a.yofs = yofs; a.xcoef = xcoef; a.ycoef = ycoef; a.Hs = Hs; a.Ws = Ws; a.Ht = Ht; a.Wt = Wt; a.block_bytes = block;
+        a.out = out + (int64_t)m0 * block;
+        const int64_t n_dwords = (block + 3) / 4 + 1;
+        const dim3 grid((unsigned)std::min<int64_t>((n_dwords + kResizeThreads - 1) / kResizeThreads, 4096), (unsigned)M);
+        if (channels == 3) resize_launch<3>(kernel_mode, grid, (hipStream_t)stream, a);
+        else resize_launch<1>(kernel_mode, grid, (hipStream_t)stream, a);
+    }
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }

@@ -54,7 +54,8 @@ def main(argv=None):
     vertices, faces = load_mesh(mesh)
     device = stage.open_device(args.device, "extract_emitter_ldr")
     scene = Scene(vertices, faces, device=device)
-    out = extract_emitters(scene, vertices, faces, stage.photograph_batches(views, img_hw, photographs, device), args.threshold, device=device)
+    batches = stage.photograph_batches(views, img_hw, photographs, device, resize=stage.layout_resizes(args.dataset, args.cameras))
+    out = extract_emitters(scene, vertices, faces, batches, args.threshold, device=device)
     os.makedirs(args.output, exist_ok=True)
     torch.save(out, os.path.join(args.output, "emitter.pth"))
     print(f"extract_emitter_ldr: {len(views)} views, {int(out['is_emitter'].sum())} of {len(faces)} triangles emit -> {os.path.join(args.output, 'emitter.pth')}", flush=True)

@@ -160,8 +160,9 @@ def open_prebake(args, name, need_exposure):
                                                         max_views=args.max_views)
     if not views:
         raise L.IrisError(f"{name}: the train split has no views")
+    resize = stage.layout_resizes(args.dataset, args.cameras)          # the scannetpp layout's 8-bit photographs are resized on the device (--res_scale)
     for path, _ in photographs:                                        # everything that can be refused is refused before the device is touched
-        stage.check_photograph_size(path, img_hw)
+        stage.check_photograph_size(path, img_hw, resize)
     return mesh, img_hw, views, photographs
 
 
@@ -184,7 +185,7 @@ def main(argv=None):
     device = stage.open_device(args.device, "slf_bake")
     scene = load_scene(mesh, device=device)
     model_crf.to(device)
-    batches = stage.photograph_batches(views, img_hw, photographs, device)
+    batches = stage.photograph_batches(views, img_hw, photographs, device, resize=stage.layout_resizes(args.dataset, args.cameras))
     out = bake_slf(scene, batches, res_spatial=args.voxel_num, dataset=args.dataset, device=device, crf=model_crf)
     os.makedirs(args.output, exist_ok=True)
     torch.save(out, os.path.join(args.output, "vslf.npz"))

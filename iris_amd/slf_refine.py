@@ -35,7 +35,8 @@ def main(argv=None):
     device = stage.open_device(args.device, "slf_refine")
     model_crf = stage.load_crf(crf_state, args.crf_basis, args.emor_path, device)
     scene = load_scene(mesh, device=device)
-    out = refine_slf(state, scene, stage.photograph_batches(views, img_hw, photographs, device), device=device, crf=model_crf)
+    batches = stage.photograph_batches(views, img_hw, photographs, device, resize=stage.layout_resizes(args.dataset, args.cameras))
+    out = refine_slf(state, scene, batches, device=device, crf=model_crf)
     torch.save(out, os.path.join(args.output, args.save))
     print(f"slf_refine: {len(views)} views, {int(out['weight']['count'].sum())} hits pooled -> {os.path.join(args.output, args.save)}", flush=True)
     return 0

@@ -11,8 +11,9 @@ parameters and the refresh of the half copy the forward reads, in one pass (iris
 iris_amd/utils/trainer.py's.
 
 Not built: the in-training validation images (train_brdf_crf.py:339-453; `python -m iris_amd.render --ckpt last.ckpt` shows the same thing), TensorBoard /
-W&B logging (the scalars go to metrics.jsonl under the reference's names), the `val/loss`-monitored best checkpoint, the `Ranger` optimizer, the
-scannetpp layout; `--val_step` and `--num_workers` are accepted and ignored.
+W&B logging (the scalars go to metrics.jsonl under the reference's names), the `val/loss`-monitored best checkpoint, the `Ranger` optimizer,
+`--res_scale` other than 1 for the real and synthetic layouts (`--dataset scannetpp ROOT --scene S` takes any: its 8-bit files are resized on the device,
+iris_amd/utils/resize.py); `--val_step` and `--num_workers` are accepted and ignored.
 """
 import argparse
 

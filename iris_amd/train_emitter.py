@@ -22,7 +22,8 @@ slf_refine, refine_shading and render as the reference's does) and `emitter.radi
 
 Not built: the in-training validation images (the reference's validation(); `python -m iris_amd.render --ckpt last.ckpt` shows the same thing), TensorBoard /
 W&B logging (the scalars go to metrics.jsonl under the reference's names), the `val/loss`-monitored best checkpoint, the
-synthetic layout's `albedo` / `roughness` ground-truth scalars, the `Ranger` optimizer, the scannetpp layout, `--res_scale` other than 1; `--val_step`,
+synthetic layout's `albedo` / `roughness` ground-truth scalars, the `Ranger` optimizer, `--res_scale` other than 1 for the real and synthetic layouts (the scannetpp layout takes any: its 8-bit files are resized on the
+device, iris_amd/utils/resize.py); `--val_step`,
 `--num_workers`, `--dir_val` and `--val_frame` are accepted and ignored.
 """
 import argparse

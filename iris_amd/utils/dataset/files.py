@@ -8,7 +8,12 @@ segmentation) and the baked shadings of ``cache_dir``.  8-bit images stay 8-bit 
 File indices: the real layout names its images by the id of the view in the capture (the train split leaves out views 0, 10, .. 150) and its cache files by
 the view's position in the split (real_ldr.py:342-363); the synthetic layout (rooted at ``<scene>/train``) uses the frame index for both.
 
-Not built, and refused with a message: an image whose size differs from the scene's, ``res_scale != 1``, the scannetpp layout.
+The scannetpp layout (``InvScannetpp``, scannetpp/dataset.py:263-384: ``psdf/images``, ``psdf/albedo``, ``psdf/seg`` by the view's file name, exposures all 1)
+is the one that takes a ``res_scale``: its 8-bit files are uploaded at the size they have and resized to the views' size on the device
+(iris_amd/utils/resize.py: linear as cv2.resize for the images, nearest as PIL for the segment ids).
+
+Not built, and refused with a message: for the real and synthetic layouts an image whose size differs from the scene's and ``res_scale != 1`` (their
+reference classes take no scale); resizing float32 (EXR) maps; a shading cache baked at another scale than the one trained at.
 """
 import os
 
@@ -45,16 +50,93 @@ def _image_size(root, first_png):
         return int(im.size[1]), int(im.size[0])
 
 
-def load_training_files(dataset, root, ldr_img_dir, *, has_part=0, res_scale=1.0, cache_dir=None, device="cuda"):
-    """-> dict(img_hw, views, synthetic, rgb [V x (H,W,3) uint8], int_albedo [V x (H,W,3) uint8], segmentation [V x (H*W) float32], exposure (V) float32,
-    cache: ShadingCache or None, mesh_path) for ``--dataset real DIR`` / ``--dataset synthetic DIR``."""
+EIGHT_BIT_MODES = ("1", "L", "P", "LA", "PA", "RGB", "RGBA", "RGBX", "CMYK", "YCbCr")      # PIL modes of one byte per channel
+
+
+def _scannetpp_paths(root, scene, name):
+    psdf = os.path.join(root, "data", scene, "psdf")
+    return [os.path.join(psdf, d, name) for d in ("images", "albedo", "seg")]
+
+
+def _check_eight_bit(path, im):
+    if im.mode not in EIGHT_BIT_MODES:
+        raise L.IrisError(f"{path}: expected an 8-bit image, got PIL mode {im.mode}")
+
+
+def check_scannetpp_files(root, scene, res_scale=1.0):
+    """what can be refused of a scannetpp training scene without a device and without decoding an image -> (img_hw, views) of the train split.  IrisError
+    naming the layout and the missing path for psdf/train_test_lists.json, psdf/transforms_all.json, an empty split and the mesh; FileNotFoundError or
+    IrisError for the FIRST view's three files (images, albedo, seg: their headers only)."""
+    from PIL import Image
+    scene = scene or ""
+    psdf = os.path.join(root, "data", scene, "psdf")
+    for name in ("train_test_lists.json", "transforms_all.json"):
+        if not os.path.isfile(os.path.join(psdf, name)):
+            raise L.IrisError(f"--dataset scannetpp: {os.path.join(psdf, name)} is missing (the scannetpp layout is <root>/data/<--scene>/psdf with "
+                              "train_test_lists.json, transforms_all.json, images/, albedo/ and seg/)")
+    img_hw, views = cameras.load_scannetpp(root, scene, res_scale, "train")
+    if not views:
+        raise L.IrisError(f"--dataset scannetpp: {psdf}: the train split has no views")
+    if min(img_hw) < 1:
+        raise L.IrisError(f"--dataset scannetpp: --res_scale {res_scale} leaves views of {img_hw[0]} x {img_hw[1]} pixels")
+    mesh_path("scannetpp", root, scene)
+    for path in _scannetpp_paths(root, scene, views[0]["name"]):
+        if not os.path.isfile(path):
+            raise FileNotFoundError(path)
+        with Image.open(path) as im:
+            _check_eight_bit(path, im)
+    return img_hw, views
+
+
+def _load_scannetpp(root, scene, res_scale, cache_dir, device):
+    """InvScannetpp(root, scene, split='train', pixel=True, cache_dir, res_scale) (utils/dataset/scannetpp/dataset.py:263-384): per view name of the train
+    split the photograph psdf/images/<name> and the albedo prior psdf/albedo/<name> through open_png -- cv2.resize, linear, when the file's size is not
+    img_hw --, the segment ids from channel B of psdf/seg/<name> (cv2.imread(...)[:, :, 0] is PIL's convert('RGB') channel 2) through sample_nearest when
+    the size differs; exposures all 1 (np.ones).  Every file is decoded on the host, uploaded at full size and resized on the device
+    (utils.resize.resize_u8): the lists hold HIP tensors, which PixelSet takes as they are."""
+    import torch
+    from PIL import Image
+    from ..resize import resize_u8
+    img_hw, views = check_scannetpp_files(root, scene, res_scale)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.IrisError(f"{device}: the scannetpp training files are resized on a HIP device (there is no CPU fallback)")
+
+    def decode(path):
+        if not os.path.isfile(path):
+            raise FileNotFoundError(path)
+        with Image.open(path) as im:
+            _check_eight_bit(path, im)
+            return torch.from_numpy(np.array(im.convert("RGB"))).to(device)
+
+    rgb, albedo, seg = [], [], []
+    for view in views:
+        image, prior, ids = (decode(p) for p in _scannetpp_paths(root, scene, view["name"]))
+        rgb.append(resize_u8(image, img_hw, "linear"))
+        albedo.append(resize_u8(prior, img_hw, "linear"))
+        seg.append(resize_u8(ids[..., 2].contiguous(), img_hw, "nearest").reshape(-1))
+    hw = img_hw[0] * img_hw[1]
+    cache = None
+    if cache_dir is not None:
+        from ..shading_cache import ShadingCache
+        cache = ShadingCache.from_exr_dir(cache_dir, len(views), device=device)        # cache files are numbered by position in the split
+        if len(cache) != hw * len(views):
+            raise L.IrisError(f"{cache_dir}: the maps hold {len(cache) // len(views)} pixels per view, the images {hw} (a cache baked at another --res_scale?)")
+    return dict(img_hw=img_hw, views=views, synthetic=False, rgb=rgb, int_albedo=albedo, segmentation=seg, exposure=np.ones(len(views), np.float32), cache=cache,
+                mesh_path=mesh_path("scannetpp", root, scene))
+
+
+def load_training_files(dataset, root, ldr_img_dir, *, has_part=0, res_scale=1.0, cache_dir=None, device="cuda", scene=None):
+    """-> dict(img_hw, views, synthetic, rgb [V x (H,W,3) uint8], int_albedo [V x (H,W,3) uint8], segmentation [V x (H*W)], exposure (V) float32,
+    cache: ShadingCache or None, mesh_path) for ``--dataset real DIR`` / ``--dataset synthetic DIR`` (host arrays, segment ids float32) and for
+    ``--dataset scannetpp ROOT --scene ID`` (_load_scannetpp: HIP tensors, segment ids uint8, any res_scale; ldr_img_dir and has_part are not needed and
+    are ignored, as in the reference)."""
     if dataset == "scannetpp":
-        raise L.IrisError("--dataset scannetpp: the scannetpp training files (psdf/images, the per-scene albedo and segmentation folders) are not built; "
-                          "only the real and synthetic layouts are")
+        return _load_scannetpp(root, scene, res_scale, cache_dir, device)
     if dataset not in ("real", "synthetic"):
-        raise L.IrisError(f"--dataset {dataset}: expected real or synthetic")
+        raise L.IrisError(f"--dataset {dataset}: expected real, synthetic or scannetpp")
     if float(res_scale) != 1.0:
-        raise L.IrisError(f"--res_scale {res_scale}: resizing the training images is not built (only res_scale 1)")
+        raise L.IrisError(f"--res_scale {res_scale}: resizing the training images is built for the scannetpp layout only (real and synthetic: res_scale 1)")
     if not ldr_img_dir:
         raise L.IrisError("--ldr_img_dir is needed: the BRDF-CRF stage trains on the LDR images, their exposures and their albedo prior")
     synthetic = dataset == "synthetic"

@@ -87,12 +87,20 @@ def read_image(path, img_hw):
     return a
 
 
-def check_photograph_size(path, img_hw):
-    """IrisError when the photograph's size (read from its header: nothing is decoded) is not the view's: resizing is not built, so --res_scale != 1 against
-    full-size files ends here; FileNotFoundError when there is no such file"""
+def layout_resizes(dataset, cameras_json=None):
+    """whether the stages resize this layout's 8-bit images to the views' size: only the scannetpp layout does (the reference's real and synthetic scripts
+    never pass a scale, and InvRealDatasetLDR and InvSyntheticDatasetLDR take none); a --cameras file replaces the layout"""
+    return dataset == "scannetpp" and not cameras_json
+
+
+def check_photograph_size(path, img_hw, resize=False):
+    """IrisError when the photograph's size (read from its header: nothing is decoded) is not the view's -- unless it is an 8-bit file of a layout that resizes
+    (resize: layout_resizes; the device resizes it, utils/resize.py).  Resizing is built for the scannetpp layout's 8-bit files only, so --res_scale != 1
+    against the full-size files of another layout, or against an .exr, ends here; FileNotFoundError when there is no such file"""
     if not os.path.isfile(path):
         raise FileNotFoundError(path)
-    if path.lower().endswith(".exr"):
+    is_exr = path.lower().endswith(".exr")
+    if is_exr:
         from .exr import read_exr_header
         h = read_exr_header(path)
         size = (int(h["height"]), int(h["width"]))
@@ -100,14 +108,16 @@ def check_photograph_size(path, img_hw):
         from PIL import Image
         with Image.open(path) as im:
             size = (int(im.size[1]), int(im.size[0]))
-    if size != tuple(img_hw):
-        raise L.IrisError(f"{path}: the photograph is {size[0]} x {size[1]}, the view {img_hw[0]} x {img_hw[1]}: resizing photographs is not built (--res_scale 1 only)")
+    if size != tuple(img_hw) and (is_exr or not resize):
+        raise L.IrisError(f"{path}: the photograph is {size[0]} x {size[1]}, the view {img_hw[0]} x {img_hw[1]}: resizing photographs is built for the 8-bit "
+                          "files of the scannetpp layout only (elsewhere --res_scale 1 only)")
 
 
-def read_photograph(path, img_hw):
+def read_photograph(path, img_hw, resize=False):
     """a view's photograph as the pre-bake stages pool it: a PNG or JPEG through PIL as (H, W, 3) uint8 -- it stays 8-bit on its way to the device, where the
-    kernel decodes it as u / 255 --, an .exr through read_image as float32.  IrisError when its size is not the view's."""
-    check_photograph_size(path, img_hw)
+    kernel decodes it as u / 255 --, an .exr through read_image as float32.  IrisError when its size is not the view's; with resize (layout_resizes) an 8-bit
+    file comes back at the size it has."""
+    check_photograph_size(path, img_hw, resize)
     if path.lower().endswith(".exr"):
         return np.ascontiguousarray(read_image(path, img_hw)[..., :3], dtype=np.float32)
     from PIL import Image
@@ -262,12 +272,15 @@ def add_common_options(parser, *names, **help_texts):
 
 # ---- what a stage's main() opens and ends with
 def refuse_unbuilt_training(args):
-    """what every trainer's main() refuses first, before the device is touched: the dataset layouts that are not built (scannetpp, --res_scale != 1, no
-    --ldr_img_dir: load_training_files' own messages), then --optimizer Ranger (make_optimizer's)"""
-    from .dataset.files import load_training_files
+    """what every trainer's main() refuses first, before the device is touched: a scannetpp root without its lists, camera file, mesh or first view's files
+    (check_scannetpp_files: two JSON files and three image headers, nothing is decoded), what is not built of the real and synthetic layouts (--res_scale
+    != 1, no --ldr_img_dir: load_training_files' own messages), then --optimizer Ranger (make_optimizer's)"""
+    from .dataset.files import check_scannetpp_files, load_training_files
     from .trainer import make_optimizer
     dataset, root = args.dataset
-    if dataset == "scannetpp" or float(args.res_scale) != 1.0 or not args.ldr_img_dir:
+    if dataset == "scannetpp":
+        check_scannetpp_files(root, args.scene, args.res_scale)
+    elif float(args.res_scale) != 1.0 or not args.ldr_img_dir:
         load_training_files(dataset, root, args.ldr_img_dir, res_scale=args.res_scale)
     if args.optimizer == "Ranger":
         make_optimizer(args.optimizer, [], args.learning_rate, args.weight_decay, networks=())
@@ -301,7 +314,8 @@ def open_training_set(args, device, ray_diff=True, cache_dir=None):
     from .dataset.files import load_training_files
     from .path_tracing import load_scene
     dataset, root = args.dataset
-    files = load_training_files(dataset, root, args.ldr_img_dir, has_part=args.has_part, res_scale=args.res_scale, cache_dir=cache_dir, device=device)
+    files = load_training_files(dataset, root, args.ldr_img_dir, has_part=args.has_part, res_scale=args.res_scale, cache_dir=cache_dir, device=device,
+                                scene=args.scene)
     scene = load_scene(files["mesh_path"], device=device)
     ps = PixelSet(files["views"], files["img_hw"], files["rgb"], segmentation=files["segmentation"], int_albedo=files["int_albedo"], exposure=files["exposure"],
                   synthetic=files["synthetic"], batch_size=args.batch_size, device=device, ray_diff=ray_diff)
@@ -325,11 +339,16 @@ def load_crf(crf_state, crf_basis, emor_path, device):
     return model_crf.to(device)
 
 
-def photograph_batches(views, img_hw, photographs, device):
+def photograph_batches(views, img_hw, photographs, device, resize=False):
     """the batch dicts iris_amd.slf_bake's functions take, one per view, made as they are asked for: {'camera', 'img_hw', 'image' on the device (8-bit
-    stays 8-bit), 'exposure'}"""
+    stays 8-bit), 'exposure'}.  resize (layout_resizes): an 8-bit photograph of another size is uploaded as it is and resized to img_hw on the device
+    (utils.resize.resize_u8, linear: the reference's open_png); the smaller image never exists on the host."""
+    from .resize import resize_u8
     for view, (path, exposure) in zip(views, photographs):
-        yield {"camera": view, "img_hw": tuple(img_hw), "image": torch.from_numpy(read_photograph(path, img_hw)).to(device), "exposure": exposure}
+        image = torch.from_numpy(read_photograph(path, img_hw, resize)).to(device)
+        if resize and image.dtype == torch.uint8:
+            image = resize_u8(image, img_hw, "linear")
+        yield {"camera": view, "img_hw": tuple(img_hw), "image": image, "exposure": exposure}
 
 
 def freeze(*modules):
