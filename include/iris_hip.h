@@ -654,6 +654,38 @@ typedef struct {
 } iris_pool_view_args;
 IRIS_API int iris_pool_view(const iris_scene *, const iris_pool_view_args *, iris_stream_t);
 
+/* ---- 5c-16: segmentation fusion (utils/fuse_segmentation.py): per-triangle label vote, the rows' winners, a view painted from a table -------- */
+/* One launch per view for the vote and for the painting: per pixel a primary ray and its closest hit (iris_intersect's traversal, bit for bit).  No
+ * intermediate tensors, no host synchronisation.  Every result is an integer count or a copy of a table entry: exact and bitwise reproducible. */
+typedef struct {
+    /* rays, as iris_pool_view_args'.  camera != NULL: HOST pointer to 24 floats K[9] | c2w[12] | focal | 2 pad; pixel i = y W + x of an H x W view, B is
+     * H W.  camera == NULL: B explicit rays, ray i at rays_o + i ray_stride and rays_d + i ray_stride floats (device; ray_stride >= 3). */
+    const float *camera;
+    int32_t H, W, synthetic;
+    const float *rays_o, *rays_d;
+    int64_t ray_stride, B;
+    /* rows of hist / entries of table (the scene's triangle count); a hit on a triangle index >= n_tri is treated as a miss */
+    int64_t n_tri;
+    /* iris_label_vote.  ids: the id of pixel i, B values (device), float32 -- truncated toward zero, torch's .long() -- or uint8.  hist: (n_tri, n_labels)
+     * uint32 (device), hist[tri n_labels + id] += 1 for a hit with 1 <= id < n_labels.  Ids that are 0, negative, NaN, infinite or >= n_labels are
+     * dropped, and so are misses; column 0 is never written.  iris_label_view ignores these four. */
+    const void *ids;
+    int32_t ids_is_u8;
+    uint32_t *hist;
+    int32_t n_labels;
+    /* iris_label_view.  table: n_tri int32 (device).  out: B values (device), out[i] = table[tri] on a hit and miss_value otherwise, written as float32
+     * or, with out_is_u8, as the value's low byte (miss_value -1 -> 255, a table entry 300 -> 44).  iris_label_vote ignores these four. */
+    const int32_t *table;
+    void *out;
+    int32_t out_is_u8, miss_value;
+} iris_label_view_args;
+IRIS_API int iris_label_vote(const iris_scene *, const iris_label_view_args *, iris_stream_t);
+/* tri_label[t] (F int32, device) = the column c in [1, n_labels) of row t of hist (F, n_labels) uint32 with the highest count -- counts compare as unsigned,
+ * equal counts go to the LOWER column (the first occurrence, as numpy's and torch-CPU's argmax) --, or 0 when every such column is 0.  Column 0 is not
+ * read.  One wave per row. */
+IRIS_API int iris_label_argmax(const uint32_t *hist, int64_t F, int32_t n_labels, int32_t *tri_label, iris_stream_t);
+IRIS_API int iris_label_view(const iris_scene *, const iris_label_view_args *, iris_stream_t);
+
 #ifdef __cplusplus
 }
 #endif

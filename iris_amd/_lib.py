@@ -31,6 +31,13 @@ class PoolViewArgs(C.Structure):
                 ("exposure_value", _F), ("bounds", _P), ("hist", _P), ("voxel_min", _D), ("voxel_max", _D), ("hist_H", C.c_int32), ("slf", _P), ("slf_acc", _P),
                 ("slf_count", _P), ("tri_sum", _P), ("tri_count", _P), ("n_tri", _I64)]
 
+
+class LabelViewArgs(C.Structure):
+    """iris_label_view_args (include/iris_hip.h); a field left alone is NULL / 0"""
+    _fields_ = [("camera", _P), ("H", C.c_int32), ("W", C.c_int32), ("synthetic", C.c_int32), ("rays_o", _P), ("rays_d", _P), ("ray_stride", _I64), ("B", _I64),
+                ("n_tri", _I64), ("ids", _P), ("ids_is_u8", C.c_int32), ("hist", _P), ("n_labels", C.c_int32), ("table", _P), ("out", _P),
+                ("out_is_u8", C.c_int32), ("miss_value", C.c_int32)]
+
 # name -> argtypes (restype is int unless listed in _RESTYPE)
 PROTOTYPES = {
     "iris_scene_create": [_P, _I64, _P, _I64, _I32, C.POINTER(_P)],
@@ -105,6 +112,9 @@ PROTOTYPES = {
     "iris_voxel_histogram": [_P, _I64, _D, _D, _I32, _P, _P],
     "iris_scatter_add_rows": [_P, _P, _I64, _I64, _P, _P, _P],
     "iris_pool_view": [_P, _P, _P],
+    "iris_label_vote": [_P, _P, _P],
+    "iris_label_argmax": [_P, _I64, _I32, _P, _P],
+    "iris_label_view": [_P, _P, _P],
     "iris_cache_row_floats": [_I32],
     "iris_cache_pack": [_P, _P, _P, _I64, _I32, _P, _P],
     "iris_cache_gather": [_P, _P, _I64, _I32, _P, _P],

@@ -36,6 +36,7 @@
 #include "iris_batch.h"
 #include "iris_optim.h"
 #include "iris_prebake.h"
+#include "iris_labels.h"
 
 using namespace iris;
 
@@ -2192,6 +2193,58 @@ extern "C" IRIS_API int iris_pool_view(const iris_scene* s, const iris_pool_view
     with_trace(s->dev, a.B, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL((pool_view_kernel<T::layout, T::joint>), dim3(grid_for(a.B, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, s->dev, a);
+    });
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
+// 5c-16: segmentation fusion -- a view's label vote per triangle, the rows' winners, a view painted from a per-triangle table (iris_labels.h)
+static int label_view_args(const char* fn, const iris_scene* s, const iris_label_view_args* v, LabelViewArgs& a) {
+    const std::string name(fn);
+    if (!s || !v) return fail(IRIS_ERR_ARG, name + ": bad arguments");
+    a.from_camera = v->camera != nullptr;
+    if (a.from_camera) {
+        if (v->H <= 0 || v->W <= 0) return fail(IRIS_ERR_ARG, name + ": a camera needs a positive image size");
+        std::memcpy(a.camera, v->camera, sizeof(a.camera));
+        a.H = v->H; a.W = v->W; a.synthetic = v->synthetic != 0;
+        a.B = (int64_t)v->H * v->W;
+    } else {
+        if (v->B < 0 || (v->B > 0 && (!v->rays_o || !v->rays_d || v->ray_stride < 3))) return fail(IRIS_ERR_ARG, name + ": bad rays");
+        a.rays_o = v->rays_o; a.rays_d = v->rays_d; a.ray_stride = v->ray_stride; a.B = v->B;
+    }
+    if (v->n_tri < 0) return fail(IRIS_ERR_ARG, name + ": negative triangle count");
+    a.n_tri = v->n_tri;
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_label_vote(const iris_scene* s, const iris_label_view_args* v, iris_stream_t stream) {
+    LabelViewArgs a{};
+    if (const int rc = label_view_args("iris_label_vote", s, v, a)) return rc;
+    if (v->n_labels < 1) return fail(IRIS_ERR_ARG, "iris_label_vote: n_labels < 1");
+    if (a.B > 0 && (!v->ids || !v->hist)) return fail(IRIS_ERR_ARG, "iris_label_vote: the vote needs the pixels' ids and the histogram");
+    if (a.B == 0 || a.n_tri == 0 || v->n_labels == 1) return IRIS_OK;      // (one column: only column 0, which is never written)
+    a.ids = v->ids; a.ids_u8 = v->ids_is_u8 != 0; a.hist = v->hist; a.n_labels = v->n_labels;
+    a.combine = g_opt_pool_combine >= 0 ? g_opt_pool_combine != 0 : 1;      // iris_debug_set("pool_combine", 0): per-lane atomics, the comparison arm of tools/bench_fuse_segmentation.py
+    with_trace(s->dev, a.B, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((label_vote_kernel<T::layout, T::joint>), dim3(grid_for(a.B, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, s->dev, a);
+    });
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_label_argmax(const uint32_t* hist, int64_t F, int32_t n_labels, int32_t* tri_label, iris_stream_t stream) {
+    if (F < 0 || n_labels < 1 || (F > 0 && (!hist || !tri_label))) return fail(IRIS_ERR_ARG, "iris_label_argmax: bad arguments");
+    if (F == 0) return IRIS_OK;
+    return launch1d(label_argmax_kernel, (F + kArgmaxRows - 1) / kArgmaxRows * 64, 1 << 16, stream, hist, F, (int)n_labels, tri_label);      // one wave per kArgmaxRows rows
+}
+extern "C" IRIS_API int iris_label_view(const iris_scene* s, const iris_label_view_args* v, iris_stream_t stream) {
+    LabelViewArgs a{};
+    if (const int rc = label_view_args("iris_label_view", s, v, a)) return rc;
+    if (a.B > 0 && (!v->out || (a.n_tri > 0 && !v->table))) return fail(IRIS_ERR_ARG, "iris_label_view: the view needs the table and the output");
+    if (a.B == 0) return IRIS_OK;
+    a.table = v->table; a.out = v->out; a.out_u8 = v->out_is_u8 != 0; a.miss_value = v->miss_value;
+    with_trace(s->dev, a.B, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((label_view_kernel<T::layout, T::joint>), dim3(grid_for(a.B, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, s->dev, a);
     });
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
