@@ -615,18 +615,23 @@ IRIS_API int iris_philox_u2(uint64_t seed, uint64_t idx0, uint32_t stream_id, in
 IRIS_API const char *iris_last_error(void);
 IRIS_API const char *iris_version(void);
 
+/* ---- the rays of a per-view call (iris_pool_view, iris_label_vote, iris_label_view): the first member of its argument structure -------- */
+/* camera != NULL: HOST pointer to 24 floats K[9] | c2w[12] | focal | 2 pad (a row of the trainers' camera table); the rays are those of
+ * iris_raygen_real / iris_raygen_synthetic (ray_diff = 0) for pixel i = y W + x of an H x W view, and B is H W.  camera == NULL: B explicit rays,
+ * ray i at rays_o + i ray_stride and rays_d + i ray_stride floats (device; ray_stride >= 3; an (N,6) tensor: rays_d = rays_o + 3, ray_stride = 6). */
+typedef struct {
+    const float *camera;
+    int32_t H, W, synthetic;
+    const float *rays_o, *rays_d;
+    int64_t ray_stride, B;
+} iris_view_rays;
+
 /* ---- 5c-11: one view's primary hits pooled where they land (slf_bake.py, slf_refine.py, extract_emitter_ldr.py) -------- */
 /* One launch per view and pass: per pixel a primary ray, its closest hit (iris_intersect's traversal and position, bit for bit) and, for a hit, any subset
  * of four sinks, selected by which pointers are non-NULL (none: the launch only traces).  A miss contributes to nothing.  No intermediate tensors, no
  * host synchronisation.  Float sums are float atomics: equal to a sequential scatter up to summation order; counts, histogram and bounds are exact. */
 typedef struct {
-    /* rays.  camera != NULL: HOST pointer to 24 floats K[9] | c2w[12] | focal | 2 pad (a row of the trainers' camera table); the rays are those of
-     * iris_raygen_real / iris_raygen_synthetic (ray_diff = 0) for pixel i = y W + x of an H x W view, and B is H W.  camera == NULL: B explicit rays,
-     * ray i at rays_o + i ray_stride and rays_d + i ray_stride floats (device; ray_stride >= 3; an (N,6) tensor: rays_d = rays_o + 3, ray_stride = 6). */
-    const float *camera;
-    int32_t H, W, synthetic;
-    const float *rays_o, *rays_d;
-    int64_t ray_stride, B;
+    iris_view_rays rays;
     /* radiance of ray i: row i of a (B,3) store, uint8 decoded as float(double(u) / 255) or float32 as stored; NULL when no pooling sink is given.
      * crf_grid != NULL: passed through the inverse response, interp(crf_grid, crf_inv_table[c], clip(v, 0, 1)) / exposure -- iris_crf_lookup_inv's
      * arithmetic and its exposure convention (exposure NULL: exposure_value; else n_exposure = 1 or B device values). */
@@ -658,12 +663,7 @@ IRIS_API int iris_pool_view(const iris_scene *, const iris_pool_view_args *, iri
 /* One launch per view for the vote and for the painting: per pixel a primary ray and its closest hit (iris_intersect's traversal, bit for bit).  No
  * intermediate tensors, no host synchronisation.  Every result is an integer count or a copy of a table entry: exact and bitwise reproducible. */
 typedef struct {
-    /* rays, as iris_pool_view_args'.  camera != NULL: HOST pointer to 24 floats K[9] | c2w[12] | focal | 2 pad; pixel i = y W + x of an H x W view, B is
-     * H W.  camera == NULL: B explicit rays, ray i at rays_o + i ray_stride and rays_d + i ray_stride floats (device; ray_stride >= 3). */
-    const float *camera;
-    int32_t H, W, synthetic;
-    const float *rays_o, *rays_d;
-    int64_t ray_stride, B;
+    iris_view_rays rays;
     /* rows of hist / entries of table (the scene's triangle count); a hit on a triangle index >= n_tri is treated as a miss */
     int64_t n_tri;
     /* iris_label_vote.  ids: the id of pixel i, B values (device), float32 -- truncated toward zero, torch's .long() -- or uint8.  hist: (n_tri, n_labels)

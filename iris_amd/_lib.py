@@ -24,18 +24,21 @@ class SceneInfo(C.Structure):
 _P, _I64, _I32, _F, _D, _U64, _U32 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_uint64, C.c_uint32
 
 
+class ViewRays(C.Structure):
+    """iris_view_rays (include/iris_hip.h), filled by utils.gbuffer.view_rays_args"""
+    _fields_ = [("camera", _P), ("H", C.c_int32), ("W", C.c_int32), ("synthetic", C.c_int32), ("rays_o", _P), ("rays_d", _P), ("ray_stride", _I64), ("B", _I64)]
+
+
 class PoolViewArgs(C.Structure):
     """iris_pool_view_args (include/iris_hip.h); a field left alone is NULL / 0"""
-    _fields_ = [("camera", _P), ("H", C.c_int32), ("W", C.c_int32), ("synthetic", C.c_int32), ("rays_o", _P), ("rays_d", _P), ("ray_stride", _I64), ("B", _I64),
-                ("rgb", _P), ("rgb_is_u8", C.c_int32), ("crf_grid", _P), ("crf_inv_table", _P), ("crf_n", C.c_int32), ("exposure", _P), ("n_exposure", _I64),
+    _fields_ = [("rays", ViewRays), ("rgb", _P), ("rgb_is_u8", C.c_int32), ("crf_grid", _P), ("crf_inv_table", _P), ("crf_n", C.c_int32), ("exposure", _P), ("n_exposure", _I64),
                 ("exposure_value", _F), ("bounds", _P), ("hist", _P), ("voxel_min", _D), ("voxel_max", _D), ("hist_H", C.c_int32), ("slf", _P), ("slf_acc", _P),
                 ("slf_count", _P), ("tri_sum", _P), ("tri_count", _P), ("n_tri", _I64)]
 
 
 class LabelViewArgs(C.Structure):
     """iris_label_view_args (include/iris_hip.h); a field left alone is NULL / 0"""
-    _fields_ = [("camera", _P), ("H", C.c_int32), ("W", C.c_int32), ("synthetic", C.c_int32), ("rays_o", _P), ("rays_d", _P), ("ray_stride", _I64), ("B", _I64),
-                ("n_tri", _I64), ("ids", _P), ("ids_is_u8", C.c_int32), ("hist", _P), ("n_labels", C.c_int32), ("table", _P), ("out", _P),
+    _fields_ = [("rays", ViewRays), ("n_tri", _I64), ("ids", _P), ("ids_is_u8", C.c_int32), ("hist", _P), ("n_labels", C.c_int32), ("table", _P), ("out", _P),
                 ("out_is_u8", C.c_int32), ("miss_value", C.c_int32)]
 
 # name -> argtypes (restype is int unless listed in _RESTYPE)

@@ -49,6 +49,26 @@ __device__ __forceinline__ PixelRay raygen_pixel(const float* __restrict__ K, co
     return r;
 }
 
+// The rays of a per-view kernel (pool_view_kernel, label_vote_kernel, label_view_kernel), carried in its arguments: from_camera -> ray i is pixel
+// (x, y) = (i % W, i / W) of an H x W view through raygen_pixel(camera), the rays of iris_raygen_real / iris_raygen_synthetic with ray_diff = 0; else
+// o = rays_o[i * ray_stride], d = rays_d[i * ray_stride] (an (N,6) rays tensor is read in place).  The host fills it in view_rays_args (iris_hip.hip).
+struct ViewRays {
+    float camera[kCamFloats];
+    int from_camera, H, W, synthetic;
+    const float* rays_o; const float* rays_d; int64_t ray_stride;
+    int64_t B;
+};
+struct Ray { f3 o, d; };
+// ray i (i < v.B); by value and assigned once, as raygen_pixel's
+__device__ __forceinline__ Ray view_ray(const ViewRays& v, int64_t i) {
+    if (v.from_camera) {
+        const int y = (int)(i / v.W), x = (int)(i - (int64_t)y * v.W);
+        const PixelRay r = raygen_pixel(v.camera, v.camera + 9, v.camera[21], v.H, v.W, 0, v.synthetic, x, y);
+        return Ray{r.o, r.d};
+    }
+    return Ray{ld3(v.rays_o + i * v.ray_stride), ld3(v.rays_d + i * v.ray_stride)};
+}
+
 struct PixelBatchArgs {
     const int64_t* ids; int64_t B;
     const float* cameras; int64_t V;

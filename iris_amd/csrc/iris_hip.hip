@@ -203,6 +203,8 @@ static int num_cus() {
     }
     return cus;
 }
+// the grid of a one-ray-per-lane traversal launch (with_trace) over n rays: kBlock-thread workgroups, at most six per compute unit
+static dim3 trace_grid(int64_t n) { return dim3(grid_for(n, kBlock, num_cus() * 6)); }
 
 // ------------------------------------------------------------------------------------------------------
 extern "C" IRIS_API int iris_scene_create(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, int device, iris_scene** out) {
@@ -698,7 +700,7 @@ extern "C" IRIS_API int iris_intersect(const iris_scene* s, const float* xs, con
     if (B == 0) return IRIS_OK;
     with_trace(s->dev, B, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((intersect_kernel<T::layout, T::joint>), dim3(grid_for(B, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, s->dev, xs, ds, B,
+        hipLaunchKernelGGL((intersect_kernel<T::layout, T::joint>), trace_grid(B), dim3(kBlock), 0, (hipStream_t)stream, s->dev, xs, ds, B,
                            pos, nrm, uv, idx, valid);
     });
     HIP_TRY(hipGetLastError());
@@ -1617,7 +1619,7 @@ static int pt_primary_launch(const iris_scene* sc, const iris_emitter* e, const 
                              float jitter_offset, int64_t B, int spp, float* wi, float* wo, float* pos, float* nrm, int32_t* e0, uint8_t* valid_next, int32_t* path_of,
                              iris_stream_t stream) {
     const int64_t N = B * spp;
-    const dim3 grid(grid_for(N, kBlock, num_cus() * 6));
+    const dim3 grid = trace_grid(N);
     with_trace(sc->dev, N, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL((pt_primary_kernel<T::layout, T::joint>), grid, dim3(kBlock), 0, (hipStream_t)stream, sc->dev, e->dev, rays_o, rays_d, dxdu, dydv, dudv, jitter_offset, B, spp, wi, wo, pos, nrm, e0, valid_next, path_of);
@@ -1683,7 +1685,7 @@ extern "C" IRIS_API int iris_pt_nee(const iris_scene* sc, const iris_emitter* e,
     else
         with_trace(a.sc, N, [&](auto t) {
             using T = decltype(t);
-            hipLaunchKernelGGL((pt_nee_kernel<T::layout, T::joint>), dim3(grid_for(N, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, a);
+            hipLaunchKernelGGL((pt_nee_kernel<T::layout, T::joint>), trace_grid(N), dim3(kBlock), 0, (hipStream_t)stream, a);
         });
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
@@ -1708,7 +1710,7 @@ extern "C" IRIS_API int iris_pt_brdf_trace(const iris_scene* sc, const float* po
     else
         with_trace(a.sc, N, [&](auto t) {
             using T = decltype(t);
-            hipLaunchKernelGGL((pt_brdf_trace_kernel<T::layout, T::joint>), dim3(grid_for(N, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, a);
+            hipLaunchKernelGGL((pt_brdf_trace_kernel<T::layout, T::joint>), trace_grid(N), dim3(kBlock), 0, (hipStream_t)stream, a);
         });
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
@@ -1854,7 +1856,7 @@ extern "C" IRIS_API int iris_pt_nee_spot(const iris_scene* sc, const float* pos,
     a.pos = pos; a.nrm = nrm; a.wo = wo; a.albedo = albedo; a.rough = roughness; a.metal = metallic; a.pick = pick; a.spots = spots; a.coef = coef; a.e = e;
     with_trace(a.sc, N, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((pt_nee_spot_kernel<T::layout, T::joint>), dim3(grid_for(N, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((pt_nee_spot_kernel<T::layout, T::joint>), trace_grid(N), dim3(kBlock), 0, (hipStream_t)stream, a);
     });
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
@@ -2159,40 +2161,50 @@ extern "C" IRIS_API int iris_scatter_add_rows(const float* values, const int64_t
     return launch1d(scatter_add_rows_kernel, B, 8192, stream, values, idx, B, F, out, count);
 }
 
+// The rays of a per-view call (iris_view_rays -> ViewRays, iris_batch.h), checked and filled for entry point fn; r.B is the ray count afterwards.
+static int view_rays_args(const char* fn, const iris_view_rays& v, ViewRays& r) {
+    const std::string name(fn);
+    r.from_camera = v.camera != nullptr;
+    if (r.from_camera) {
+        if (v.H <= 0 || v.W <= 0) return fail(IRIS_ERR_ARG, name + ": a camera needs a positive image size");
+        std::memcpy(r.camera, v.camera, sizeof(r.camera));
+        r.H = v.H; r.W = v.W; r.synthetic = v.synthetic != 0;
+        r.B = (int64_t)v.H * v.W;
+    } else {
+        if (v.B < 0 || (v.B > 0 && (!v.rays_o || !v.rays_d || v.ray_stride < 3))) return fail(IRIS_ERR_ARG, name + ": bad rays");
+        r.rays_o = v.rays_o; r.rays_d = v.rays_d; r.ray_stride = v.ray_stride; r.B = v.B;
+    }
+    return IRIS_OK;
+}
+// iris_debug_set("pool_combine", 0): per-lane atomics, the comparison arm of tools/bench_prebake.py and tools/bench_fuse_segmentation.py
+static int pool_combine() { return g_opt_pool_combine >= 0 ? g_opt_pool_combine != 0 : 1; }
+
 // 5c-11: a view's primary hits pooled where they land (iris_prebake.h)
 extern "C" IRIS_API int iris_pool_view(const iris_scene* s, const iris_pool_view_args* v, iris_stream_t stream) {
     if (!s || !v) return fail(IRIS_ERR_ARG, "iris_pool_view: bad arguments");
     PoolViewArgs a{};
-    a.from_camera = v->camera != nullptr;
-    if (a.from_camera) {
-        if (v->H <= 0 || v->W <= 0) return fail(IRIS_ERR_ARG, "iris_pool_view: a camera needs a positive image size");
-        std::memcpy(a.camera, v->camera, sizeof(a.camera));
-        a.H = v->H; a.W = v->W; a.synthetic = v->synthetic != 0;
-        a.B = (int64_t)v->H * v->W;
-    } else {
-        if (v->B < 0 || (v->B > 0 && (!v->rays_o || !v->rays_d || v->ray_stride < 3))) return fail(IRIS_ERR_ARG, "iris_pool_view: bad rays");
-        a.rays_o = v->rays_o; a.rays_d = v->rays_d; a.ray_stride = v->ray_stride; a.B = v->B;
-    }
+    if (const int rc = view_rays_args("iris_pool_view", v->rays, a.rays)) return rc;
+    const int64_t B = a.rays.B;
     const bool pools = v->slf || v->tri_sum;
-    if (pools && !v->rgb && a.B > 0) return fail(IRIS_ERR_ARG, "iris_pool_view: a pooling sink without a radiance store");
+    if (pools && !v->rgb && B > 0) return fail(IRIS_ERR_ARG, "iris_pool_view: a pooling sink without a radiance store");
     if (v->slf && (!v->slf_acc || !v->slf_count)) return fail(IRIS_ERR_ARG, "iris_pool_view: the voxel pool needs its sum and count buffers");
     if (v->tri_sum && v->n_tri < 0) return fail(IRIS_ERR_ARG, "iris_pool_view: negative triangle count");
     if (v->hist && v->hist_H <= 0) return fail(IRIS_ERR_ARG, "iris_pool_view: the histogram needs a positive resolution");
-    if (v->crf_grid && (!v->crf_inv_table || v->crf_n < 2 || v->crf_n > kCrfMaxKnots || (v->exposure && v->n_exposure != 1 && v->n_exposure != a.B)))
+    if (v->crf_grid && (!v->crf_inv_table || v->crf_n < 2 || v->crf_n > kCrfMaxKnots || (v->exposure && v->n_exposure != 1 && v->n_exposure != B)))
         return fail(IRIS_ERR_ARG, "iris_pool_view: bad response tables or exposure count");
-    if (a.B == 0) return IRIS_OK;
+    if (B == 0) return IRIS_OK;
     a.rgb = v->rgb; a.rgb_u8 = v->rgb_is_u8 != 0;
     a.crf.grid = v->crf_grid; a.crf.table = v->crf_inv_table; a.crf.n = v->crf_n;
-    a.crf.exposure = v->exposure; a.crf.n_exposure = v->n_exposure; a.crf.exposure_value = v->exposure_value; a.crf.B = a.B;
+    a.crf.exposure = v->exposure; a.crf.n_exposure = v->n_exposure; a.crf.exposure_value = v->exposure_value; a.crf.B = B;
     a.bounds = v->bounds;
     a.hist = v->hist;
     a.hist_grid.H = v->hist_H; a.hist_grid.vmin = (float)v->voxel_min; a.hist_grid.den = (float)(v->voxel_max - v->voxel_min);      // as iris_voxel_histogram
     if (v->slf) { a.has_slf = 1; a.slf = v->slf->dev; a.slf_acc = v->slf_acc; a.slf_count = (unsigned long long*)v->slf_count; }
     a.tri_sum = v->tri_sum; a.tri_count = v->tri_count; a.n_tri = v->n_tri;
-    a.combine = g_opt_pool_combine >= 0 ? g_opt_pool_combine != 0 : 1;      // iris_debug_set("pool_combine", 0): per-lane atomics, the comparison arm of tools/bench_prebake.py
-    with_trace(s->dev, a.B, [&](auto t) {
+    a.combine = pool_combine();
+    with_trace(s->dev, B, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((pool_view_kernel<T::layout, T::joint>), dim3(grid_for(a.B, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, s->dev, a);
+        hipLaunchKernelGGL((pool_view_kernel<T::layout, T::joint>), trace_grid(B), dim3(kBlock), 0, (hipStream_t)stream, s->dev, a);
     });
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
@@ -2202,16 +2214,7 @@ extern "C" IRIS_API int iris_pool_view(const iris_scene* s, const iris_pool_view
 static int label_view_args(const char* fn, const iris_scene* s, const iris_label_view_args* v, LabelViewArgs& a) {
     const std::string name(fn);
     if (!s || !v) return fail(IRIS_ERR_ARG, name + ": bad arguments");
-    a.from_camera = v->camera != nullptr;
-    if (a.from_camera) {
-        if (v->H <= 0 || v->W <= 0) return fail(IRIS_ERR_ARG, name + ": a camera needs a positive image size");
-        std::memcpy(a.camera, v->camera, sizeof(a.camera));
-        a.H = v->H; a.W = v->W; a.synthetic = v->synthetic != 0;
-        a.B = (int64_t)v->H * v->W;
-    } else {
-        if (v->B < 0 || (v->B > 0 && (!v->rays_o || !v->rays_d || v->ray_stride < 3))) return fail(IRIS_ERR_ARG, name + ": bad rays");
-        a.rays_o = v->rays_o; a.rays_d = v->rays_d; a.ray_stride = v->ray_stride; a.B = v->B;
-    }
+    if (const int rc = view_rays_args(fn, v->rays, a.rays)) return rc;
     if (v->n_tri < 0) return fail(IRIS_ERR_ARG, name + ": negative triangle count");
     a.n_tri = v->n_tri;
     return IRIS_OK;
@@ -2220,13 +2223,13 @@ extern "C" IRIS_API int iris_label_vote(const iris_scene* s, const iris_label_vi
     LabelViewArgs a{};
     if (const int rc = label_view_args("iris_label_vote", s, v, a)) return rc;
     if (v->n_labels < 1) return fail(IRIS_ERR_ARG, "iris_label_vote: n_labels < 1");
-    if (a.B > 0 && (!v->ids || !v->hist)) return fail(IRIS_ERR_ARG, "iris_label_vote: the vote needs the pixels' ids and the histogram");
-    if (a.B == 0 || a.n_tri == 0 || v->n_labels == 1) return IRIS_OK;      // (one column: only column 0, which is never written)
+    if (a.rays.B > 0 && (!v->ids || !v->hist)) return fail(IRIS_ERR_ARG, "iris_label_vote: the vote needs the pixels' ids and the histogram");
+    if (a.rays.B == 0 || a.n_tri == 0 || v->n_labels == 1) return IRIS_OK;      // (one column: only column 0, which is never written)
     a.ids = v->ids; a.ids_u8 = v->ids_is_u8 != 0; a.hist = v->hist; a.n_labels = v->n_labels;
-    a.combine = g_opt_pool_combine >= 0 ? g_opt_pool_combine != 0 : 1;      // iris_debug_set("pool_combine", 0): per-lane atomics, the comparison arm of tools/bench_fuse_segmentation.py
-    with_trace(s->dev, a.B, [&](auto t) {
+    a.combine = pool_combine();
+    with_trace(s->dev, a.rays.B, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((label_vote_kernel<T::layout, T::joint>), dim3(grid_for(a.B, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, s->dev, a);
+        hipLaunchKernelGGL((label_vote_kernel<T::layout, T::joint>), trace_grid(a.rays.B), dim3(kBlock), 0, (hipStream_t)stream, s->dev, a);
     });
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
@@ -2239,12 +2242,12 @@ extern "C" IRIS_API int iris_label_argmax(const uint32_t* hist, int64_t F, int32
 extern "C" IRIS_API int iris_label_view(const iris_scene* s, const iris_label_view_args* v, iris_stream_t stream) {
     LabelViewArgs a{};
     if (const int rc = label_view_args("iris_label_view", s, v, a)) return rc;
-    if (a.B > 0 && (!v->out || (a.n_tri > 0 && !v->table))) return fail(IRIS_ERR_ARG, "iris_label_view: the view needs the table and the output");
-    if (a.B == 0) return IRIS_OK;
+    if (a.rays.B > 0 && (!v->out || (a.n_tri > 0 && !v->table))) return fail(IRIS_ERR_ARG, "iris_label_view: the view needs the table and the output");
+    if (a.rays.B == 0) return IRIS_OK;
     a.table = v->table; a.out = v->out; a.out_u8 = v->out_is_u8 != 0; a.miss_value = v->miss_value;
-    with_trace(s->dev, a.B, [&](auto t) {
+    with_trace(s->dev, a.rays.B, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((label_view_kernel<T::layout, T::joint>), dim3(grid_for(a.B, kBlock, num_cus() * 6)), dim3(kBlock), 0, (hipStream_t)stream, s->dev, a);
+        hipLaunchKernelGGL((label_view_kernel<T::layout, T::joint>), trace_grid(a.rays.B), dim3(kBlock), 0, (hipStream_t)stream, s->dev, a);
     });
     HIP_TRY(hipGetLastError());
     return IRIS_OK;

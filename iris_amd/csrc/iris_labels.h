@@ -3,8 +3,7 @@
 //
 // The reference composes the vote from ray_intersect (five full-size outputs), a boolean-mask compaction (a host synchronisation) and scatter_add_ of int64
 // ones, and the painting from ray_intersect, a gather and a masked fill.  Here each is one launch per view, one thread per pixel:
-//     ray        raygen_pixel (iris_batch.h) from a 24-float camera row carried in the kernel arguments, or explicit origins / directions read with a row
-//                stride: exactly pool_view_kernel's (iris_prebake.h)
+//     ray        view_ray (iris_batch.h): the ViewRays in the kernel arguments, a camera row or explicit origins / directions
 //     hit        the trace_bvh4 instantiation pool_view_kernel and intersect_kernel get from with_trace: ray_intersect's closest hit, bit for bit
 //     vote       hist[tri * n_labels + id] += 1 (uint32) for a hit whose pixel carries an id in [1, n_labels); column 0 is never written (nothing reads it)
 //     argmax     per triangle row the column in [1, n_labels) with the highest count, the LOWER id among equal counts (numpy / torch-CPU argmax: first
@@ -27,11 +26,7 @@
 namespace iris {
 
 struct LabelViewArgs {
-    // rays: from_camera -> pixel (x, y) of an H x W view through raygen_pixel(camera); else o = rays_o[i * stride], d = rays_d[i * stride]
-    float camera[kCamFloats];
-    int from_camera, H, W, synthetic;
-    const float* rays_o; const float* rays_d; int64_t ray_stride;
-    int64_t B;
+    ViewRays rays;
     int64_t n_tri;                // rows of hist / entries of table: a hit on a triangle beyond them counts as a miss
     // vote
     const void* ids; int ids_u8;  // the pixels' ids: float32 (truncated toward zero, as .long()) or uint8
@@ -40,20 +35,6 @@ struct LabelViewArgs {
     // view
     const int32_t* table; void* out; int out_u8; int miss_value;
 };
-
-// the closest hit of ray i (i < a.B), as pool_view_kernel takes it
-template <int LAYOUT, bool JOINT>
-__device__ __forceinline__ Hit label_hit(const SceneDev& sc, const LabelViewArgs& a, int64_t i, uint32_t* stack) {
-    f3 o, d;
-    if (a.from_camera) {
-        const int y = (int)(i / a.W), x = (int)(i - (int64_t)y * a.W);
-        const PixelRay r = raygen_pixel(a.camera, a.camera + 9, a.camera[21], a.H, a.W, 0, a.synthetic, x, y);
-        o = r.o; d = r.d;
-    } else {
-        o = ld3(a.rays_o + i * a.ray_stride); d = ld3(a.rays_d + i * a.ray_stride);
-    }
-    return trace_bvh4<LAYOUT, false, kStackLds, false, JOINT>(sc, o, d, stack);
-}
 
 // the id pixel i votes for, or -1: 0, negative, NaN, infinite and >= n_labels are dropped.  (The float is compared before it is converted: 1 <= f < 2^31
 // holds exactly when its truncation is an int >= 1, and NaN fails every comparison.)
@@ -73,12 +54,13 @@ template <int LAYOUT, bool JOINT>
 __global__ __launch_bounds__(kBlock) void label_vote_kernel(SceneDev sc, LabelViewArgs a) {
     __shared__ uint32_t s_stack[kStackLds * kBlock];
     // (the loop's bound is the workgroup's, not the lane's: every lane stays for the wave-wide step below, a lane past the end with key -1)
-    for (int64_t base = blockIdx.x * (int64_t)kBlock; base < a.B; base += (int64_t)gridDim.x * kBlock) {
+    for (int64_t base = blockIdx.x * (int64_t)kBlock; base < a.rays.B; base += (int64_t)gridDim.x * kBlock) {
         const int64_t i = base + threadIdx.x;
         long long key = -1;
-        if (i < a.B) {
+        if (i < a.rays.B) {
             const int id = label_id(a, i);
-            const Hit h = label_hit<LAYOUT, JOINT>(sc, a, i, s_stack + threadIdx.x);
+            const Ray r = view_ray(a.rays, i);
+            const Hit h = trace_bvh4<LAYOUT, false, kStackLds, false, JOINT>(sc, r.o, r.d, s_stack + threadIdx.x);
             if (h.slot >= 0 && id >= 0 && h.id >= 0 && h.id < a.n_tri) key = (long long)h.id * a.n_labels + id;
         }
         if (!a.combine) {
@@ -127,8 +109,9 @@ __global__ __launch_bounds__(256) void label_argmax_kernel(const uint32_t* __res
 template <int LAYOUT, bool JOINT>
 __global__ __launch_bounds__(kBlock) void label_view_kernel(SceneDev sc, LabelViewArgs a) {
     __shared__ uint32_t s_stack[kStackLds * kBlock];
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < a.B; i += (int64_t)gridDim.x * kBlock) {
-        const Hit h = label_hit<LAYOUT, JOINT>(sc, a, i, s_stack + threadIdx.x);
+    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < a.rays.B; i += (int64_t)gridDim.x * kBlock) {
+        const Ray r = view_ray(a.rays, i);
+        const Hit h = trace_bvh4<LAYOUT, false, kStackLds, false, JOINT>(sc, r.o, r.d, s_stack + threadIdx.x);
         const int v = h.slot >= 0 && h.id >= 0 && h.id < a.n_tri ? a.table[h.id] : a.miss_value;
         if (a.out_u8) ((uint8_t*)a.out)[i] = (uint8_t)(v & 0xFF);      // numpy's astype(uint8) of an int: the low byte (-1 -> 255, 300 -> 44)
         else ((float*)a.out)[i] = (float)v;

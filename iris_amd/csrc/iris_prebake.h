@@ -3,8 +3,7 @@
 // The reference, and this project's first version of these stages, compose a pass over a view from a ray generator, ray_intersect (five full-size
 // outputs), two boolean-mask compactions (each a host synchronisation), the response model's inverse over a float copy of the photograph, and a scatter.
 // pool_view_kernel is that pass as one launch, one thread per pixel:
-//     ray        raygen_pixel (iris_batch.h) from a 24-float camera row carried in the kernel arguments, or explicit origins / directions read with a
-//                row stride (an (N,6) rays tensor is read in place)
+//     ray        view_ray (iris_batch.h): the ViewRays in the kernel arguments, a camera row or explicit origins / directions
 //     hit        the trace_bvh4 instantiation intersect_kernel gets from with_trace, hit_vertices, hit_position; a miss contributes to nothing
 //     radiance   3 bytes of an 8-bit photograph through a 3 x 256 table in LDS (the decode float(double(u) / 255), and behind it the inverse response of
 //                that value when a response model is given: 768 lookups per workgroup instead of three per pixel, the same bits), or three floats
@@ -98,11 +97,7 @@ __device__ __forceinline__ void pool_rows_combined(long long key, f3 rgb, float*
 }
 
 struct PoolViewArgs {
-    // rays: from_camera -> pixel (x, y) of an H x W view through raygen_pixel(camera); else o = rays_o[i * stride], d = rays_d[i * stride]
-    float camera[kCamFloats];
-    int from_camera, H, W, synthetic;
-    const float* rays_o; const float* rays_d; int64_t ray_stride;
-    int64_t B;
+    ViewRays rays;
     // radiance (NULL: none; the pooling sinks need it)
     const void* rgb; int rgb_u8;
     CrfArgs crf;                  // grid NULL: no response model; table = the (3, n) INVERSE table; exposure as crf_exposure reads it
@@ -132,20 +127,13 @@ __global__ __launch_bounds__(kBlock) void pool_view_kernel(SceneDev sc, PoolView
     }
     float lo = INFINITY, hi = -INFINITY;
     // (the loop's bound is the workgroup's, not the lane's: every lane stays for the wave-wide steps below, a lane past the end as a miss)
-    for (int64_t base = blockIdx.x * (int64_t)kBlock; base < a.B; base += (int64_t)gridDim.x * kBlock) {
+    for (int64_t base = blockIdx.x * (int64_t)kBlock; base < a.rays.B; base += (int64_t)gridDim.x * kBlock) {
         const int64_t i = base + threadIdx.x;
         Hit h; h.slot = -1; h.id = -1;
         f3 p = mk3(0.f, 0.f, 0.f), rgb = mk3(0.f, 0.f, 0.f);
-        if (i < a.B) {
-            f3 o, d;
-            if (a.from_camera) {
-                const int y = (int)(i / a.W), x = (int)(i - (int64_t)y * a.W);
-                const PixelRay r = raygen_pixel(a.camera, a.camera + 9, a.camera[21], a.H, a.W, 0, a.synthetic, x, y);
-                o = r.o; d = r.d;
-            } else {
-                o = ld3(a.rays_o + i * a.ray_stride); d = ld3(a.rays_d + i * a.ray_stride);
-            }
-            h = trace_bvh4<LAYOUT, false, kStackLds, false, JOINT>(sc, o, d, s_stack + threadIdx.x);
+        if (i < a.rays.B) {
+            const Ray r = view_ray(a.rays, i);
+            h = trace_bvh4<LAYOUT, false, kStackLds, false, JOINT>(sc, r.o, r.d, s_stack + threadIdx.x);
         }
         const bool hit = h.slot >= 0;
         if (hit) {

@@ -11,6 +11,29 @@ import torch
 from .. import _lib as L
 
 
+def view_rays_args(fn, a, keep, scene, camera, img_hw, rays):
+    """Fills a (an L.ViewRays: the `rays` member of the argument structure of fn -- pool_view, vote_view, label_view) from camera= and img_hw=, or from
+    rays=; what a points at is appended to keep, to stay alive until the call returns -> (number of rays, the device the call runs under)"""
+    if (camera is None) == (rays is None):
+        raise L.IrisError(f"{fn}: pass either camera= (with img_hw=) or rays=")
+    if camera is not None:
+        from .dataset.pixel_set import camera_table
+        if img_hw is None:
+            raise L.IrisError(f"{fn}: camera= needs img_hw=(H, W)")
+        synthetic = camera["kind"] == "synthetic"
+        row = np.ascontiguousarray(camera_table([camera], synthetic)[0])
+        keep.append(row)
+        a.camera, a.H, a.W, a.synthetic = row.ctypes.data_as(C.c_void_p), int(img_hw[0]), int(img_hw[1]), int(synthetic)
+        return a.H * a.W, scene.device
+    rays = L.require_gpu(rays, torch.float32, "rays")
+    if rays.dim() < 2 or rays.shape[-1] < 6:
+        raise L.IrisError(f"rays: expected (N, 6) [origin, direction], got {tuple(rays.shape)}")
+    rays = rays.reshape(-1, rays.shape[-1])              # (rows wider than 6 -- a dataset's ray differentials -- are stepped over)
+    keep.append(rays)
+    a.rays_o, a.rays_d, a.ray_stride, a.B = rays.data_ptr(), rays.data_ptr() + 12, rays.shape[1], rays.shape[0]
+    return rays.shape[0], rays.device
+
+
 def pool_view(scene, *, camera=None, img_hw=None, rays=None, image=None, crf_tables=None, exposure=1.0, bounds=None, hist=None, voxel_range=None, vslf=None,
               tri_sum=None, tri_count=None):
     """One view's primary hits pooled where they land, in ONE launch (iris_amd/csrc/iris_prebake.h): per pixel the ray, its closest hit (ray_intersect's,
@@ -32,25 +55,7 @@ def pool_view(scene, *, camera=None, img_hw=None, rays=None, image=None, crf_tab
             raise L.IrisError(f"{name}: a sink must be contiguous")
     a = L.PoolViewArgs()
     keep = []                                             # what the struct points at, alive until the call returns
-    if (camera is None) == (rays is None):
-        raise L.IrisError("pool_view: pass either camera= (with img_hw=) or rays=")
-    if camera is not None:
-        from .dataset.pixel_set import camera_table
-        synthetic = camera["kind"] == "synthetic"
-        row = np.ascontiguousarray(camera_table([camera], synthetic)[0])
-        keep.append(row)
-        a.camera, a.H, a.W, a.synthetic = row.ctypes.data_as(C.c_void_p), int(img_hw[0]), int(img_hw[1]), int(synthetic)
-        n = a.H * a.W
-        device = scene.device
-    else:
-        rays = L.require_gpu(rays, torch.float32, "rays")
-        if rays.dim() < 2 or rays.shape[-1] < 6:
-            raise L.IrisError(f"rays: expected (N, 6) [origin, direction], got {tuple(rays.shape)}")
-        rays = rays.reshape(-1, rays.shape[-1])          # (rows wider than 6 -- a dataset's ray differentials -- are stepped over)
-        keep.append(rays)
-        n = rays.shape[0]
-        a.rays_o, a.rays_d, a.ray_stride, a.B = rays.data_ptr(), rays.data_ptr() + 12, rays.shape[1], n
-        device = rays.device
+    n, device = view_rays_args("pool_view", a.rays, keep, scene, camera, img_hw, rays)
     if vslf is not None or tri_sum is not None:
         if image is None:
             raise L.IrisError("pool_view: the voxel and triangle pools need image=")

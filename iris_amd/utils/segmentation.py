@@ -11,34 +11,12 @@ Everything is an integer count or a copy: exact, and the same bits from run to r
 the other three return tensors they allocate."""
 import ctypes as C
 
-import numpy as np
 import torch
 
 from .. import _lib as L
+from .gbuffer import view_rays_args
 
 _HIST_DTYPES = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
-
-
-def _ray_args(fn, a, keep, scene, camera, img_hw, rays):
-    """the ray fields of a LabelViewArgs, as pool_view fills them -> (number of rays, device)"""
-    if (camera is None) == (rays is None):
-        raise L.IrisError(f"{fn}: pass either camera= (with img_hw=) or rays=")
-    if camera is not None:
-        from .dataset.pixel_set import camera_table
-        if img_hw is None:
-            raise L.IrisError(f"{fn}: camera= needs img_hw=(H, W)")
-        synthetic = camera["kind"] == "synthetic"
-        row = np.ascontiguousarray(camera_table([camera], synthetic)[0])
-        keep.append(row)
-        a.camera, a.H, a.W, a.synthetic = row.ctypes.data_as(C.c_void_p), int(img_hw[0]), int(img_hw[1]), int(synthetic)
-        return a.H * a.W, scene.device
-    rays = L.require_gpu(rays, torch.float32, "rays")
-    if rays.dim() < 2 or rays.shape[-1] < 6:
-        raise L.IrisError(f"rays: expected (N, 6) [origin, direction], got {tuple(rays.shape)}")
-    rays = rays.reshape(-1, rays.shape[-1])              # (rows wider than 6 -- a dataset's ray differentials -- are stepped over)
-    keep.append(rays)
-    a.rays_o, a.rays_d, a.ray_stride, a.B = rays.data_ptr(), rays.data_ptr() + 12, rays.shape[1], rays.shape[0]
-    return rays.shape[0], rays.device
 
 
 def _check_hist(hist, name="hist"):
@@ -65,7 +43,7 @@ def vote_view(scene, hist, labels, *, camera=None, img_hw=None, rays=None):
     if hist.shape[0] != scene.n_triangles:
         raise L.IrisError(f"hist: {hist.shape[0]} rows for a scene of {scene.n_triangles} triangles")
     a, keep = L.LabelViewArgs(), []
-    n, device = _ray_args("vote_view", a, keep, scene, camera, img_hw, rays)
+    n, device = view_rays_args("vote_view", a.rays, keep, scene, camera, img_hw, rays)
     if not isinstance(labels, torch.Tensor) or labels.dtype not in (torch.float32, torch.uint8):
         raise L.IrisError("labels: expected a float32 or uint8 tensor")
     labels = L.require_gpu(labels, labels.dtype, "labels")
@@ -99,7 +77,7 @@ def label_view(scene, table, *, camera=None, img_hw=None, rays=None, miss=0, dty
     if not -(1 << 31) <= int(miss) < (1 << 31):
         raise L.IrisError(f"label_view: miss={miss} is not a 32-bit integer")
     a, keep = L.LabelViewArgs(), [table]
-    n, device = _ray_args("label_view", a, keep, scene, camera, img_hw, rays)
+    n, device = view_rays_args("label_view", a.rays, keep, scene, camera, img_hw, rays)
     if table.device != device:
         raise L.IrisError(f"label_view: table on {table.device}, the rays on {device}")
     out = torch.empty(n, dtype=dtype, device=device)

@@ -37,6 +37,39 @@ def test_library_exports_every_declared_symbol():
     assert lib.iris_version().startswith(b"iris_hip")
 
 
+def _c_fields(cls, prefix=""):
+    """(C member path, ctypes offset) of every field of a ctypes structure, nested structures flattened as rays.camera"""
+    import ctypes as C
+    for name, typ in cls._fields_:
+        off = getattr(cls, name).offset
+        yield prefix + name, off
+        if issubclass(typ, C.Structure):
+            for sub, sub_off in _c_fields(typ, prefix + name + "."):
+                yield sub, off + sub_off
+
+
+def test_ctypes_structures_mirror_the_header(tmp_path):
+    """Every ctypes structure of _lib.py has the size and the field offsets of the C structure it stands for, as g++ lays out include/iris_hip.h; and the
+    shared ray structure leaves the binary interface of iris_pool_view / iris_label_vote / iris_label_view where it was (no library needed)."""
+    import ctypes as C
+    from iris_amd import _lib as L
+    pairs = (("iris_view_rays", L.ViewRays), ("iris_pool_view_args", L.PoolViewArgs), ("iris_label_view_args", L.LabelViewArgs), ("iris_scene_info", L.SceneInfo))
+    lines, expected = [], []
+    for c_name, cls in pairs:
+        lines.append(f'    std::printf("%zu\\n", sizeof({c_name}));')
+        expected.append((f"sizeof({c_name})", C.sizeof(cls)))
+        for member, off in _c_fields(cls):
+            lines.append(f'    std::printf("%zu\\n", offsetof({c_name}, {member}));')
+            expected.append((f"offsetof({c_name}, {member})", off))
+    src, exe = tmp_path / "layout.cpp", str(tmp_path / "layout")
+    src.write_text('#include <cstddef>\n#include <cstdio>\n#include "iris_hip.h"\nint main() {\n' + "\n".join(lines) + "\n    return 0;\n}\n")
+    subprocess.run(["g++", "-std=c++17", "-I", os.path.join(REPO, "include"), str(src), "-o", exe], check=True, timeout=120)
+    got = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True, timeout=60).stdout.split()]
+    assert len(expected) > 60 and len(got) == len(expected)
+    assert [(what, v) for (what, _), v in zip(expected, got)] == expected
+    assert C.sizeof(L.ViewRays) == 56 and L.PoolViewArgs.rgb.offset == 56 and L.LabelViewArgs.n_tri.offset == 56
+
+
 def test_public_boundary_has_no_experiment_knobs():
     """include/iris_hip.h is the drop-in boundary: no kernel-variant / instrumentation arguments, and the library reads no
     environment variables (tuning goes through iris_debug_set of the diagnostics header)."""

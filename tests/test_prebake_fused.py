@@ -256,6 +256,13 @@ def test_empty_ray_batch_is_a_no_op(box):
     assert not got["hist"].any() and not got["v_count"].any() and not got["tri_sum"].any() and not got["tri_count"].any()
 
 
+def test_a_camera_without_an_image_size_is_refused(box):
+    from iris_amd._lib import IrisError
+    from iris_amd.utils.gbuffer import pool_view
+    with pytest.raises(IrisError):
+        pool_view(box, camera=synth_view("real", 37, 53, 1))
+
+
 def test_hits_in_an_empty_voxel_are_dropped(box):
     hw = (48, 64)
     view = synth_view("real", *hw, 0)

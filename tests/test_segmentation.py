@@ -238,6 +238,42 @@ def test_label_view(box, open_box, dtype, miss, form):
             assert 100 < (~valid).sum() < N - 100
 
 
+# ---- view shapes and the empty batch, for both label kernels
+@pytest.mark.parametrize("combine", [True, False], ids=["combined", "per_lane"])
+@pytest.mark.parametrize("hw", [(1, 1), (64, 1)])
+def test_view_shapes(box, hw, combine):
+    """a single lane; and exactly one wave, with nothing behind it in the vote's workgroup-bounded loop"""
+    from iris_amd.utils.segmentation import label_view, vote_view
+    n, n_labels = hw[0] * hw[1], 7
+    view = synth_view("real", *hw, 1)
+    _, idx, valid = hits_of(box, rays_of(view, hw))
+    assert valid.any()
+    m = torch.from_numpy((1 + np.arange(n) % (n_labels - 1)).astype(np.float32)).to(dev())
+    table = 301 + np.arange(F)
+
+    def run():
+        hist = torch.zeros(F, n_labels, dtype=torch.int32, device=dev())
+        assert vote_view(box, hist, m, camera=view, img_hw=hw) is None
+        return hist.cpu().numpy().astype(np.int64), label_view(box, torch.from_numpy(table.astype(np.int32)).to(dev()), camera=view, img_hw=hw, miss=-1)
+    hist, painted = run() if combine else per_lane(run)
+    assert np.array_equal(hist, ref.vote(idx, valid, m.cpu().numpy(), F, n_labels)) and hist.sum() == valid.sum()
+    assert painted.dtype == torch.float32 and tuple(painted.shape) == (n,)
+    assert np.array_equal(painted.cpu().numpy().astype(np.int64), ref.label_view(idx, valid, table, -1))
+
+
+def test_empty_ray_batch_is_a_no_op(box):
+    from iris_amd.utils.segmentation import label_view, vote_view
+    rays = torch.empty(0, 6, device=dev())
+    before = torch.arange(1, 1 + F * 7, dtype=torch.int32).reshape(F, 7)
+    hist = before.to(dev())
+    assert vote_view(box, hist, torch.empty(0, device=dev()), rays=rays) is None
+    assert torch.equal(hist.cpu(), before)
+    table = torch.zeros(F, dtype=torch.int32, device=dev())
+    for dtype in (torch.float32, torch.uint8):
+        out = label_view(box, table, rays=rays, dtype=dtype)
+        assert tuple(out.shape) == (0,) and out.dtype == dtype
+
+
 # ---- fuse
 TRUTH = 1 + np.arange(F) % 5
 

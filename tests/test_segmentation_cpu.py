@@ -102,6 +102,46 @@ def test_the_restatement_drops_what_is_no_id():
     assert ref.triangle_labels(big).tolist() == [2]
 
 
+# ---- the ray arguments of pool_view, vote_view and label_view
+class _SceneStandIn:
+    device = "the scene's device"
+
+
+def _views():
+    c2w = np.array([[1, 0, 0, 2.0], [0, 0, 1, 1.5], [0, -1, 0, 1.2]], np.float32)
+    K = np.array([[0.8 * W, 0, W / 2.0], [0, 0.7 * W, H / 2.0], [0, 0, 1]], np.float32)
+    return [{"kind": "real", "K": K, "c2w": c2w}, {"kind": "synthetic", "focal": 41.5, "c2w": c2w}]
+
+
+@pytest.mark.parametrize("view", _views(), ids=["real", "synthetic"])
+def test_the_ray_arguments_of_a_camera(view):
+    import ctypes as C
+    from iris_amd import _lib as L
+    from iris_amd.utils.dataset.pixel_set import camera_table
+    from iris_amd.utils.gbuffer import view_rays_args
+    synthetic = view["kind"] == "synthetic"
+    a, keep, scene = L.PoolViewArgs(), [], _SceneStandIn()
+    assert view_rays_args("pool_view", a.rays, keep, scene, view, (H, W), None) == (H * W, scene.device)
+    assert (a.rays.H, a.rays.W, a.rays.synthetic) == (H, W, int(synthetic))
+    assert not a.rays.rays_o and not a.rays.rays_d and a.rays.ray_stride == 0 and not a.rgb          # (the rest of the structure is left alone)
+    row = camera_table([view], synthetic)[0]
+    assert row.shape == (24,) and row.dtype == np.float32 and row.any()
+    assert np.array_equal(np.ctypeslib.as_array(C.cast(a.rays.camera, C.POINTER(C.c_float)), (24,)), row)
+    assert any(isinstance(k, np.ndarray) and k.ctypes.data == a.rays.camera for k in keep)
+
+
+def test_the_ray_arguments_that_are_refused():
+    import torch
+    from iris_amd import _lib as L
+    from iris_amd.utils.gbuffer import view_rays_args
+    view = _views()[0]
+    for camera, img_hw, rays in ((view, (H, W), torch.zeros(4, 6)), (None, (H, W), None), (view, None, None), (None, None, torch.zeros(4, 6))):
+        keep = []
+        with pytest.raises(L.IrisError):
+            view_rays_args("label_view", L.LabelViewArgs().rays, keep, _SceneStandIn(), camera, img_hw, rays)
+        assert not keep
+
+
 # ---- the stage's host half
 def test_split_all_of_a_real_layout_is_every_capture_in_order(tmp_path):
     from iris_amd import fuse_segmentation as fs
