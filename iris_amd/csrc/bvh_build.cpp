@@ -175,6 +175,12 @@ float sah_of(const Node2* nodes, int32_t i, float root_area) {
 
 }  // namespace
 
+bool buildable_extent(const float* verts, const int32_t* faces, int64_t nf) {
+    Box g; g.reset();
+    for (int64_t i = 0; i < nf * 3; ++i) { const float* p = verts + (int64_t)faces[i] * 3; g.grow(p, p); }
+    return std::isfinite(g.area());
+}
+
 WideBvh build_wide_bvh(const float* verts, int64_t /*nv*/, const int32_t* faces, int64_t nf, int width, int leaf_tris,
                        float pad_rel, float tri_cost, float presplit) {
     leaf_tris = std::min(7, std::max(1, leaf_tris));
@@ -191,6 +197,8 @@ WideBvh build_wide_bvh(const float* verts, int64_t /*nv*/, const int32_t* faces,
         return w;
     };
     if (nf <= 0) { out.nodes.push_back(empty_node()); out.depth = 1; return out; }
+    // (areas relative to an infinite root area are NaN: the collapse below would find no split of any node and never stop handing out slots)
+    if (!buildable_extent(verts, faces, nf)) return out;
 
     std::vector<TriInfo> tri((size_t)nf);
     std::vector<int32_t> order((size_t)nf);

@@ -37,8 +37,12 @@ struct WideBvh {
 // Boxes are padded by `pad_rel * max(|coordinate|, extent)` so that the f32 slab test is conservative with respect to the
 // Moeller-Trumbore test (see DESIGN.md "closest-hit semantics").  presplit: early split clipping of triangles whose box is longer than
 // presplit x the median triangle's (0 = off), see bvh_build.cpp.
+// A mesh whose bounding-box AREA is not finite in float32 (coordinates beyond ~1e19 apart) cannot be built: every SAH cost is inf or NaN.  build_wide_bvh
+// returns a tree without nodes (depth 0) for it; callers refuse such a mesh up front with buildable_extent().
 WideBvh build_wide_bvh(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, int width, int leaf_tris,
                        float pad_rel = 2e-5f, float tri_cost = 0.7f, float presplit = 8.f);
+// true when the area of the mesh's bounding box, as the builder computes it, is finite (an empty mesh is)
+bool buildable_extent(const float* verts, const int32_t* faces, int64_t nf);
 
 // ------------------------------------------------------------------------------------------------------
 // The tree as the kernels read it (iris_trace.h): what this encoder and the traversal share.

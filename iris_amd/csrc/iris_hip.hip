@@ -219,6 +219,8 @@ extern "C" IRIS_API int iris_debug_scene_create(const float* verts, int64_t nv, 
         if (faces[i] < 0 || faces[i] >= nv) return fail(IRIS_ERR_ARG, "iris_scene_create: face index out of range");
     if (layout == IRIS_BVH_DEFAULT) layout = IRIS_BVH4_Q8;
     if (layout != IRIS_BVH4_F32 && layout != IRIS_BVH4_Q8) return fail(IRIS_ERR_ARG, "iris_scene_create: unknown BVH layout");
+    if (!buildable_extent(verts, faces, nf))
+        return fail(IRIS_ERR_ARG, "iris_scene_create: the area of the mesh's bounding box is not finite in float32 (coordinates too far apart for the SAH build)");
     HIP_TRY(hipSetDevice(device));
     auto t0 = std::chrono::steady_clock::now();
     int max_leaf = 4;

@@ -802,6 +802,15 @@ static int32_t build_rec(build_ctx *cx, int32_t start, int32_t count) {
     return me;
 }
 
+/* intersect_bvh keeps one stack entry per level it has descended: the tree may not be deeper than its array */
+#define ORC_STACK 128
+static int tree_depth(const orc_scene *sc, int32_t i) {
+    const orc_node *n = &sc->nodes[i];
+    if (n->left < 0) return 1;
+    int l = tree_depth(sc, n->left), r = tree_depth(sc, n->start);
+    return 1 + (l > r ? l : r);
+}
+/* NULL: the tree is deeper than ORC_STACK levels (a one-sided tree over a geometric progression of triangles; use the brute-force path of a smaller scene) */
 ORC_API orc_scene *orc_scene_create(const float *verts, int64_t nv, const int32_t *faces, int64_t nf) {
     orc_scene *sc = (orc_scene *)calloc(1, sizeof(orc_scene));
     sc->nv = nv; sc->nf = nf; sc->verts = verts; sc->faces = faces;
@@ -825,8 +834,10 @@ ORC_API orc_scene *orc_scene_create(const float *verts, int64_t nv, const int32_
     build_ctx cx = {sc, tb, 1e-4f * ext + 1e-30f};
     build_rec(&cx, 0, (int32_t)nf);
     free(tb);
+    if (tree_depth(sc, 0) > ORC_STACK) { free(sc->nodes); free(sc->order); free(sc); return NULL; }
     return sc;
 }
+ORC_API int orc_scene_depth(const orc_scene *sc) { return sc && sc->nf ? tree_depth(sc, 0) : 0; }   /* levels of the binary tree (<= ORC_STACK) */
 ORC_API void orc_scene_destroy(orc_scene *sc) { if (sc) { free(sc->nodes); free(sc->order); free(sc); } }
 
 static inline int slab(const orc_node *n, v3 o, v3 id, float tbest, float *tnear) {
@@ -850,7 +861,7 @@ static orc_hit intersect_bvh(const orc_scene *sc, v3 o, v3 d, int64_t *n_nodes, 
     if (sc->nf == 0) return h;
     v3 id = v3_make(safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
     const ray_xf xf = ray_xform(o, d);
-    int32_t stack[128]; int sp = 0;
+    int32_t stack[ORC_STACK]; int sp = 0;      /* (sp < depth of the tree <= ORC_STACK: orc_scene_create) */
     int32_t cur = 0; float tn;
     if (n_nodes) ++*n_nodes;
     if (!slab(&sc->nodes[0], o, id, h.t, &tn)) return h;

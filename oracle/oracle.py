@@ -257,6 +257,12 @@ class Scene:
         self.vertices = _f32(vertices).reshape(-1, 3)
         self.faces = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
         self.h = C.c_void_p(lib().orc_scene_create(_p(self.vertices), C.c_int64(self.vertices.shape[0]), _p(self.faces), C.c_int64(self.faces.shape[0])))
+        if not self.h:
+            raise ValueError("oracle.Scene: the BVH over this mesh is deeper than the traversal stack of intersect_bvh (128 levels)")
+
+    def depth(self):
+        """levels of the oracle's own binary BVH (intersect_bvh keeps one stack entry per level, 128 at the most)"""
+        return int(lib().orc_scene_depth(self.h))
 
     def ray_intersect(self, xs, ds, brute=False, counters=False):
         xs = _f32(xs); ds = _f32(ds); B = xs.shape[0]

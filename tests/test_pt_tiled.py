@@ -20,7 +20,8 @@ def force_tiles():
     L.debug_set("pt_tile_min", -1)
 
 
-def _stage_outputs(scene, em, dev, N, seed):
+def _stage_outputs(scene, em, dev, N, seed, points=None):
+    """points: (pos, nrm, wo) N x 3 device tensors for a scene other than the box room (tests/test_deep_stack.py); the draws stay the same"""
     from iris_amd import _lib as L
     from iris_amd.utils.path_tracing import _lobe_trace
     g = torch.Generator(device="cpu").manual_seed(seed)
@@ -28,6 +29,8 @@ def _stage_outputs(scene, em, dev, N, seed):
     pos = (R(N, 3) * torch.tensor([3.6, 2.6, 2.2], device=dev) + 0.2).contiguous()
     nrm = torch.nn.functional.normalize(R(N, 3) - 0.5, dim=-1).contiguous()
     wo = torch.nn.functional.normalize(nrm + 0.8 * (R(N, 3) - 0.5), dim=-1).contiguous()
+    if points is not None:
+        pos, nrm, wo = (t.contiguous() for t in points)
     albedo, rough, metal = R(N, 3).contiguous(), (R(N) * 0.9 + 0.05).contiguous(), R(N).contiguous()
     s1, s2 = R(N), R(N, 2)
     out = []
