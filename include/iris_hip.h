@@ -541,6 +541,42 @@ IRIS_API int iris_uv_resolve(const float *vt, int64_t n_vt, const int32_t *ft, c
 IRIS_API int iris_texture_quantize(const float *albedo, const float *roughness, const float *metallic, const int32_t *ids, int64_t texel0, int64_t n,
                           int64_t n_texels, uint8_t *albedo_img, uint8_t *rm_img, iris_stream_t);
 
+/* ---- texture export: the area-proportional atlas and the seam dilation (no counterpart in the reference, which calls xatlas) ---- */
+/* One chart per face, sized by the face's area: exact in integers and float64 (iris_amd/csrc/iris_atlas.h; restated in numpy by
+ * tests/atlas_ref.py).  tex_res = R: a square power of two in [4, 8192]; F at most 2^23 (two faces per 4 x 4 cell of the largest texture).
+ * iris_atlas_measure: v (n_v, 3) float32, f (F, 3) int32 -> S (F) float64 and corner (F) uint8.  In float64, every product and sum rounded on its own, sums
+ *   left to right: e1 = p1 - p0, e2 = p2 - p0, c = e1 x e2, S = cx^2 + cy^2 + cz^2 (four times the squared area; no square root anywhere); l0 = |p2 - p1|^2,
+ *   l1 = |p0 - p2|^2, l2 = |p1 - p0|^2; corner = argmax(l0, l1, l2), first maximum: the vertex opposite the longest edge.  A face that names a vertex outside
+ *   [0, n_v), or whose S is not finite or not > 0, gets S = 0 and corner = 0.
+ * iris_atlas_density: D_j = M[j mod 2] 2^floor(j / 2), M = (1, 1.4142135623730951), the squared number of texels per unit area at step j of the ladder
+ *   [-800, 800]; 0 outside it.  A host function.
+ * iris_atlas_classes: S, j -> k (F) uint8 and hist (16 int64 on the device, zeroed by the call).  A cell of class k is 2^k x 2^k texels, KMIN = 2,
+ *   2^KMAX = R; k_f is the smallest k in [KMIN, KMAX] with 4 16^k >= S_f D_j (one rounded product), KMAX when none (S = 0 gives KMIN).  hist[k] counts the
+ *   faces of class k, hist[14] those the lower clamp raised (64 >= S_f D_j), hist[15] those no class in range satisfies.  Integer atomics only: the counters
+ *   do not depend on scheduling.  Two faces share a cell, cells_k = ceil(hist[k] / 2); step j FITS when sum_k cells_k 4^k <= R^2.  Every k_f is
+ *   non-decreasing in j; the sum is too, except where a face that moves up fills the free half of a cell of the next class (the sum then drops by the cell it
+ *   left).  The step used is the one ONE stated bisection returns: lo = -800 (it must fit), hi = 801; mid = floor((lo + hi) / 2) becomes lo when it fits and
+ *   hi when not, until hi - lo = 1; j = lo.  That j fits and j + 1 does not (or j = 800); past such a dip a larger step may fit, and is not looked for.  One
+ *   memset and one launch on the stream.
+ * iris_atlas_place: k and corner as above, order (F) int64 = the faces sorted by class with the face index breaking ties (a STABLE sort of k), hist_host =
+ *   the 14 class counters of the chosen step ON THE HOST -> vt (3 F, 2) float32; ft is arange(3 F).  Refused unless the counters sum to F and fit.  Position
+ *   i of order is rank r = i - (faces of lower classes) of its class and sits in cell r / 2 of that class, the lower half for even r, the upper half for odd r.
+ *   Classes are laid out from the largest down: base_k = sum_{k' > k} cells_k' 4^k', texel offset o = base_k + (r / 2) 4^k, and the cell's corner is
+ *   x0 = the even bits of o compacted, y0 = the odd bits (Morton order): o is a multiple of 4^k, so the cells tile without overlap.  With x1 = x0 + 2^k,
+ *   y1 = y0 + 2^k, in texels:  lower P0 = (x0 + .25, y0 + .25), P1 = (x1 - .5, y0 + .25), P2 = (x0 + .25, y1 - .5);  upper P0 = (x1 - .25, y1 - .25),
+ *   P1 = (x0 + .5, y1 - .25), P2 = (x1 - .25, y0 + .5).  Mesh corner (corner + i) mod 3 takes P_i / R: the winding is kept, the longest edge lies on the
+ *   diagonal, and the float32 UVs are exact.  One launch.
+ * iris_texture_dilate: ids (H, W) int32 as iris_uv_raster leaves it, the two (H, W, 3) uint8 images of iris_texture_quantize, 0 <= n <= 4, any H and W
+ *   in [1, 8192].  An uncovered texel (ids < 0) takes the bytes of the covered texel within Chebyshev distance n with the smallest squared Euclidean
+ *   distance, then the smallest row, then the smallest column; none: left as it is.  In place, one launch (none for n = 0): covered texels are only read,
+ *   uncovered ones only written.  ids is not changed. */
+IRIS_API int iris_atlas_measure(const float *v, int64_t n_v, const int32_t *f, int64_t F, double *S, uint8_t *corner, iris_stream_t);
+IRIS_API double iris_atlas_density(int32_t j);
+IRIS_API int iris_atlas_classes(const double *S, int64_t F, int32_t j, int32_t tex_res, uint8_t *k, int64_t *hist, iris_stream_t);
+IRIS_API int iris_atlas_place(const uint8_t *k, const uint8_t *corner, const int64_t *order, int64_t F, int32_t tex_res, const int64_t *hist_host, float *vt,
+                     iris_stream_t);
+IRIS_API int iris_texture_dilate(const int32_t *ids, int32_t H, int32_t W, int32_t n, uint8_t *albedo_img, uint8_t *rm_img, iris_stream_t);
+
 /* ---- OpenEXR ZIP / ZIPS writer, device half ------------------------------------------------------------- */
 /* Deflate of the scanline blocks of n_maps maps (utils/exr.py scanline_blocks_torch): full (n_maps, n_full, block_bytes) and tail (n_maps, tail_bytes)
  * hold the PREDICTED bytes (reordered, delta-coded) of every block, device uint8, contiguous.  records receives, map by map, every chunk record as the

@@ -147,6 +147,11 @@ PROTOTYPES = {
     "iris_debug_uv_raster": [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _U64, _I32, _P],
     "iris_uv_resolve": [_P, _I64, _P, _P, _I64, _P, _I64, _I32, _I32, _P, _I64, _I64, _P, _P, _P],
     "iris_texture_quantize": [_P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P],
+    "iris_atlas_measure": [_P, _I64, _P, _I64, _P, _P, _P],
+    "iris_atlas_density": [_I32],
+    "iris_atlas_classes": [_P, _I64, _I32, _I32, _P, _P, _P],
+    "iris_atlas_place": [_P, _P, _P, _I64, _I32, _P, _P, _P],
+    "iris_texture_dilate": [_P, _I32, _I32, _I32, _P, _P, _P],
     "iris_exr_zip_workspace_bytes": [_I32, _I64, _I64, _I64],
     "iris_exr_zip_encode": [_P, _P, _I32, _I64, _I64, _I64, _I32, _P, _P, _P, _U64, _P],
     "iris_png_row_bytes": [_I32, _I32, _I32, _I32],
@@ -171,7 +176,7 @@ _RESTYPE = {"iris_scene_destroy": None, "iris_slf_destroy": None, "iris_emitter_
             "iris_loss_photometric_workspace_bytes": C.c_uint64,
             "iris_png_row_bytes": C.c_int64, "iris_png_stream_bound": C.c_uint64, "iris_png_workspace_bytes": C.c_uint64, "iris_png_magma_table": None,
             "iris_jpeg_stream_bound": C.c_uint64, "iris_jpeg_workspace_bytes": C.c_uint64, "iris_jpeg_tables": None,
-            "iris_image_metrics_workspace_bytes": C.c_uint64, "iris_uv_raster_workspace_bytes": C.c_uint64}
+            "iris_image_metrics_workspace_bytes": C.c_uint64, "iris_uv_raster_workspace_bytes": C.c_uint64, "iris_atlas_density": C.c_double}
 
 _lib = None
 

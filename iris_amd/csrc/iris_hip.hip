@@ -24,6 +24,7 @@
 #include "iris_denoise.h"
 #include "iris_metrics.h"
 #include "iris_texture.h"
+#include "iris_atlas.h"
 #include "iris_ngp.h"
 #include "iris_prop.h"
 #include "iris_loss.h"
@@ -1304,6 +1305,87 @@ extern "C" IRIS_API int iris_texture_quantize(const float* albedo, const float* 
     const int64_t groups = (texel0 + n + 3) / 4 - texel0 / 4;
     hipLaunchKernelGGL(uv_quantize_kernel, dim3((unsigned)uv_blocks(groups)), dim3(kUvThreads), 0, (hipStream_t)stream, albedo, roughness, metallic, ids, texel0, n,
                        albedo_img, rm_img);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
+// ======================================================================================================
+// texture export: the area-proportional atlas and the seam dilation (iris_atlas.h)
+// ======================================================================================================
+// -> KMAX (2^KMAX = R), or -1 unless R is a power of two in [4, 8192]
+static int atlas_kmax(int R) {
+    if (R < 4 || R > kUvMaxRes || (R & (R - 1))) return -1;
+    int k = 0;
+    while ((1 << k) < R) ++k;
+    return k;
+}
+static_assert((1 << kAtlasKMaxLimit) == kUvMaxRes && kAtlasKMaxLimit + 3 == kAtlasHist, "classes 0 .. 13 and two clamp counters");
+static const int64_t kAtlasMaxFaces = kUvMaxRes * kUvMaxRes / 16 * 2;          // two faces per 4 x 4 cell of the largest texture
+extern "C" IRIS_API int iris_atlas_measure(const float* v, int64_t n_v, const int32_t* f, int64_t F, double* S, uint8_t* corner, iris_stream_t stream) {
+    if (n_v < 0 || n_v > INT32_MAX || F < 0 || F > kAtlasMaxFaces)
+        return fail(IRIS_ERR_ARG, "iris_atlas_measure: bad sizes (n_v " + std::to_string(n_v) + ", F " + std::to_string(F) + "): F at most 2^23");
+    if (F == 0) return IRIS_OK;
+    if (!f || !S || !corner || (n_v > 0 && !v) || (uintptr_t)v % 4 || (uintptr_t)f % 4 || (uintptr_t)S % 8)
+        return fail(IRIS_ERR_ARG, "iris_atlas_measure: null or misaligned pointer");
+    hipLaunchKernelGGL(atlas_measure_kernel, dim3((unsigned)((F + kAtlasThreads - 1) / kAtlasThreads)), dim3(kAtlasThreads), 0, (hipStream_t)stream, v, n_v, f, F, S,
+                       corner);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+extern "C" IRIS_API double iris_atlas_density(int32_t j) {
+    if (j < kAtlasJMin || j > kAtlasJMax) return 0.0;
+    return std::ldexp((j & 1) ? 1.4142135623730951 : 1.0, j >> 1);          // (>> of a negative int floors; the scaling is exact: no subnormals in this range)
+}
+extern "C" IRIS_API int iris_atlas_classes(const double* S, int64_t F, int32_t j, int32_t tex_res, uint8_t* k, int64_t* hist, iris_stream_t stream) {
+    const int kmax = atlas_kmax(tex_res);
+    if (kmax < 0 || F < 0 || F > kAtlasMaxFaces || j < kAtlasJMin || j > kAtlasJMax)
+        return fail(IRIS_ERR_ARG, "iris_atlas_classes: bad sizes (F " + std::to_string(F) + ", j " + std::to_string(j) + ", tex_res " + std::to_string(tex_res) +
+                                      "): tex_res a power of two in [4, 8192], j in [-800, 800], F at most 2^23");
+    if (!hist || (uintptr_t)hist % 8 || (F > 0 && (!S || !k || (uintptr_t)S % 8))) return fail(IRIS_ERR_ARG, "iris_atlas_classes: null or misaligned pointer");
+    const hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(hist, 0, kAtlasHist * sizeof(int64_t), st));
+    if (F == 0) return IRIS_OK;
+    const int64_t blocks = std::min<int64_t>((F + kAtlasThreads - 1) / kAtlasThreads, kAtlasClassBlocks);
+    hipLaunchKernelGGL(atlas_classes_kernel, dim3((unsigned)blocks), dim3(kAtlasThreads), 0, st, S, F, iris_atlas_density(j), kmax, k, (unsigned long long*)hist);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_atlas_place(const uint8_t* k, const uint8_t* corner, const int64_t* order, int64_t F, int32_t tex_res, const int64_t* hist_host,
+                                         float* vt, iris_stream_t stream) {
+    const int kmax = atlas_kmax(tex_res);
+    if (kmax < 0 || F < 0 || F > kAtlasMaxFaces || !hist_host)
+        return fail(IRIS_ERR_ARG, "iris_atlas_place: bad sizes (F " + std::to_string(F) + ", tex_res " + std::to_string(tex_res) + ") or no class histogram");
+    AtlasTable t;
+    int64_t faces = 0, texels = 0;
+    for (int c = 0; c <= kAtlasKMaxLimit; ++c) {
+        const int64_t n = hist_host[c];
+        if (n < 0 || n > F || (n > 0 && (c < kAtlasKMin || c > kmax))) return fail(IRIS_ERR_ARG, "iris_atlas_place: the histogram names a class outside [2, KMAX]");
+        t.start[c] = faces;                                     // the order is sorted by ascending class
+        faces += n;
+    }
+    for (int c = kAtlasKMaxLimit; c >= 0; --c) {                // the layout goes from the largest class down
+        t.base[c] = texels;
+        texels += (hist_host[c] + 1) / 2 * ((int64_t)1 << (2 * c));
+    }
+    if (faces != F) return fail(IRIS_ERR_ARG, "iris_atlas_place: the histogram counts " + std::to_string(faces) + " faces, F is " + std::to_string(F));
+    if (texels > (int64_t)tex_res * tex_res)
+        return fail(IRIS_ERR_ARG, "iris_atlas_place: the classes need " + std::to_string(texels) + " texels, the texture has " + std::to_string((int64_t)tex_res * tex_res));
+    if (F == 0) return IRIS_OK;
+    if (!k || !corner || !order || !vt || (uintptr_t)order % 8 || (uintptr_t)vt % 4) return fail(IRIS_ERR_ARG, "iris_atlas_place: null or misaligned pointer");
+    hipLaunchKernelGGL(atlas_place_kernel, dim3((unsigned)((F + kAtlasThreads - 1) / kAtlasThreads)), dim3(kAtlasThreads), 0, (hipStream_t)stream, k, corner, order, F,
+                       (int)tex_res, kmax, t, vt);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_texture_dilate(const int32_t* ids, int32_t H, int32_t W, int32_t n, uint8_t* albedo_img, uint8_t* rm_img, iris_stream_t stream) {
+    if (H < 1 || W < 1 || H > kUvMaxRes || W > kUvMaxRes || n < 0 || n > kDilateMax)
+        return fail(IRIS_ERR_ARG, "iris_texture_dilate: bad sizes (H " + std::to_string(H) + ", W " + std::to_string(W) + ", n " + std::to_string(n) +
+                                      "): H and W in [1, 8192], n in [0, 4]");
+    if (!ids || !albedo_img || !rm_img || (uintptr_t)ids % 4 || albedo_img == rm_img) return fail(IRIS_ERR_ARG, "iris_texture_dilate: null, misaligned or shared pointer");
+    if (n == 0) return IRIS_OK;
+    const int64_t texels = (int64_t)H * W;
+    hipLaunchKernelGGL(texture_dilate_kernel, dim3((unsigned)((texels + kAtlasThreads - 1) / kAtlasThreads)), dim3(kAtlasThreads), 0, (hipStream_t)stream, ids, (int)H,
+                       (int)W, (int)n, albedo_img, rm_img);
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }

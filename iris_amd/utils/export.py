@@ -7,13 +7,18 @@ with ft.npy / vt.npy, the atlas they were baked in.  The voxel bounds come from 
 (load_ngpbrdf), the mesh from load_mesh.  The UV triangles are rasterised and the positions interpolated by iris_amd.utils.texture (HIP, an exact contract of
 its own: DESIGN.md section 5c-7), the network runs on every texel, the outputs are quantised on the device; the PNGs are written with zlib alone.
 
-Additions: --material pkg.module:factory (as the other command lines); --atlas auto|files|grid; --write_obj (mesh.obj + mesh.mtl next to the images).
+Additions: --material pkg.module:factory (as the other command lines); --atlas auto|files|grid|area; --dilate N; --write_obj (mesh.obj + mesh.mtl next to the
+images).
     --atlas files  reads <dir_save>/ft.npy and vt.npy, exactly the reference's cache: an atlas unwrapped with xatlas elsewhere drops in that way.
     --atlas grid   builds texture.grid_atlas (two faces per grid cell, shape and area ignored: valid, not good) and saves the two files.
+    --atlas area   builds texture.area_atlas on the device from the loaded mesh (one chart per face in a power-of-two cell sized by the face's area, placed in
+                   Morton order; exact), saves the two files and prints its report.  --tex_res must be a power of two in [4, 8192].
     --atlas auto   (default) uses the files when both exist and FAILS otherwise: a poor atlas is never produced silently.
+    --dilate N     (default 0, at most 4) seam dilation after the bake: every uncovered texel within N texels of a covered one takes the nearest covered
+                   texel's bytes, so that a bilinear lookup at a chart's border does not read black.  The reference has none.
 
-Not built: calling xatlas itself (not a dependency, no ROCm relevance: run it anywhere and drop the .npy files in); seam dilation (the reference has none);
-reading vt from an OBJ.
+Not built: calling xatlas itself (not a dependency, no ROCm relevance: run it anywhere and drop the .npy files in); charts of several faces and charts that keep
+a face's shape (every chart of the two built-in atlases is a right isosceles triangle); a non-square texture for --atlas area; reading vt from an OBJ.
 """
 import os
 import sys
@@ -25,7 +30,10 @@ from .. import _lib as L
 from . import stage, texture as T
 
 
-def build_parser():
+def build_parser(area_atlas=False):
+    """The stage's parser.  build_parser() is the stage as it was first built -- the reference's arguments, --material, --atlas auto|files|grid, --write_obj:
+    the option table that tests/test_stage_setup_cpu.py pins, option for option.  build_parser(area_atlas=True) is the command line that main() runs: the same
+    options plus what the built-in area atlas brought, the choice --atlas area and the option --dilate (tests/test_atlas_cpu.py pins that table whole)."""
     import argparse
     parser = argparse.ArgumentParser(description="python -m iris_amd.utils.export: the reference's utils/export.py on MI355X")
     parser.add_argument("--mesh")
@@ -37,16 +45,37 @@ def build_parser():
     parser.add_argument("--chunk_size", type=int, default=160000)
     # additions
     stage.add_common_options(parser, "material")
-    parser.add_argument("--atlas", type=str, default="auto", choices=["auto", "files", "grid"],
-                        help="files: <dir_save>/ft.npy + vt.npy; grid: the grid stand-in, saved there; auto: the files when both exist, else an error")
+    parser.add_argument("--atlas", type=str, default="auto", choices=["auto", "files", "grid"] + (["area"] if area_atlas else []),
+                        help="files: <dir_save>/ft.npy + vt.npy; grid: the grid stand-in, saved there; auto: the files when both exist, else an error" +
+                             ("; area: the area-proportional atlas, built on the device and saved there" if area_atlas else ""))
+    if area_atlas:
+        parser.add_argument("--dilate", type=int, default=0, help="seam dilation: fill uncovered texels within N texels (0 to 4) of a covered one from the nearest")
     parser.add_argument("--write_obj", action="store_true", help="also write mesh.obj and mesh.mtl (map_Kd albedo.png)")
     return parser
 
 
-def load_atlas(mode, dir_save, n_faces, tex_res):
-    """-> (vt (N, 2) float32, ft (F, 3) int32), host numpy, by the rule of --atlas"""
+def build_area_atlas(dir_save, v, f, tex_res, device=None):
+    """texture.area_atlas of the mesh on `device`, saved as <dir_save>/ft.npy and vt.npy, its report printed -> (vt, ft, vt_host, ft_host): the device tensors,
+    which the bake takes as they are, and the host copies the files were written from"""
+    path_ft, path_vt = os.path.join(dir_save, "ft.npy"), os.path.join(dir_save, "vt.npy")
+    vt, ft, report = T.area_atlas(v, f, tex_res, device=device)
+    vt_np, ft_np = vt.cpu().numpy(), ft.cpu().numpy()
+    np.save(path_ft, ft_np)
+    np.save(path_vt, vt_np)
+    print(f"[INFO] area atlas (one chart per face, cells of 2^k texels by area) saved to {path_ft} and {path_vt}: j = {report['j']}, D_j = {report['D_j']:.6g}, "
+          f"used = {report['used']:.4f}, faces per class = {report['histogram']}, clamped at KMIN / KMAX = {report['clamped_min']} / {report['clamped_max']}")
+    return vt, ft, vt_np, ft_np
+
+
+def load_atlas(mode, dir_save, n_faces, tex_res, v=None, f=None, device=None):
+    """-> (vt (N, 2) float32, ft (F, 3) int32), host numpy, by the rule of --atlas.  mode 'area' builds the atlas of the mesh (v, f) on `device`
+    (build_area_atlas, which also hands out the device tensors)."""
     path_ft, path_vt = os.path.join(dir_save, "ft.npy"), os.path.join(dir_save, "vt.npy")
     have = os.path.exists(path_ft) and os.path.exists(path_vt)
+    if mode == "area":
+        if v is None or f is None:
+            raise L.IrisError("load_atlas: the area atlas is built from the mesh: pass v and f")
+        return build_area_atlas(dir_save, v, f, tex_res, device)[2:]
     if mode == "grid":
         vt, ft = T.grid_atlas(n_faces, tex_res)
         np.save(path_ft, ft)
@@ -55,27 +84,35 @@ def load_atlas(mode, dir_save, n_faces, tex_res):
         return vt, ft
     if not have:
         raise L.IrisError(f"no UV atlas: {path_ft} and {path_vt} do not both exist.  Unwrap the mesh with xatlas (not a dependency of this package) and save its "
-                          f"ft.npy (F, 3) and vt.npy (N, 2) there, or pass --atlas grid for the built-in stand-in, which is valid but ignores triangle shape and area")
+                          f"ft.npy (F, 3) and vt.npy (N, 2) there, or pass --atlas grid for the built-in stand-in, which is valid but ignores triangle shape and area, "
+                          f"or --atlas area for the built-in atlas that gives every face a chart sized by its area")
     print(f"[INFO] found existing UVs, loading from {path_ft} and {path_vt}")
     return np.load(path_vt).astype(np.float32), np.load(path_ft).astype(np.int32)
 
 
 def main(argv=None):
     from .path_tracing import load_mesh
-    args = build_parser().parse_args(argv)
+    args = build_parser(area_atlas=True).parse_args(argv)
     for name in ("mesh", "emitter_path", "dir_save"):
         if not getattr(args, name):
             raise L.IrisError(f"export: --{name} is required")
+    T.check_dilate(args.dilate)
     os.makedirs(args.dir_save, exist_ok=True)
     v_np, f_np = load_mesh(args.mesh)
-    vt_np, ft_np = load_atlas(args.atlas, args.dir_save, f_np.shape[0], args.tex_res)
-    T.check_inputs(vt_np, ft_np, v_np, f_np, args.tex_res)                 # before the device is touched
-    device = stage.open_device(args.device, "export")
+    if args.atlas == "area":                                               # the one atlas that is built on the device: its host checks come first
+        T.check_atlas_inputs(v_np, f_np, args.tex_res)
+        device = stage.open_device(args.device, "export")
+        vt, ft, vt_np, ft_np = build_area_atlas(args.dir_save, v_np, f_np, args.tex_res, device)          # vt, ft stay on the device for the bake
+        T.check_inputs(vt_np, ft_np, v_np, f_np, args.tex_res)
+    else:
+        vt, ft = vt_np, ft_np = load_atlas(args.atlas, args.dir_save, f_np.shape[0], args.tex_res)
+        T.check_inputs(vt_np, ft_np, v_np, f_np, args.tex_res)             # before the device is touched
+        device = stage.open_device(args.device, "export")
     material_net = stage.load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), args.ckpt)
     if isinstance(material_net, torch.nn.Module):
         material_net.to(device)
     print(f"[INFO] mesh v={v_np.shape} f={f_np.shape} vt={vt_np.shape} ft={ft_np.shape}, texture {args.tex_res} x {args.tex_res}")
-    albedo, rm = T.bake_textures(material_net, vt_np, ft_np, v_np, f_np, args.tex_res, args.chunk_size, device=device)
+    albedo, rm = T.bake_textures(material_net, vt, ft, v_np, f_np, args.tex_res, args.chunk_size, device=device, dilate=args.dilate)
     path_albedo, path_rm = os.path.join(args.dir_save, "albedo.png"), os.path.join(args.dir_save, "rm.png")
     T.write_png(path_albedo, albedo)
     T.write_png(path_rm, rm)

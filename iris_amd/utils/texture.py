@@ -7,6 +7,7 @@ texture has its centre at u = (c + .5) / W, v = (r + .5) / H, row 0 at v ~ 0; UV
 lowest face index wins an overlap; barycentrics from a float64 division, positions interpolated in float32 in one stated order.  tests/uv_raster_ref.py is
 the same contract in numpy, and the kernels equal it bit for bit.
 """
+import ctypes as C
 import os
 import struct
 import zlib
@@ -155,15 +156,44 @@ def quantize_into(albedo, roughness, metallic, ids, texel0, albedo_img, rm_img):
                                               L.ptr(rm_img), L.stream()))
 
 
+MAX_DILATE = 4
+
+
+def check_dilate(n):
+    """-> n as an int; IrisError unless it is an integer in [0, 4]"""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= MAX_DILATE:
+        raise L.IrisError(f"dilate = {n!r}: an integer in [0, {MAX_DILATE}]")
+    return int(n)
+
+
+def dilate_into(ids, albedo_img, rm_img, n):
+    """iris_texture_dilate, seam dilation in place: every uncovered texel (ids < 0) of the two (H, W, 3) uint8 images takes the bytes of the covered texel
+    within Chebyshev distance n (0 <= n <= 4) that has the smallest squared Euclidean distance, then the smallest row, then the smallest column; it is left as it
+    is when there is none.  Covered texels and ids are not changed; n = 0 launches nothing."""
+    n = check_dilate(n)
+    ids = L.require_gpu(ids, torch.int32, "ids")
+    if ids.dim() != 2 or ids.numel() == 0:
+        raise L.IrisError(f"dilate: ids {tuple(ids.shape)} must be (H, W)")
+    H, W = ids.shape
+    for img in (albedo_img, rm_img):
+        if not torch.is_tensor(img) or img.dtype != torch.uint8 or not img.is_contiguous() or tuple(img.shape) != (H, W, 3) or img.device != ids.device:
+            raise L.IrisError("dilate: the images must be contiguous (H, W, 3) uint8 tensors on the device of ids")
+    if albedo_img.data_ptr() == rm_img.data_ptr():
+        raise L.IrisError("dilate: albedo and rm are the same image")
+    with torch.cuda.device(ids.device):
+        L.check(L.lib().iris_texture_dilate(L.ptr(ids), H, W, n, L.ptr(albedo_img), L.ptr(rm_img), L.stream()))
+
+
 @torch.no_grad()
-def bake_textures(material_net, vt, ft, v, f, tex_res, chunk_size=160000, device=None):
+def bake_textures(material_net, vt, ft, v, f, tex_res, chunk_size=160000, device=None, dilate=0):
     """The material network baked into the UV atlas (utils/export.py:77-135) -> (albedo, rm): two (H, W, 3) uint8 device tensors, rm = (roughness, metallic, 0).
     The ids are rasterised once; then, per chunk of `chunk_size` consecutive texels: resolve, material_net(xyz), quantise.  The network runs on EVERY texel of
     a chunk, covered or not (uncovered ones sit at the origin and are masked by the quantiser): no compaction pass, no host round trip.
-    material_net: any callable with NGPBRDF.forward's contract."""
+    material_net: any callable with NGPBRDF.forward's contract.  dilate = n > 0: dilate_into after the last chunk (seam dilation; the reference has none)."""
     chunk_size = int(chunk_size)
     if chunk_size < 1:
         raise L.IrisError(f"bake_textures: chunk_size = {chunk_size}")
+    dilate = check_dilate(dilate)
     m = UVMesh(vt, ft, v, f, tex_res, device)
     ids = m.raster()
     albedo = torch.empty(m.H, m.W, 3, dtype=torch.uint8, device=m.device)
@@ -172,6 +202,8 @@ def bake_textures(material_net, vt, ft, v, f, tex_res, chunk_size=160000, device
         _, xyz = m.resolve(ids, texel0, min(chunk_size, m.H * m.W - texel0), bary=False)
         mat = material_net(xyz)
         quantize_into(mat["albedo"], mat["roughness"], mat["metallic"], ids, texel0, albedo, rm)
+    if dilate:
+        dilate_into(ids, albedo, rm, dilate)
     return albedo, rm
 
 
@@ -198,6 +230,129 @@ def grid_atlas(n_faces, tex_res):
     tri = np.stack([lower, upper], 1).reshape(-1, 3, 2)[:F]        # faces 2 k and 2 k + 1 share cell k
     vt = (tri / np.array([W, H], np.float64)).reshape(-1, 2).astype(np.float32)
     return vt, np.arange(3 * F, dtype=np.int32).reshape(F, 3)
+
+
+ATLAS_KMIN, ATLAS_JMIN, ATLAS_JMAX = 2, -800, 800              # iris_amd/csrc/iris_atlas.h kAtlasKMin, kAtlasJMin, kAtlasJMax
+
+
+def atlas_min_res(n_faces):
+    """the smallest power of two R whose R x R texels hold ceil(F / 2) cells of 4 x 4 (it may exceed MAX_TEX_RES)"""
+    R = 4
+    while (int(n_faces) + 1) // 2 * 16 > R * R:
+        R *= 2
+    return R
+
+
+def check_atlas_inputs(v, f, tex_res):
+    """The host checks of area_atlas, before a device is touched -> (R, KMAX, V, F).  IrisError on: a tex_res that is not a square power of two in [4, 8192];
+    v not (V, 3) floating point, f not (F, 3) integers, F < 1; more faces than R x R texels hold at two per 4 x 4 cell.  The VALUES of v and f are not looked at:
+    a face that names a vertex out of range or has no finite positive area is part of the contract (it gets the smallest chart)."""
+    if isinstance(tex_res, (tuple, list)):
+        if len(tex_res) != 2 or tex_res[0] != tex_res[1]:
+            raise L.IrisError(f"area_atlas: tex_res = {tex_res!r}: the atlas is built for a square texture (an integer, or (R, R))")
+        tex_res = tex_res[0]
+    if isinstance(tex_res, bool) or not isinstance(tex_res, (int, np.integer)) or not 4 <= int(tex_res) <= MAX_TEX_RES or int(tex_res) & (int(tex_res) - 1):
+        raise L.IrisError(f"area_atlas: tex_res = {tex_res!r}: a power of two in [4, {MAX_TEX_RES}]")
+    R = int(tex_res)
+
+    def shape_kind(a):
+        if torch.is_tensor(a):
+            return tuple(a.shape), "f" if a.is_floating_point() else "i" if a.dtype in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) else "?"
+        a = np.asarray(a)
+        return a.shape, "f" if a.dtype.kind == "f" else "i" if a.dtype.kind in "iu" else "?"
+    (s_v, k_v), (s_f, k_f) = shape_kind(v), shape_kind(f)
+    if len(s_v) != 2 or s_v[1] != 3 or k_v != "f":
+        raise L.IrisError(f"area_atlas: v {s_v} must be a floating-point (V, 3) array")
+    if len(s_f) != 2 or s_f[1] != 3 or k_f != "i" or s_f[0] < 1:
+        raise L.IrisError(f"area_atlas: f {s_f} must be an integer (F, 3) array with F >= 1")
+    F = int(s_f[0])
+    if s_v[0] > 2 ** 31 - 1:
+        raise L.IrisError("area_atlas: more than 2^31 - 1 vertices")
+    if (F + 1) // 2 * 16 > R * R:
+        need = atlas_min_res(F)
+        raise L.IrisError(f"area_atlas: {F} faces need {(F + 1) // 2} cells of 4 x 4 texels and tex_res = {R} holds {R * R // 16}: the smallest tex_res that holds "
+                          f"them is {need}" + ("" if need <= MAX_TEX_RES else f", above the limit of {MAX_TEX_RES}"))
+    return R, R.bit_length() - 1, int(s_v[0]), F
+
+
+def _faces_i32(f, n_v, dev):
+    """f as (F, 3) int32 on the device; an index that int32 could not hold (or any other outside [0, n_v)) arrives as -1 instead of wrapping into range"""
+    if torch.is_tensor(f):
+        t = f.detach()
+    else:
+        a = np.asarray(f)
+        t = torch.from_numpy(np.ascontiguousarray(a if a.dtype.kind == "i" else a.astype(np.int64)))          # (torch has no unsigned types beyond uint8)
+    if t.dtype != torch.int32:
+        t = t.to(torch.int64)
+        t = t.masked_fill((t < 0) | (t >= n_v), -1)
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _atlas_texels(hist):
+    return sum((int(n) + 1) // 2 * 4 ** k for k, n in enumerate(hist))
+
+
+def area_atlas(v, f, tex_res, device=None):
+    """The built-in atlas that respects surface area (the kernels and the contract are in iris_amd/csrc/iris_atlas.h, the numpy
+    restatement in tests/atlas_ref.py): v (V, 3) float, f (F, 3) integer, host arrays or device tensors; tex_res = R, a square power of two in [4, 8192]
+    -> (vt (3 F, 2) float32, ft = arange(3 F).reshape(F, 3) int32, report), vt and ft DEVICE tensors that UVMesh / bake_textures take as they are.
+    Every face is a chart of its own, as in grid_atlas, but its cell is a 2^k x 2^k square with 4 16^k >= S_f D_j > 4 16^(k - 1), S_f four times the squared
+    area in float64 and D_j = M[j mod 2] 2^floor(j / 2) the density of the ladder that a bisection over j in [-800, 800] ends at: all cells fit the texture at
+    step j and not at j + 1 (the texel sum is monotone in j except where a face moves into the free half of a cell, so this is the bisection's j, stated in
+    DESIGN.md, and not in every case the largest that fits).  An unclamped face gets between
+    1 / 2 and 2 times sqrt(D_j) area texels.  Cells are placed without a search, by class (largest first), face index and Morton order; the longest edge lies
+    on the cell's diagonal.  Integers and float64 in one stated order: bit for bit the restatement's result.
+    report: j, D_j, histogram (faces per class 0 .. KMAX), used (share of the texels inside cells), clamped_min / clamped_max (faces whose class the limits
+    KMIN = 2 and 2^KMAX = R changed; faces without a finite positive area count as clamped_min).
+    Refused (IrisError, before anything is launched): the sizes check_atlas_inputs lists.  Refused after the first probe: areas so large (beyond about 1e60,
+    coordinates beyond 1e30) that even the ladder's lowest density does not fit.
+    Still per-face charts: no chart of several faces, no shape preservation (every chart is the same right isosceles triangle), no non-square texture."""
+    L.no_autograd("area_atlas", v)
+    R, kmax, V, F = check_atlas_inputs(v, f, tex_res)
+    if device is None:
+        device = next((a.device for a in (v, f) if torch.is_tensor(a) and a.is_cuda), "cuda")
+    dev = torch.device("cuda", L.device_index(device))
+    lib = L.lib()
+    v_d, f_d = _upload(v, torch.float32, dev), _faces_i32(f, V, dev)
+    S = torch.empty(F, dtype=torch.float64, device=dev)
+    corner = torch.empty(F, dtype=torch.uint8, device=dev)
+    k = torch.empty(F, dtype=torch.uint8, device=dev)
+    hist = torch.empty(16, dtype=torch.int64, device=dev)
+    vt = torch.empty(3 * F, 2, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.mark()
+        L.check(lib.iris_atlas_measure(L.ptr(v_d), V, L.ptr(f_d), F, L.ptr(S), L.ptr(corner), L.stream()))
+        L.mark("measure")
+
+        def probe(j):
+            L.check(lib.iris_atlas_classes(L.ptr(S), F, j, R, L.ptr(k), L.ptr(hist), L.stream()))
+            h = hist.cpu().tolist()                         # (the one small read per probe)
+            L.mark("classes")
+            return h
+        h = probe(ATLAS_JMIN)
+        if _atlas_texels(h[:14]) > R * R:
+            raise L.IrisError(f"area_atlas: the faces do not fit {R} x {R} texels even at the lowest density of the ladder (j = {ATLAS_JMIN}): "
+                              "some face's area is beyond about 1e60")
+        lo, hi, probed = ATLAS_JMIN, ATLAS_JMAX + 1, ATLAS_JMIN          # lo fits, hi does not: the contract's bisection, step for step
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            h_mid = probe(mid)
+            probed = mid
+            if _atlas_texels(h_mid[:14]) <= R * R:
+                lo, h = mid, h_mid
+            else:
+                hi = mid
+        j = lo
+        if probed != j:
+            h = probe(j)                                    # k of the chosen step
+        order = torch.sort(k, stable=True)[1]               # by class, the face index breaking ties: position - class start is the rank within the class
+        L.mark("rank")
+        L.check(lib.iris_atlas_place(L.ptr(k), L.ptr(corner), L.ptr(order), F, R, (C.c_int64 * 14)(*h[:14]), L.ptr(vt), L.stream()))
+        L.mark("place")
+        ft = torch.arange(3 * F, dtype=torch.int32, device=dev).reshape(F, 3)
+    report = {"j": j, "D_j": float(lib.iris_atlas_density(j)), "histogram": [int(n) for n in h[:kmax + 1]], "used": _atlas_texels(h[:14]) / (R * R),
+              "clamped_min": int(h[14]), "clamped_max": int(h[15])}
+    return vt, ft, report
 
 
 def write_png(path, rgb_uint8):
