@@ -128,6 +128,10 @@ IRIS_API int iris_sample_specular_v(const float *u2, const float *wo, const floa
                            float *wi, float *pdf, float *w0, float *w1, iris_stream_t);
 
 /* ---- a5: VoxelSLF.spatial_idx/forward (model/slf.py:41-70), SLFEmitter.eval_emitter (model/emitter.py:180-221) */
+/* The voxel coordinate of every entry point that takes positions (this one, iris_eval_emitter, iris_slf_scatter_add, iris_voxel_histogram, the bake and
+ * the view pools) is the reference's float32 expression ((x - voxel_min) / (voxel_max - voxel_min) * H).long().clamp(0, H - 1), one IEEE operation per step.
+ * The cast: truncation toward zero where the value is finite and of magnitude below 2^63, INT64_MIN otherwise (NaN, +-inf, magnitude >= 2^63), then the
+ * clamp -- so a huge finite coordinate below 2^63 lands in cell H - 1, and NaN, +inf and 2^63 and above in cell 0.  No position reads outside the grid. */
 IRIS_API int iris_slf_lookup(const iris_slf *, const float *x, int64_t B, int64_t *idx /*nullable*/, float *rgb /*nullable*/,
                     iris_stream_t);
 /* roughness: NULL <=> the reference's roughness=None; otherwise (B) f32.  The iris_slf may be NULL when the cache cannot be reached: roughness NULL, or

@@ -231,10 +231,13 @@ struct EmitDev {
 };
 
 // model/slf.py:41-54 spatial_idx: ((x-vmin)/(vmax-vmin)*H).long().clamp(0,H-1) -> inds[z,y,x]
+// The cast rule (.long() on the reference's platform; tests/voxel_ref.py states it and tests/test_voxel_slf.py holds every lookup to it): f truncated toward
+// zero where it is finite and |f| < 2^63, INT64_MIN otherwise (+-inf, NaN, |f| >= 2^63); then the clamp.  So f in [H, 2^63) gives H - 1, and NaN,
+// +inf and f >= 2^63 give 0, as every negative f does.  (2^63 exactly, not "about 9.2e18": a float in [9.2e18, 2^63) still has a valid int64.)
 __device__ __forceinline__ int voxel_coord(float p, const SlfDev& s) {
     float f = (p - s.vmin) / s.den * (float)s.H;
-    int v = (int)f;                    // v_cvt_i32_f32: truncates, saturates, NaN -> 0
-    if (!(f < 9.2e18f)) v = 0;         // torch's int64 cast of +inf/huge/NaN is INT64_MIN -> clamps to 0
+    int v = (int)f;                    // v_cvt_i32_f32: truncates, saturates (f >= 2^31 -> INT_MAX -> H - 1; f <= -2^31 -> INT_MIN -> 0), NaN -> 0
+    if (!(f < 0x1p63f)) v = 0;         // +inf, NaN, f >= 2^63: INT64_MIN -> clamps to 0
     return min(max(v, 0), s.H - 1);
 }
 __device__ __forceinline__ int slf_index(const SlfDev& s, f3 p) {

@@ -563,9 +563,9 @@ static inline int64_t slf_spatial_idx(const orc_slf *s, v3 p) {
     for (int k = 0; k < 3; ++k) {
         float f = q[k] * (float)s->H;
         int64_t v;
-        /* .long(): truncation toward zero; out-of-range/NaN is UB in C, saturate explicitly
-           (torch on x86 yields INT64_MIN, which the clamp maps to 0) */
-        if (!(f > -9.2e18f)) v = INT64_MIN; else if (f >= 9.2e18f) v = INT64_MIN; else v = (int64_t)f;
+        /* .long(): truncation toward zero where f is finite and |f| < 2^63; anything else (NaN, +-inf, |f| >= 2^63) is UB in C, so it is
+           written out: torch on x86 yields INT64_MIN, which the clamp maps to 0.  (-2^63 itself is INT64_MIN either way.) */
+        if (!(f > -0x1p63f)) v = INT64_MIN; else if (f >= 0x1p63f) v = INT64_MIN; else v = (int64_t)f;
         if (v < 0) v = 0;
         if (v > s->H - 1) v = s->H - 1;
         c[k] = v;

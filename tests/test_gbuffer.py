@@ -5,22 +5,7 @@ import pytest
 import torch
 
 from conftest import golden
-
-
-def np_scatter_add(inds, H, vmin, vmax, x, rgb, kv):
-    """model/slf.py:41-61 in numpy: spatial_idx, then sequential scatter_add of radiance and count."""
-    q = ((x - np.float32(vmin)) / np.float32(vmax - vmin) * np.float32(H)).astype(np.int64).clip(0, H - 1)
-    idx = inds[q[:, 2], q[:, 1], q[:, 0]]
-    rad = np.zeros((kv, 3), np.float32); cnt = np.zeros(kv, np.int64)
-    np.add.at(rad, idx, rgb); np.add.at(cnt, idx, 1)
-    return rad, cnt
-
-
-def np_voxel_histogram(x, vmin, vmax, H):
-    """slf_bake.py:104-110"""
-    q = ((x - np.float32(vmin)) / np.float32(vmax - vmin) * np.float32(H)).astype(np.int64).clip(0, H - 1)
-    lin = q[:, 0] + q[:, 1] * H + q[:, 2] * H * H
-    return np.bincount(lin, minlength=H ** 3).astype(np.float32).reshape(H, H, H)
+from voxel_ref import np_scatter_add, np_voxel_histogram          # the index with its cast written out: one restatement for this file and tests/test_voxel_slf*.py
 
 
 def test_numpy_restatement_matches_reference_scatter_add():

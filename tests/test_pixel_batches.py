@@ -2,7 +2,8 @@
 
 Every comparison is torch.equal: the kernel computes the rays with the whole-view kernel's own per-pixel function, decodes 8-bit levels as
 np.float32(u / 255.0) and copies everything else; PixelSet adds indexing only.  Three views of 5 x 7 pixels with distinct cameras, as real (K) and
-as synthetic (focal) views.  No test hands the device an id outside [0, 105)."""
+as synthetic (focal) views.  No test here hands the device an id outside [0, 105): tests/test_raygen_ref64.py does (zero rows, segment -1), and asks
+the kernel for rows of a view larger than one pass of the whole-view kernel."""
 import ctypes as C
 import itertools
 

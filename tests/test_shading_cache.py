@@ -1,11 +1,20 @@
 """8(f)-3: packed shading cache + the BRDF trainer's shading combine (utils/dataset/scannetpp/dataset.py:359-377,409-414;
 train_brdf_crf.py:195-203).  GPU tests call the HIP kernels through the C ABI and compare with the golden vectors captured from the
-reference (tests/golden/shade_cached.npz) and bit for bit with the oracle."""
+reference (tests/golden/shade_cached.npz) and bit for bit with the oracle.
+
+Below them, the combine and its three gradients per element against the float64 closed form of tests/shade_ref64.py, through ShadingCache.shade and
+autograd: R in {1, 2, 5, 6, 8}; roughness at every level knot, at its float neighbours and outside [0.02, 1] (brdf_ref64.lerp_case); metallic and albedo
+with exact 0 and 1; a 4099-row cache indexed by a permutation, with repeats and not at all; batches of 1, 63, 65 and 2^15.  The bounds are the rounding
+counts of shade_ref64's docstring, which tests/test_shading_cache_cpu.py validates on the oracle and on the float32 restatement.  g_roughness is exactly 0
+wherever floor and ceil of the level coincide.
+
+Worst |err| / tol on an MI355X over all R and batches: L 0.41, g_albedo 0.60, g_metallic 0.40, g_roughness 0.38 (the oracle's figures: the kernels' bits)."""
 import os
 
 import numpy as np
 import pytest
 
+import shade_ref64 as SR
 from conftest import golden, rel_l2
 
 R = 6
@@ -130,3 +139,54 @@ def test_cache_from_bake_and_exr_round_trip(tmp_path):
     c2 = ShadingCache.from_exr_dir(str(tmp_path), 2, 6, dev)
     assert torch.equal(c1.rows, c2.rows)
     assert float(c1.rows.abs().sum()) > 0
+
+
+class HipShade:
+    """ShadingCache.shade and torch.autograd.grad, numpy in / numpy out"""
+    name = "hip"
+
+    def cache(self, R):
+        import torch
+        from iris_amd.utils.shading_cache import ShadingCache
+        dev = torch.device("cuda:0")
+        T = lambda a: torch.from_numpy(np.array(a)).to(dev)
+        d, s0, s1 = SR.cache_maps(R)
+        cache = ShadingCache(SR.N_ROWS, R, dev)
+        cache.rows.fill_(float("nan"))                                  # (put_view writes every lane, the padding included)
+        cache.put_view(0, T(d), [T(m) for m in s0], [T(m) for m in s1])
+        return cache, T
+
+    def shade(self, c):
+        import torch
+        cache, T = self.cache(c["R"])
+        a, m, r = (T(c[k]).requires_grad_(True) for k in ("albedo", "metallic", "rough"))
+        L = cache.shade(None if c["idx"] is None else T(c["idx"]), a, m, r)
+        ga, gm, gr = torch.autograd.grad(L, [a, m, r], T(c["gL"]))
+        assert gm.shape == m.shape and gr.shape == r.shape
+        return L.detach().cpu().numpy(), ga.cpu().numpy(), gm.reshape(-1).cpu().numpy(), gr.reshape(-1).cpu().numpy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("batch", SR.BATCHES, ids=SR.batch_id)
+@pytest.mark.parametrize("levels", SR.LEVELS)
+def test_shade_against_float64(levels, batch):
+    SR.check_shade(HipShade(), levels, batch)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("levels", SR.LEVELS)
+def test_gather_returns_the_packed_maps(levels):
+    """gather: the maps bit for bit for every R, through a permutation, an index with repeats and no index; the rows' padding lanes are zero"""
+    cache, T = HipShade().cache(levels)
+    d, s0, s1 = SR.cache_maps(levels)
+    bits = lambda a: np.ascontiguousarray(a, np.float32).view(np.int32)
+    for B, mode in SR.BATCHES:
+        idx = SR.case(levels, B, mode)["idx"]
+        rows = np.arange(SR.N_ROWS) if idx is None else idx
+        di, sp0, sp1 = (t.cpu().numpy() for t in cache.gather(None if idx is None else T(idx)))
+        assert di.shape == (len(rows), 3) and sp0.shape == (len(rows), levels, 3) and sp1.shape == (len(rows), levels, 3)
+        assert np.array_equal(bits(di), bits(d[rows]))
+        assert np.array_equal(bits(sp0), bits(np.stack(s0, 1)[rows])) and np.array_equal(bits(sp1), bits(np.stack(s1, 1)[rows]))
+    raw = cache.rows.cpu().numpy()
+    assert raw.shape[1] % 4 == 0 and raw.shape[1] >= 4 + 6 * levels
+    assert (bits(raw[:, 3]) == 0).all() and (bits(raw[:, 4 + 6 * levels:]) == 0).all()
