@@ -649,6 +649,24 @@ IRIS_API int iris_resize_tables(int mode, int ns, int nd, int32_t *ofs, int16_t 
 IRIS_API int iris_resize_u8(const void *const *images, int n_images, int Hs, int Ws, int channels, int mode, const int32_t *xofs, const int16_t *xcoef,
                    const int32_t *yofs, const int16_t *ycoef, uint8_t *out, int Ht, int Wt, iris_stream_t);
 
+/* ---- 5c-17: the exported textures read back (utils/closest.py, model/texture.py; the contracts: DESIGN.md 5c-17) ----------------- */
+/* iris_closest_point: per query point xs[i] (B, 3) the closest point of the scene's mesh.  tri (B) int64 = the ORIGINAL face index, -1 when there is none (a
+ * mesh without a triangle of non-zero area, a query point that is not finite); bary (B, 2) = (b1, b2) as iris_intersect's uv, b1, b2 >= 0, b1 + b2 <= 1;
+ * pos (B, 3) = (1 - b1 - b2) p0 + b1 p1 + b2 p2 as iris_intersect interpolates it; dist2 (B) the squared distance as computed, +inf when tri = -1.  Any output
+ * pointer may be NULL.  The closest point of a triangle is the vertex / edge / interior classification in float32; the winner is the lexicographic minimum of
+ * (dist2, original index); triangles whose float32 cross product is exactly zero are skipped.  A scene in the default layout (IRIS_BVH4_Q8) only.  No atomics, no
+ * workspace, bitwise reproducible.  One launch; B = 0 launches nothing.
+ * iris_texture_sample: tri (B) int64 and bary (B, 2) as above, ft (F, 3) int32 and vt (n_vt, 2) f32 the UV triangles of the export, the two (H, W, 3) uint8
+ * images, H and W in [1, 8192] -> albedo (B, 3), roughness (B), metallic (B) f32: a bilinear fetch in the rasteriser's texel convention (texel (r, c) has its
+ * centre at u = (c + .5) / W, v = (r + .5) / H), bytes as byte / 255, lerp form; albedo linear, roughness = max(channel 0 of rm, 0.02), metallic = channel 1 of
+ * rm; tri outside [0, F) gives zeros and roughness 0.02.
+ * iris_texture_material: iris_closest_point, then iris_texture_sample at its (tri, bary), as ONE launch and bit for bit the two-call composition. */
+IRIS_API int iris_closest_point(const iris_scene *, const float *xs, int64_t B, int64_t *tri, float *bary, float *pos, float *dist2, iris_stream_t);
+IRIS_API int iris_texture_sample(const int64_t *tri, const float *bary, int64_t B, const int32_t *ft, int64_t F, const float *vt, int64_t n_vt,
+                        const uint8_t *albedo_img, const uint8_t *rm_img, int32_t H, int32_t W, float *albedo, float *roughness, float *metallic, iris_stream_t);
+IRIS_API int iris_texture_material(const iris_scene *, const float *xs, int64_t B, const int32_t *ft, int64_t F, const float *vt, int64_t n_vt,
+                          const uint8_t *albedo_img, const uint8_t *rm_img, int32_t H, int32_t W, float *albedo, float *roughness, float *metallic, iris_stream_t);
+
 /* ---- misc --------------------------------------------------------------------------------------------- */
 /* Philox uniforms exactly as the bake kernels draw them (for tests): u2[i] = U(seed, idx0+i, stream_id). */
 IRIS_API int iris_philox_u2(uint64_t seed, uint64_t idx0, uint32_t stream_id, int64_t n, float *u2, iris_stream_t);

@@ -38,6 +38,8 @@
 #include "iris_optim.h"
 #include "iris_prebake.h"
 #include "iris_labels.h"
+#include "iris_closest.h"
+#include "iris_texmat.h"
 
 using namespace iris;
 
@@ -1386,6 +1388,54 @@ extern "C" IRIS_API int iris_texture_dilate(const int32_t* ids, int32_t H, int32
     const int64_t texels = (int64_t)H * W;
     hipLaunchKernelGGL(texture_dilate_kernel, dim3((unsigned)((texels + kAtlasThreads - 1) / kAtlasThreads)), dim3(kAtlasThreads), 0, (hipStream_t)stream, ids, (int)H,
                        (int)W, (int)n, albedo_img, rm_img);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
+// ======================================================================================================
+// 5c-17: closest point on the mesh, the exported textures read back (iris_closest.h, iris_texmat.h)
+// ======================================================================================================
+static int closest_scene_check(const char* who, const iris_scene* s) {
+    if (!s) return fail(IRIS_ERR_ARG, std::string(who) + ": null scene");
+    if (s->dev.layout != kLayoutQ8) return fail(IRIS_ERR_ARG, std::string(who) + ": the distance query reads the quantised node table (IRIS_BVH4_Q8, the default layout)");
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_closest_point(const iris_scene* s, const float* xs, int64_t B, int64_t* tri, float* bary, float* pos, float* dist2, iris_stream_t stream) {
+    if (int rc = closest_scene_check("iris_closest_point", s)) return rc;
+    if (B < 0 || (B > 0 && !xs)) return fail(IRIS_ERR_ARG, "iris_closest_point: bad arguments");
+    if (B == 0) return IRIS_OK;
+    hipLaunchKernelGGL(closest_point_kernel, trace_grid(B), dim3(kBlock), 0, (hipStream_t)stream, s->dev, xs, B, tri, bary, pos, dist2);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+static int tex_args(const char* who, const int32_t* ft, int64_t F, const float* vt, int64_t n_vt, const uint8_t* albedo_img, const uint8_t* rm_img, int32_t H, int32_t W,
+                    int64_t B, const float* albedo, const float* rough, const float* metal, TexDev& t) {
+    if (H < 1 || W < 1 || H > kUvMaxRes || W > kUvMaxRes || F < 0 || n_vt < 0 || B < 0)
+        return fail(IRIS_ERR_ARG, std::string(who) + ": bad sizes (H " + std::to_string(H) + ", W " + std::to_string(W) + ", F " + std::to_string(F) + ", n_vt " +
+                                      std::to_string(n_vt) + ", B " + std::to_string(B) + "): H and W in [1, 8192]");
+    if (!albedo_img || !rm_img || (F > 0 && (!ft || !vt)) || (B > 0 && (!albedo || !rough || !metal)) || (uintptr_t)ft % 4 || (uintptr_t)vt % 4)
+        return fail(IRIS_ERR_ARG, std::string(who) + ": null or misaligned pointer");
+    t.ft = ft; t.vt = vt; t.albedo = albedo_img; t.rm = rm_img; t.F = F; t.n_vt = n_vt; t.H = (int)H; t.W = (int)W;
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_texture_sample(const int64_t* tri, const float* bary, int64_t B, const int32_t* ft, int64_t F, const float* vt, int64_t n_vt,
+                                            const uint8_t* albedo_img, const uint8_t* rm_img, int32_t H, int32_t W, float* albedo, float* rough, float* metal,
+                                            iris_stream_t stream) {
+    TexDev t;
+    if (int rc = tex_args("iris_texture_sample", ft, F, vt, n_vt, albedo_img, rm_img, H, W, B, albedo, rough, metal, t)) return rc;
+    if (B == 0) return IRIS_OK;
+    if (!tri || !bary || (uintptr_t)tri % 8 || (uintptr_t)bary % 4) return fail(IRIS_ERR_ARG, "iris_texture_sample: null or misaligned pointer");
+    return launch1d(texture_sample_kernel, B, 4096, stream, t, tri, bary, B, albedo, rough, metal);
+}
+extern "C" IRIS_API int iris_texture_material(const iris_scene* s, const float* xs, int64_t B, const int32_t* ft, int64_t F, const float* vt, int64_t n_vt,
+                                              const uint8_t* albedo_img, const uint8_t* rm_img, int32_t H, int32_t W, float* albedo, float* rough, float* metal,
+                                              iris_stream_t stream) {
+    if (int rc = closest_scene_check("iris_texture_material", s)) return rc;
+    TexDev t;
+    if (int rc = tex_args("iris_texture_material", ft, F, vt, n_vt, albedo_img, rm_img, H, W, B, albedo, rough, metal, t)) return rc;
+    if (B == 0) return IRIS_OK;
+    if (!xs) return fail(IRIS_ERR_ARG, "iris_texture_material: null positions");
+    hipLaunchKernelGGL(texture_material_kernel, trace_grid(B), dim3(kBlock), 0, (hipStream_t)stream, s->dev, t, xs, B, albedo, rough, metal);
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }

@@ -191,23 +191,37 @@ def build_parser():
     return parser
 
 
+def build_cli_parser():
+    """build_parser() and --textures DIR: what main() parses.  They stand apart because build_parser()'s option table is pinned entry for entry
+    (tests/test_stage_setup_cpu.py) as the table of the options this stage had before it could render from the exported textures."""
+    from .utils import stage
+    parser = build_parser()
+    stage.add_common_options(parser, "textures")
+    return parser
+
+
 def main(argv=None):
     from .model.emitter import SLFEmitter
     from .utils import cameras, stage
     from .utils.path_tracing import load_scene
-    args = build_parser().parse_args(argv)
+    args = build_cli_parser().parse_args(argv)
+    stage.refuse_textures_with_material(args)
     if args.light_type != "slf":
         raise L.IrisError("--light_type area (AreaEmitter, relighting) is not part of this stage: only slf")
     device = stage.open_device(args.device, "render")
     print("==========================\nExp: {}\nOutput: {}\nSplit: {}\n==========================".format(args.experiment_name, args.output_path, args.split))
     name, path = args.dataset
-    scene = load_scene(stage.mesh_path(name, path, args.scene), device=device)
+    mesh = stage.mesh_path(name, path, args.scene)
+    scene = load_scene(mesh, device=device)
     img_hw, views = stage.load_views(name, path, args.scene, args.res_scale, split=args.split, cameras_json=args.cameras, extras=True)
     if args.max_views is not None:
         views = views[:args.max_views]
 
     ckpt = os.path.join(args.checkpoint_path, args.experiment_name, args.ckpt)
-    material_net = stage.load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), ckpt)        # NGPBRDF(mask['voxel_min'], mask['voxel_max']) + 'material.' (:110-119)
+    if args.textures:
+        material_net = stage.load_texture_material(args.textures, mesh, device)
+    else:
+        material_net = stage.load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), ckpt)    # NGPBRDF(mask['voxel_min'], mask['voxel_max']) + 'material.' (:110-119)
     if isinstance(material_net, torch.nn.Module):
         material_net.to(device)
     emitter_net = SLFEmitter(os.path.join(args.emitter_path, "emitter.pth"), os.path.join(args.emitter_path, "vslf_0.npz")).to(device)      # :123-124

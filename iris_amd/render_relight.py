@@ -137,11 +137,12 @@ def build_parser():
 
 
 def build_video_parser():
-    """build_parser() and the two options of the video stage, --video and --video_quality: what main() parses.  They stand apart because build_parser()'s
-    option table is pinned entry for entry (tests/test_stage_setup_cpu.py) as the table of the options this stage had before it could write a video."""
+    """build_parser(), the two options of the video stage, --video and --video_quality, and --textures DIR: what main() parses.  They stand apart because
+    build_parser()'s option table is pinned entry for entry (tests/test_stage_setup_cpu.py) as the table of the options this stage had before it could write a
+    video or render from the exported textures."""
     from .utils import stage
     parser = build_parser()
-    stage.add_common_options(parser, "video", "video_quality", video=stage.COMMON_OPTIONS["video"]["help"] + " (--mode traj: relight.avi beside relight.ffconcat)")
+    stage.add_common_options(parser, "video", "video_quality", "textures", video=stage.COMMON_OPTIONS["video"]["help"] + " (--mode traj: relight.avi beside relight.ffconcat)")
     return parser
 
 
@@ -149,20 +150,25 @@ def main(argv=None):
     from .utils import cameras, stage
     from .utils.exr import write_exr
     args = build_video_parser().parse_args(argv)
+    stage.refuse_textures_with_material(args)
     name, path = args.dataset
     traj = None
     if args.mode == "traj" and not args.cameras:
         traj = stage.load_trajectory(name, path, args.scene, args.res_scale, split=args.split)          # (before the device: a missing trajectory ends here)
     device = stage.open_device(args.device, "render_relight")
     print("==========================\nExp: {}\nMode: {}\nOutput: {}\nSplit: {}\n==========================".format(args.experiment_name, args.mode, args.output_path, args.split))
-    verts, faces = load_mesh(stage.mesh_path(name, path, args.scene))
+    mesh = stage.mesh_path(name, path, args.scene)
+    verts, faces = load_mesh(mesh)
     emitter_state = torch.load(os.path.join(args.emitter_path, "emitter.pth"), map_location="cpu")
     lights = LT.load_light_config(args.light_cfg)
     img_hw, views = traj or stage.load_views(name, path, args.scene, args.res_scale, split=args.split, cameras_json=args.cameras, extras=True)
     if args.max_views is not None:
         views = views[:args.max_views]
     ckpt = os.path.join(args.checkpoint_path, args.experiment_name, args.ckpt)
-    material_net = stage.load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), ckpt)
+    if args.textures:                           # the material's own Scene of the ROOM mesh: the traced scene below has the inserted lights in it
+        material_net = stage.load_texture_material(args.textures, mesh, device)
+    else:
+        material_net = stage.load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), ckpt)
     if isinstance(material_net, torch.nn.Module):
         material_net.to(device)
     model_crf = stage.load_crf(stage.read_checkpoint(ckpt)["model_crf"], args.crf_basis, args.emor_path, device)

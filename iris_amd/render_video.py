@@ -210,7 +210,7 @@ def build_parser():
     stage.add_common_options(parser, "material", "emor_path", "denoise", "seed", "max_views", max_views="render only the first N frames of the trajectory")
     parser.add_argument("--png_encoder", type=str, default="device", choices=["device", "host"], help="where the eight PNG files of a frame are encoded: on the GPU "
                         "(default; larger files, matches at distance 1 only) or with zlib on host threads; both decode to the same pixels")
-    stage.add_common_options(parser, "video", "video_quality")
+    stage.add_common_options(parser, "video", "video_quality", "textures")
     return parser
 
 
@@ -219,6 +219,7 @@ def main(argv=None):
     from .utils import cameras, stage
     from .utils.path_tracing import load_scene
     args = build_parser().parse_args(argv)
+    stage.refuse_textures_with_material(args)
     if args.light_type != "slf":
         raise L.IrisError("--light_type area (AreaEmitter, relighting) is not part of this stage: only slf")
     name, path = args.dataset
@@ -227,9 +228,13 @@ def main(argv=None):
         views = views[:args.max_views]
     device = stage.open_device(args.device, "render_video")
     print("==========================\nExp: {}\nOutput: {}\nFrames: {}\n==========================".format(args.experiment_name, args.output_path, len(views)))
-    scene = load_scene(stage.mesh_path(name, path, args.scene), device=device)
+    mesh = stage.mesh_path(name, path, args.scene)
+    scene = load_scene(mesh, device=device)
     ckpt = os.path.join(args.checkpoint_path, args.experiment_name, args.ckpt)
-    material_net = stage.load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), ckpt)
+    if args.textures:
+        material_net = stage.load_texture_material(args.textures, mesh, device)
+    else:
+        material_net = stage.load_material(args.material, os.path.join(args.emitter_path, "vslf.npz"), ckpt)
     if isinstance(material_net, torch.nn.Module):
         material_net.to(device)
     emitter_net = SLFEmitter(os.path.join(args.emitter_path, "emitter.pth"), os.path.join(args.emitter_path, "vslf_0.npz")).to(device)

@@ -8,14 +8,18 @@ with ft.npy / vt.npy, the atlas they were baked in.  The voxel bounds come from 
 its own: DESIGN.md section 5c-7), the network runs on every texel, the outputs are quantised on the device; the PNGs are written with zlib alone.
 
 Additions: --material pkg.module:factory (as the other command lines); --atlas auto|files|grid|area; --dilate N; --write_obj (mesh.obj + mesh.mtl next to the
-images).
+images); --verify N.
     --atlas files  reads <dir_save>/ft.npy and vt.npy, exactly the reference's cache: an atlas unwrapped with xatlas elsewhere drops in that way.
     --atlas grid   builds texture.grid_atlas (two faces per grid cell, shape and area ignored: valid, not good) and saves the two files.
     --atlas area   builds texture.area_atlas on the device from the loaded mesh (one chart per face in a power-of-two cell sized by the face's area, placed in
                    Morton order; exact), saves the two files and prints its report.  --tex_res must be a power of two in [4, 8192].
     --atlas auto   (default) uses the files when both exist and FAILS otherwise: a poor atlas is never produced silently.
     --dilate N     (default 0, at most 4) seam dilation after the bake: every uncovered texel within N texels of a covered one takes the nearest covered
-                   texel's bytes, so that a bilinear lookup at a chart's border does not read black.  The reference has none.
+                   texel's bytes, so that a bilinear lookup at a chart's border (model.texture.BakedTextureBRDF, --textures of the render stages) does not
+                   read black.  The reference has none.
+    --verify N     (default 0: off) after the files are written, the network and the textures read back (BakedTextureBRDF on the arrays still on the device)
+                   are evaluated at N surface points -- face i F // N, barycentrics from a CPU generator seeded with 0 -- and one line prints the PSNR of albedo,
+                   roughness and metallic: whether --tex_res and --dilate were enough.
 
 Not built: calling xatlas itself (not a dependency, no ROCm relevance: run it anywhere and drop the .npy files in); charts of several faces and charts that keep
 a face's shape (every chart of the two built-in atlases is a right isosceles triangle); a non-square texture for --atlas area; reading vt from an OBJ.
@@ -30,10 +34,11 @@ from .. import _lib as L
 from . import stage, texture as T
 
 
-def build_parser(area_atlas=False):
+def build_parser(area_atlas=False, verify=False):
     """The stage's parser.  build_parser() is the stage as it was first built -- the reference's arguments, --material, --atlas auto|files|grid, --write_obj:
-    the option table that tests/test_stage_setup_cpu.py pins, option for option.  build_parser(area_atlas=True) is the command line that main() runs: the same
-    options plus what the built-in area atlas brought, the choice --atlas area and the option --dilate (tests/test_atlas_cpu.py pins that table whole)."""
+    the option table that tests/test_stage_setup_cpu.py pins, option for option.  build_parser(area_atlas=True) is that plus what the built-in area atlas
+    brought, the choice --atlas area and the option --dilate (tests/test_atlas_cpu.py pins that table whole).  build_parser(area_atlas=True, verify=True) is
+    the command line that main() runs: one more option, --verify N."""
     import argparse
     parser = argparse.ArgumentParser(description="python -m iris_amd.utils.export: the reference's utils/export.py on MI355X")
     parser.add_argument("--mesh")
@@ -51,7 +56,46 @@ def build_parser(area_atlas=False):
     if area_atlas:
         parser.add_argument("--dilate", type=int, default=0, help="seam dilation: fill uncovered texels within N texels (0 to 4) of a covered one from the nearest")
     parser.add_argument("--write_obj", action="store_true", help="also write mesh.obj and mesh.mtl (map_Kd albedo.png)")
+    if verify:
+        parser.add_argument("--verify", type=int, default=0, metavar="N", help="after the files are written: the PSNR of the textures, read back through "
+                            "model.texture.BakedTextureBRDF, against the network at N surface points (0, the default: off)")
     return parser
+
+
+def verify_points(v, f, n):
+    """The N surface points of --verify, on the host and reproducible -> (face (N,) int64, bary (N, 2) float32, position (N, 3) float32): point i lies on face
+    i * F // N, at the barycentrics (b1, b2) = row i of torch.rand(N, 2) from a CPU generator seeded with 0, folded into the triangle (a row with b1 + b2 > 1
+    becomes (1 - b1, 1 - b2)); position = ((1 - b1 - b2) p0 + b1 p1) + b2 p2 in float32."""
+    v, f = np.asarray(v, np.float32).reshape(-1, 3), np.asarray(f).reshape(-1, 3)
+    n, F = int(n), f.shape[0]
+    if n < 1 or F < 1:
+        raise L.IrisError(f"verify_points: {n} points on {F} faces")
+    face = (np.arange(n, dtype=np.int64) * F) // n
+    u = torch.rand(n, 2, generator=torch.Generator().manual_seed(0)).numpy()
+    u = np.where((u[:, :1] + u[:, 1:]) > 1.0, np.float32(1.0) - u, u).astype(np.float32)
+    b1, b2 = u[:, :1], u[:, 1:]
+    p0, p1, p2 = (v[f[face, k]] for k in range(3))
+    pos = ((np.float32(1.0) - b1 - b2) * p0 + b1 * p1) + b2 * p2
+    return face, u, pos.astype(np.float32)
+
+
+def _psnr(a, b):
+    mse = float(((a.double() - b.double()) ** 2).mean())
+    return float("inf") if mse == 0.0 else -10.0 * float(np.log10(mse))
+
+
+@torch.no_grad()
+def verify_textures(material_net, v, f, vt, ft, albedo, rm, n, device):
+    """--verify N: the network and a BakedTextureBRDF built from the arrays that are still on the device, at verify_points(v, f, N) -> {'albedo', 'roughness',
+    'metallic'}: PSNR in dB at a data range of 1 (inf when equal).  What the 8-bit quantisation, the texture resolution, the atlas and the seams cost: the
+    number that says whether --tex_res and --dilate were enough."""
+    from ..model.texture import BakedTextureBRDF
+    from .path_tracing import Scene
+    _, _, pos = verify_points(v, f, n)
+    pos = torch.from_numpy(pos).to(device)
+    baked = BakedTextureBRDF(Scene(v, f, device=device), ft, vt, albedo, rm)
+    want, got = material_net(pos), baked(pos)
+    return {k: _psnr(want[k].detach().reshape(got[k].shape), got[k]) for k in ("albedo", "roughness", "metallic")}
 
 
 def build_area_atlas(dir_save, v, f, tex_res, device=None):
@@ -92,7 +136,9 @@ def load_atlas(mode, dir_save, n_faces, tex_res, v=None, f=None, device=None):
 
 def main(argv=None):
     from .path_tracing import load_mesh
-    args = build_parser(area_atlas=True).parse_args(argv)
+    args = build_parser(area_atlas=True, verify=True).parse_args(argv)
+    if args.verify < 0:
+        raise L.IrisError(f"export: --verify {args.verify}: a number of points, 0 for none")
     for name in ("mesh", "emitter_path", "dir_save"):
         if not getattr(args, name):
             raise L.IrisError(f"export: --{name} is required")
@@ -119,6 +165,10 @@ def main(argv=None):
     if args.write_obj:
         T.write_textured_obj(args.dir_save, v_np, f_np, vt_np, ft_np)
     print(f"[INFO] saved albedo to {path_albedo}, saved roughness and metallic to {path_rm}")
+    if args.verify:
+        q = verify_textures(material_net, v_np, f_np, vt, ft, albedo, rm, args.verify, device)
+        print(f"[INFO] verify: textures against the network at {args.verify} surface points: PSNR albedo {q['albedo']:.2f} dB, roughness {q['roughness']:.2f} dB, "
+              f"metallic {q['metallic']:.2f} dB")
 
 
 if __name__ == "__main__":

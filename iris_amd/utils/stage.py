@@ -233,6 +233,21 @@ def load_material(spec, slf_path, ckpt):
         return factory()
 
 
+def refuse_textures_with_material(args):
+    """--textures and --material both name the material: IrisError, before the device is touched"""
+    if getattr(args, "textures", None) and getattr(args, "material", None):
+        raise L.IrisError("--textures and --material both name the material: pass one of them")
+
+
+def load_texture_material(dir, mesh_path, device):
+    """--textures DIR: BakedTextureBRDF.from_export(DIR, <the mesh at mesh_path>) on `device`.  The material builds its own Scene of that mesh (the stage's traced
+    scene may hold more: render_relight's has the inserted lights in it).  What from_export refuses, it refuses before the device is touched."""
+    from ..model.texture import BakedTextureBRDF
+    from .path_tracing import load_mesh
+    v, f = load_mesh(mesh_path)
+    return BakedTextureBRDF.from_export(dir, v, f, device)
+
+
 def view_seed_torch(seed, i):
     """seeds torch's CPU and GPU generators for view i of a run seeded with `seed`: the integrators draw with torch.rand.  (The bake's Philox key is
     bake_shading.view_seed, a different thing.)"""
@@ -246,6 +261,9 @@ COMMON_OPTIONS = {
     "material": dict(type=str, default=None, help="pkg.module:factory returning material_net(position) -> {'albedo','roughness','metallic'} "
                      "(default: the reference's NGPBRDF, loaded from the checkpoint's 'material.' entries)"),
     "cameras": dict(type=str, default=None, help="generic camera JSON instead of the dataset's own camera files"),
+    "textures": dict(type=str, default=None, metavar="DIR", help="the folder utils.export wrote (albedo.png, rm.png, ft.npy, vt.npy, made for this stage's mesh): the material "
+                     "is those textures, looked up at the closest triangle (model.texture.BakedTextureBRDF), instead of the network; the checkpoint is still read for "
+                     "the response model; not together with --material"),
     "emor_path": dict(type=str, default=None, help="the EMoR basis file (default: crf/emor.txt under the working directory, as the reference)"),
     "denoise": dict(type=str, default="atrous", choices=["atrous", "none"]),
     "compression": dict(type=str, default="zip", choices=["none", "zips", "zip"]),
