@@ -524,6 +524,29 @@ IRIS_API uint64_t iris_image_metrics_workspace_bytes(int32_t N, int32_t H, int32
 IRIS_API int iris_image_metrics(const float *a, const float *b, int32_t N, int32_t H, int32_t W, int32_t C, float data_range, double *sums,
                        float *ssim_map, void *workspace, uint64_t workspace_bytes, iris_stream_t);
 
+/* ---- material metrics: the sums behind the reference's material table (utils/metric_brdf.py:32-92) ------------- */
+/* N views of H x W pixels, every map contiguous (device).  Ground truth as the EXR files hold it, float32: emit_gt, albedo_gt, kd_gt (N, H, W, 3),
+ * rough_gt (N, H, W).  Estimates: emit (N, H, W, 3) float32; albedo, kd (N, H, W, 3) and rough (N, H, W), each either uint8 code values (its *_is_u8
+ * flag set: a PNG as read) or float32, quantised as the render stage's PNG writer does, q(x) = trunc(min(max(x, 0), 1) * 255.f), NaN -> 0.  The per-pixel
+ * contract, in code values and exact, is stated in iris_amd/csrc/iris_matmetrics.h.  sums (N, 8) 8-byte words per view: [0] S_albedo, [1] S_kd, [2] S_rough
+ * (sums of squared code differences), [3] n_gt, [4] n_est, [5] n_and, [6] n_or (pixel counts of the two emitter masks, their intersection and union), all
+ * uint64; [7] S_emit, a double: the sum over the 3 H W values of (log((double)emit + 1) - log((double)emit_gt + 1))^2, non-finite when a term is.
+ * Partial sums go through workspace (iris_material_metrics_workspace_bytes() bytes, 8-byte aligned; 0: the size is not supported -- N, H, W >= 1,
+ * H W <= 2^30, N ceil(H W / 512) < 2^31) with plain stores and are added in a fixed order: no atomics, the same bits on every call for a given shape.
+ * Two launches on the stream, whatever N. */
+typedef struct iris_material_metrics_args {
+    const float *emit_gt, *albedo_gt, *kd_gt, *rough_gt;
+    const float *emit;
+    const void *albedo, *kd, *rough;
+    uint64_t *sums;
+    void *workspace;
+    uint64_t workspace_bytes;
+    int32_t albedo_is_u8, kd_is_u8, rough_is_u8;
+    int32_t N, H, W;
+} iris_material_metrics_args;
+IRIS_API uint64_t iris_material_metrics_workspace_bytes(int32_t N, int32_t H, int32_t W);
+IRIS_API int iris_material_metrics(const iris_material_metrics_args *, iris_stream_t);
+
 /* ---- texture export: UV rasteriser, per-texel resolve, quantisation (utils/export.py:77-135) ------------------- */
 /* The reference rasterises the UV triangles with nvdiffrast (third party, GL): parity is unpinned and the contract is this project's, exact in integers
  * (iris_amd/csrc/iris_texture.h).  Texture of H rows x W columns, both in [1, 8192]; texel (r, c) has its centre at

@@ -41,6 +41,12 @@ class LabelViewArgs(C.Structure):
     _fields_ = [("rays", ViewRays), ("n_tri", _I64), ("ids", _P), ("ids_is_u8", C.c_int32), ("hist", _P), ("n_labels", C.c_int32), ("table", _P), ("out", _P),
                 ("out_is_u8", C.c_int32), ("miss_value", C.c_int32)]
 
+class MaterialMetricsArgs(C.Structure):
+    """iris_material_metrics_args (include/iris_hip.h)"""
+    _fields_ = [("emit_gt", _P), ("albedo_gt", _P), ("kd_gt", _P), ("rough_gt", _P), ("emit", _P), ("albedo", _P), ("kd", _P), ("rough", _P), ("sums", _P),
+                ("workspace", _P), ("workspace_bytes", _U64), ("albedo_is_u8", C.c_int32), ("kd_is_u8", C.c_int32), ("rough_is_u8", C.c_int32),
+                ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
 # name -> argtypes (restype is int unless listed in _RESTYPE)
 PROTOTYPES = {
     "iris_scene_create": [_P, _I64, _P, _I64, _I32, C.POINTER(_P)],
@@ -142,6 +148,8 @@ PROTOTYPES = {
     "iris_denoise": [_P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _F, _F, _F, _P, _U64, _P],
     "iris_image_metrics_workspace_bytes": [_I32, _I32, _I32, _I32],
     "iris_image_metrics": [_P, _P, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _U64, _P],
+    "iris_material_metrics_workspace_bytes": [_I32, _I32, _I32],
+    "iris_material_metrics": [_P, _P],
     "iris_uv_raster_workspace_bytes": [_I64],
     "iris_uv_raster": [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _U64, _P],
     "iris_debug_uv_raster": [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _U64, _I32, _P],
@@ -179,7 +187,7 @@ _RESTYPE = {"iris_scene_destroy": None, "iris_slf_destroy": None, "iris_emitter_
             "iris_loss_photometric_workspace_bytes": C.c_uint64,
             "iris_png_row_bytes": C.c_int64, "iris_png_stream_bound": C.c_uint64, "iris_png_workspace_bytes": C.c_uint64, "iris_png_magma_table": None,
             "iris_jpeg_stream_bound": C.c_uint64, "iris_jpeg_workspace_bytes": C.c_uint64, "iris_jpeg_tables": None,
-            "iris_image_metrics_workspace_bytes": C.c_uint64, "iris_uv_raster_workspace_bytes": C.c_uint64, "iris_atlas_density": C.c_double}
+            "iris_image_metrics_workspace_bytes": C.c_uint64, "iris_material_metrics_workspace_bytes": C.c_uint64, "iris_uv_raster_workspace_bytes": C.c_uint64, "iris_atlas_density": C.c_double}
 
 _lib = None
 

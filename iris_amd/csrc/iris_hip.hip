@@ -23,6 +23,7 @@
 #include "iris_cache.h"
 #include "iris_denoise.h"
 #include "iris_metrics.h"
+#include "iris_matmetrics.h"
 #include "iris_texture.h"
 #include "iris_atlas.h"
 #include "iris_ngp.h"
@@ -1225,6 +1226,42 @@ extern "C" IRIS_API int iris_image_metrics(const float* a, const float* b, int32
         hipLaunchKernelGGL(metrics_tile_kernel<3>, dim3(N * tiles), dim3(kMetThreads), 0, st, g);
         hipLaunchKernelGGL(metrics_slab_sum_kernel<3>, dim3(N), dim3(kMetThreads), 0, st, (const double*)workspace, tiles, sums);
     }
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
+// ---- material metrics (iris_matmetrics.h; utils/metric_brdf.py:32-92)
+static bool matmetrics_shape(int N, int H, int W, int& chunks) {
+    if (N < 1 || H < 1 || W < 1 || (int64_t)H * W > kMmMaxPixels) return false;
+    chunks = (int)(((int64_t)H * W + kMmChunk - 1) / kMmChunk);
+    return (int64_t)N * chunks <= INT32_MAX;                              // the grid
+}
+extern "C" IRIS_API uint64_t iris_material_metrics_workspace_bytes(int32_t N, int32_t H, int32_t W) {
+    int chunks;
+    if (!matmetrics_shape(N, H, W, chunks)) return 0;
+    return (uint64_t)N * chunks * kMmWords * sizeof(uint64_t);
+}
+extern "C" IRIS_API int iris_material_metrics(const iris_material_metrics_args* v, iris_stream_t stream) {
+    if (!v) return fail(IRIS_ERR_ARG, "iris_material_metrics: null arguments");
+    int chunks;
+    if (!matmetrics_shape(v->N, v->H, v->W, chunks))
+        return fail(IRIS_ERR_ARG, "iris_material_metrics: unsupported size (N, H, W) = (" + std::to_string(v->N) + ", " + std::to_string(v->H) + ", " +
+                                      std::to_string(v->W) + "): N, H, W >= 1, H W <= 2^30, N ceil(H W / 512) < 2^31");
+    const void* f32[] = {v->emit_gt, v->albedo_gt, v->kd_gt, v->rough_gt, v->emit, v->albedo_is_u8 ? nullptr : v->albedo, v->kd_is_u8 ? nullptr : v->kd,
+                         v->rough_is_u8 ? nullptr : v->rough};
+    if (!v->emit_gt || !v->albedo_gt || !v->kd_gt || !v->rough_gt || !v->emit || !v->albedo || !v->kd || !v->rough || !v->sums || (uintptr_t)v->sums % 8)
+        return fail(IRIS_ERR_ARG, "iris_material_metrics: a null map, or null / misaligned sums");
+    for (const void* p : f32)
+        if ((uintptr_t)p % 4) return fail(IRIS_ERR_ARG, "iris_material_metrics: a float32 map is not 4-byte aligned");
+    const uint64_t need = iris_material_metrics_workspace_bytes(v->N, v->H, v->W);
+    if (!v->workspace || v->workspace_bytes < need || (uintptr_t)v->workspace % 8)
+        return fail(IRIS_ERR_ARG, "iris_material_metrics: an 8-byte aligned workspace of " + std::to_string(need) + " bytes is required (got " +
+                                      std::to_string(v->workspace_bytes) + ")");
+    MmArgs g{v->emit_gt, v->albedo_gt, v->kd_gt, v->rough_gt, v->emit, v->albedo, v->kd, v->rough, v->albedo_is_u8 != 0, v->kd_is_u8 != 0, v->rough_is_u8 != 0,
+             v->H * v->W, chunks, (uint64_t*)v->workspace};
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(matmetrics_chunk_kernel, dim3(v->N * chunks), dim3(kMmThreads), 0, st, g);
+    hipLaunchKernelGGL(matmetrics_slab_sum_kernel, dim3(v->N), dim3(kMmThreads), 0, st, (const uint64_t*)v->workspace, chunks, v->sums);
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }

@@ -4,7 +4,8 @@ denoiser, the camera response model, the maps on disk and PSNR -- with --metrics
 
 Every ingredient is a HIP stage of this package: `utils.path_tracing.path_tracing`, `utils.render.render_intrinsics` (iris_render_primary + the material network +
 iris_render_intrinsics), `utils.denoise.Denoiser` (the a-trous filter that stands where OptixDenoiser stands), `model.crf.EmorCRF`, `utils.exr.write_exr`, `utils.metrics.image_metrics` (SSIM on the
-device: skimage's defaults restated).
+device: skimage's defaults restated).  With --material_metrics GT_DIR every view's material maps are also scored against a synthetic scene's
+ground truth as it is rendered (utils.material_metrics: the reference's utils/metric_brdf.py table).
 
 Not here: --light_type area (AreaEmitter), the magma colour maps (*_color.png), merge.png, crfs.png,
 render_video.py / render_relight.py, and the trainers' validation(), which masks differently.
@@ -192,12 +193,27 @@ def build_parser():
 
 
 def build_cli_parser():
-    """build_parser() and --textures DIR: what main() parses.  They stand apart because build_parser()'s option table is pinned entry for entry
-    (tests/test_stage_setup_cpu.py) as the table of the options this stage had before it could render from the exported textures."""
+    """build_parser(), --textures DIR and --material_metrics GT_DIR: what main() parses.  They stand apart because build_parser()'s option table is pinned
+    entry for entry (tests/test_stage_setup_cpu.py) as the table of the options this stage had before it could render from the exported textures."""
     from .utils import stage
     parser = build_parser()
     stage.add_common_options(parser, "textures")
+    parser.add_argument("--material_metrics", type=str, default=None, metavar="GT_DIR", help="the split folder of a synthetic scene (Emit/, albedo/, DiffCol/, Roughness/): "
+                        "every view's emission, a_prime, kd and roughness maps are scored against its ground truth on the device (utils/material_metrics.py), the "
+                        "reference's utils/metric_brdf.py table is printed and written to <output_path>/<split>/material_metrics.json -- the numbers "
+                        "python -m iris_amd.utils.metric_brdf computes from the files this run writes")
     return parser
+
+
+def material_metrics_view(gt_dir, i, out, img_hw):
+    """utils.material_metrics.material_metrics of render_view's maps `out` (the float32 maps, quantised in the kernel as save_png quantises them: no PNG is
+    decoded) against view i of the ground-truth folder.  Nothing synchronises with the host."""
+    from .utils import material_metrics as M
+    gt = M.load_gt_view(gt_dir, i)
+    if gt["emit"].shape[:2] != tuple(img_hw):
+        raise L.IrisError(f"{gt_dir}: the ground-truth maps of view {i} are {gt['emit'].shape[0]} x {gt['emit'].shape[1]}, the view {img_hw[0]} x {img_hw[1]}")
+    est = {"emit": out["emission"], "albedo": out["a_prime"], "kd": out["kd"], "rough": out["roughness"]}
+    return M.material_metrics(M.upload([gt], out["emission"].device), {k: v.to(torch.float32) for k, v in est.items()})
 
 
 def main(argv=None):
@@ -208,6 +224,8 @@ def main(argv=None):
     stage.refuse_textures_with_material(args)
     if args.light_type != "slf":
         raise L.IrisError("--light_type area (AreaEmitter, relighting) is not part of this stage: only slf")
+    if args.material_metrics and not os.path.isdir(args.material_metrics):
+        raise L.IrisError(f"--material_metrics {args.material_metrics}: no such folder")
     device = stage.open_device(args.device, "render")
     print("==========================\nExp: {}\nOutput: {}\nSplit: {}\n==========================".format(args.experiment_name, args.output_path, args.split))
     name, path = args.dataset
@@ -230,6 +248,10 @@ def main(argv=None):
     denoiser = stage.make_denoiser(args.denoise, img_hw, device)
     metrics = tuple(args.metrics.split(","))
     psnr_list, ssim_list = [], []
+    table = None
+    if args.material_metrics:
+        from .utils import material_metrics as M
+        table = M.Table(img_hw)
     t0 = time.time()
     for i, view in enumerate(views):
         stage.view_seed_torch(args.seed, i)
@@ -238,6 +260,8 @@ def main(argv=None):
         out = render_view(scene, emitter_net, material_net, model_crf, rays, img_hw, args.SPP, args.spp, args.indir_depth, exposure=float(view.get("exposure", 1.0)),
                           gt=gt, denoise=denoiser is not None, denoiser=denoiser, metrics=metrics)
         write_view(args.output_path, args.split, i, out, args.compression)
+        if table is not None:
+            table.add(material_metrics_view(args.material_metrics, i, out, img_hw))
         if out["psnr"] is not None:
             psnr_list.append((i, out["psnr"]))
         if out["ssim"] is not None:
@@ -246,6 +270,11 @@ def main(argv=None):
         print("Mean PSNR: {:.5f}".format(float(np.mean([p for _, p in psnr_list]))))
     if ssim_list:
         print("Mean SSIM: {:.5f}".format(float(np.mean([s for _, s in ssim_list]))))
+    if table is not None and views:
+        from .utils.metric_brdf import write_json
+        summary, doc = table.finish()
+        print(M.format_summary(summary))
+        write_json(os.path.join(args.output_path, args.split, "material_metrics.json"), dict(doc, gt=args.material_metrics))
     os.makedirs(os.path.join(args.output_path, args.split, "rgb"), exist_ok=True)
     write_metrics(os.path.join(args.output_path, args.split, "rgb", "metrics.txt"), psnr_list, ssim_list if "ssim" in metrics else None)
     torch.cuda.synchronize()

@@ -1,10 +1,10 @@
-"""What the thirteen command-line stages (fuse_segmentation, slf_bake, extract_emitter_ldr, initialize, slf_refine, bake_shading, refine_shading, render, render_video,
-render_relight, train_brdf_crf, train_emitter, utils.export) do before their first kernel launches: find the mesh, list the views and their photographs -- or the frames of the
+"""What the fifteen command-line stages (fuse_segmentation, slf_bake, extract_emitter_ldr, initialize, slf_refine, bake_shading, refine_shading, render, render_video,
+render_relight, train_brdf_crf, train_emitter, utils.export, utils.metric_brdf, utils.metric_crf) do before their first kernel launches: find the mesh, list the views and their photographs -- or the frames of the
 render trajectory (load_trajectory: render_video, render_relight --mode traj) --, read checkpoints and the material network, build their parsers' shared
 options, open the device; for the two stages whose frames become a video, the ffconcat list that stands where the reference's mp4 stands (write_ffconcat);
 for the three training stages (initialize, train_brdf_crf, train_emitter; their loop is utils/trainer.py) what their main() refuses before the device
-(refuse_unbuilt_training) and the pixel set it trains on (open_training_set); and for the seven stages that end in a `cli` (fuse_segmentation, the three
-pre-bake commands and the three trainers) the exit wrapper (exit_status).
+(refuse_unbuilt_training) and the pixel set it trains on (open_training_set); and for the nine stages that end in a `cli` (fuse_segmentation, the three
+pre-bake commands, the three trainers and the two metric commands) the exit wrapper (exit_status).
 Plain functions; a stage's main() stays a linear script that calls them.  Everything down to exit_status is host code and imports without a GPU; the
 last seven functions need one.
 """
