@@ -547,6 +547,45 @@ typedef struct iris_material_metrics_args {
 IRIS_API uint64_t iris_material_metrics_workspace_bytes(int32_t N, int32_t H, int32_t W);
 IRIS_API int iris_material_metrics(const iris_material_metrics_args *, iris_stream_t);
 
+/* ---- the trainers' validation (train_brdf_crf.py:331-499; the same lines in train_emitter.py and initialize.py) -- */
+/* validation_step (:456-499) after the material network: N views of H x W pixels, every map contiguous (device).  albedo (N, H W, 3), metallic (N, H W)
+ * float32: the network's outputs at the pixel-centre primary hits, for all pixels; valid (N, H W) u8.  Per pixel and channel, each operation one correctly
+ * rounded float32 operation (no contraction):  est = valid ? albedo_c * (1.0f - metallic) : 0;  d = gt_c * m - est * m;  q = d * d.
+ *   gt_is_u8 == 0 (synthetic): gt (N, H W, 3) float32 (DiffCol), emit (N, H W, 3) float32, lut NULL;  m = ((e0 + e1) + e2 == 0) ? 1 : 0  (:461)
+ *   gt_is_u8 != 0 (ldr): gt (N, H W, 3) the photograph's 8-bit codes, read through lut, 256 float32 of the caller's (rgb^(1/2.2) clamped to [0,1], :486),
+ *                        emit NULL;  m = 1  (:463)
+ * sums (N) doubles, 8-byte aligned: S_n = sum over the view's pixels and channels of (double)q, in a fixed order -- per thread pixels ascending and channels
+ * 0, 1, 2; blocks of 512 pixels added by a fixed tree; the blocks' partials, stored into workspace (iris_val_kd_loss_workspace_bytes() bytes, 8-byte aligned;
+ * 0: the size is not supported -- N, H, W >= 1, H W <= 2^30, N ceil(H W / 512) < 2^31) with plain stores, added in index order by a second launch.  No
+ * atomics: the same bits on every call, and for a view alone or at any row of a stack.  val/loss = S / (3 H W).  Two launches on the stream, whatever N. */
+typedef struct iris_val_kd_loss_args {
+    const float *albedo, *metallic;
+    const uint8_t *valid;
+    const void *gt;
+    const float *emit;
+    const float *lut;
+    double *sums;
+    void *workspace;
+    uint64_t workspace_bytes;
+    int32_t gt_is_u8;
+    int32_t N, H, W;
+} iris_val_kd_loss_args;
+IRIS_API uint64_t iris_val_kd_loss_workspace_bytes(int32_t N, int32_t H, int32_t W);
+IRIS_API int iris_val_kd_loss(const iris_val_kd_loss_args *, iris_stream_t);
+/* validation()'s material maps (:372-396) after the material network, ONE launch over iris_render_primary's outputs (the same un-centred jitter).  Per sample
+ * i = b*spp + s (N = B*spp rows, pixel-major): e0, valid_next as iris_render_primary gives them; albedo (N,3), roughness (N), metallic (N) = material_net(pos);
+ * radiance: the emitter's (n_rad,3) tensor itself (rows beyond the emitter handle's count are never read).
+ *   emission_ = e0 >= 0 ? radiance[e0] : 0;  keep = (valid_next | e0 >= 0) & ((emission_.r + emission_.g) + emission_.b == 0);
+ *   albedo_ = keep ? albedo : 0; roughness_ = keep ? roughness : 0; metallic_ = keep ? metallic : 0; emission_ is not masked.
+ * A masked sample counts as 0 (iris_render_intrinsics: as the default material), and it is SELECTED, where the reference multiplies by 0 (:393-395): the two
+ * differ only where the network returns a non-finite value at a masked sample.
+ * SUMMATION ORDER (a contract):  map[b] += (x_0 + x_1 + ... + x_{spp-1}) * (1.0f / spp), samples added in increasing s, in float32, as iris_render_intrinsics.
+ * The four maps are the caller's: albedo_map (B,3), roughness_map (B), metallic_map (B), emission (B,3).  No atomics, every element written by one thread:
+ * bitwise reproducible.  spp: any positive int. */
+IRIS_API int iris_val_intrinsics(const iris_emitter *, const float *radiance, const int32_t *e0, const uint8_t *valid_next, const float *albedo,
+                        const float *roughness, const float *metallic, int64_t B, int spp, float *albedo_map, float *roughness_map, float *metallic_map,
+                        float *emission, iris_stream_t);
+
 /* ---- texture export: UV rasteriser, per-texel resolve, quantisation (utils/export.py:77-135) ------------------- */
 /* The reference rasterises the UV triangles with nvdiffrast (third party, GL): parity is unpinned and the contract is this project's, exact in integers
  * (iris_amd/csrc/iris_texture.h).  Texture of H rows x W columns, both in [1, 8192]; texel (r, c) has its centre at

@@ -47,6 +47,12 @@ class MaterialMetricsArgs(C.Structure):
                 ("workspace", _P), ("workspace_bytes", _U64), ("albedo_is_u8", C.c_int32), ("kd_is_u8", C.c_int32), ("rough_is_u8", C.c_int32),
                 ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
 
+
+class ValKdLossArgs(C.Structure):
+    """iris_val_kd_loss_args (include/iris_hip.h); a field left alone is NULL / 0"""
+    _fields_ = [("albedo", _P), ("metallic", _P), ("valid", _P), ("gt", _P), ("emit", _P), ("lut", _P), ("sums", _P), ("workspace", _P),
+                ("workspace_bytes", _U64), ("gt_is_u8", C.c_int32), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
 # name -> argtypes (restype is int unless listed in _RESTYPE)
 PROTOTYPES = {
     "iris_scene_create": [_P, _I64, _P, _I64, _I32, C.POINTER(_P)],
@@ -150,6 +156,9 @@ PROTOTYPES = {
     "iris_image_metrics": [_P, _P, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _U64, _P],
     "iris_material_metrics_workspace_bytes": [_I32, _I32, _I32],
     "iris_material_metrics": [_P, _P],
+    "iris_val_kd_loss_workspace_bytes": [_I32, _I32, _I32],
+    "iris_val_kd_loss": [_P, _P],
+    "iris_val_intrinsics": [_P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P],
     "iris_uv_raster_workspace_bytes": [_I64],
     "iris_uv_raster": [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _U64, _P],
     "iris_debug_uv_raster": [_P, _I64, _P, _I64, _I32, _I32, _P, _P, _U64, _I32, _P],
@@ -187,7 +196,7 @@ _RESTYPE = {"iris_scene_destroy": None, "iris_slf_destroy": None, "iris_emitter_
             "iris_loss_photometric_workspace_bytes": C.c_uint64,
             "iris_png_row_bytes": C.c_int64, "iris_png_stream_bound": C.c_uint64, "iris_png_workspace_bytes": C.c_uint64, "iris_png_magma_table": None,
             "iris_jpeg_stream_bound": C.c_uint64, "iris_jpeg_workspace_bytes": C.c_uint64, "iris_jpeg_tables": None,
-            "iris_image_metrics_workspace_bytes": C.c_uint64, "iris_material_metrics_workspace_bytes": C.c_uint64, "iris_uv_raster_workspace_bytes": C.c_uint64, "iris_atlas_density": C.c_double}
+            "iris_image_metrics_workspace_bytes": C.c_uint64, "iris_material_metrics_workspace_bytes": C.c_uint64, "iris_val_kd_loss_workspace_bytes": C.c_uint64, "iris_uv_raster_workspace_bytes": C.c_uint64, "iris_atlas_density": C.c_double}
 
 _lib = None
 

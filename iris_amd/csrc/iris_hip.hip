@@ -24,6 +24,7 @@
 #include "iris_denoise.h"
 #include "iris_metrics.h"
 #include "iris_matmetrics.h"
+#include "iris_validate.h"
 #include "iris_texture.h"
 #include "iris_atlas.h"
 #include "iris_ngp.h"
@@ -1266,6 +1267,37 @@ extern "C" IRIS_API int iris_material_metrics(const iris_material_metrics_args* 
     return IRIS_OK;
 }
 
+// ---- the trainers' validation (iris_validate.h; train_brdf_crf.py:331-499)
+extern "C" IRIS_API uint64_t iris_val_kd_loss_workspace_bytes(int32_t N, int32_t H, int32_t W) {
+    int chunks;
+    if (!matmetrics_shape(N, H, W, chunks)) return 0;
+    return (uint64_t)N * chunks * sizeof(double);
+}
+extern "C" IRIS_API int iris_val_kd_loss(const iris_val_kd_loss_args* v, iris_stream_t stream) {
+    if (!v) return fail(IRIS_ERR_ARG, "iris_val_kd_loss: null arguments");
+    int chunks;
+    if (!matmetrics_shape(v->N, v->H, v->W, chunks))
+        return fail(IRIS_ERR_ARG, "iris_val_kd_loss: unsupported size (N, H, W) = (" + std::to_string(v->N) + ", " + std::to_string(v->H) + ", " +
+                                      std::to_string(v->W) + "): N, H, W >= 1, H W <= 2^30, N ceil(H W / 512) < 2^31");
+    if (!v->albedo || !v->metallic || !v->valid || !v->gt || !v->sums || (uintptr_t)v->sums % 8)
+        return fail(IRIS_ERR_ARG, "iris_val_kd_loss: a null map, or null / misaligned sums");
+    if (v->gt_is_u8 ? (!v->lut || v->emit) : (!v->emit || v->lut))
+        return fail(IRIS_ERR_ARG, "iris_val_kd_loss: 8-bit ground truth takes lut and no emit, float32 ground truth emit and no lut");
+    const void* f32[] = {v->albedo, v->metallic, v->gt_is_u8 ? nullptr : v->gt, v->emit, v->lut};
+    for (const void* p : f32)
+        if ((uintptr_t)p % 4) return fail(IRIS_ERR_ARG, "iris_val_kd_loss: a float32 map is not 4-byte aligned");
+    const uint64_t need = iris_val_kd_loss_workspace_bytes(v->N, v->H, v->W);
+    if (!v->workspace || v->workspace_bytes < need || (uintptr_t)v->workspace % 8)
+        return fail(IRIS_ERR_ARG, "iris_val_kd_loss: an 8-byte aligned workspace of " + std::to_string(need) + " bytes is required (got " +
+                                      std::to_string(v->workspace_bytes) + ")");
+    ValLossArgs g{v->albedo, v->metallic, v->valid, v->gt, v->emit, v->lut, v->gt_is_u8 != 0, v->H * v->W, chunks, (double*)v->workspace};
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(val_loss_chunk_kernel, dim3(v->N * chunks), dim3(kMmThreads), 0, st, g);
+    hipLaunchKernelGGL(val_loss_slab_sum_kernel, dim3(v->N), dim3(kMmThreads), 0, st, (const double*)v->workspace, chunks, v->sums);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
 // ======================================================================================================
 // texture export: UV rasteriser, per-texel resolve, quantisation (iris_texture.h)
 // ======================================================================================================
@@ -1839,6 +1871,25 @@ extern "C" IRIS_API int iris_render_intrinsics(const iris_emitter* e, const iris
     a.lpp = lpp;
     const int64_t n_groups = (B + 64 / lpp - 1) / (64 / lpp);    // one wave per group of 64 / lpp pixels
     return launch1d(render_intrinsics_kernel, n_groups * 64, 16384, stream, a);
+}
+// validation()'s material maps after the material network (iris_validate.h; train_brdf_crf.py:372-396)
+extern "C" IRIS_API int iris_val_intrinsics(const iris_emitter* e, const float* radiance, const int32_t* e0, const uint8_t* valid_next, const float* albedo,
+                                   const float* roughness, const float* metallic, int64_t B, int spp, float* albedo_map, float* roughness_map,
+                                   float* metallic_map, float* emission, iris_stream_t stream) {
+    if (!e || B < 0 || spp < 1 ||
+        (B > 0 && (!radiance || !e0 || !valid_next || !albedo || !roughness || !metallic || !albedo_map || !roughness_map || !metallic_map || !emission)))
+        return fail(IRIS_ERR_ARG, "iris_val_intrinsics: bad arguments");
+    if (B == 0) return IRIS_OK;
+    if (B > (((int64_t)1 << 40) / spp)) return fail(IRIS_ERR_ARG, "iris_val_intrinsics: more than 2^40 samples in one call");
+    ValMapsArgs a{};
+    a.radiance = radiance; a.n_rad = e->n_rad; a.B = B; a.spp = spp;
+    a.albedo = albedo; a.rough = roughness; a.metal = metallic; a.e0 = e0; a.valid_next = valid_next;
+    a.albedo_map = albedo_map; a.roughness = roughness_map; a.metallic = metallic_map; a.emission = emission;
+    int lpp = 1;
+    while (lpp < spp && lpp < 64) lpp <<= 1;                     // lanes per pixel, as iris_render_intrinsics
+    a.lpp = lpp;
+    const int64_t n_groups = (B + 64 / lpp - 1) / (64 / lpp);    // one wave per group of 64 / lpp pixels
+    return launch1d(val_intrinsics_kernel, n_groups * 64, 16384, stream, a);
 }
 extern "C" IRIS_API int iris_pt_nee(const iris_scene* sc, const iris_emitter* e, const float* pos, const float* nrm, const float* wo, const float* albedo,
                            const float* roughness, const float* metallic, const float* s1, const float* s2, int64_t N, float* coef1, int32_t* e1,

@@ -15,8 +15,13 @@ def parser():
     return _stage.parser("initialize", "the initialisation stage")
 
 
+def cli_parser():
+    """parser() and --validate (train_emitter.cli_parser): what main() parses"""
+    return _stage.cli_parser("initialize", "the initialisation stage")
+
+
 def main(argv=None):
-    return _stage.run(parser().parse_args(argv), "initialize", "initialize")
+    return _stage.run(cli_parser().parse_args(argv), "initialize", "initialize")
 
 
 def cli(argv=None):

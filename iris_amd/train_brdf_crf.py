@@ -10,12 +10,17 @@ parameters and the refresh of the half copy the forward reads, in one pass (iris
 `<checkpoint_path>/<experiment_name>/last.ckpt` (`['state_dict']` with `material.*` and `model_crf.*` keys, as the reference's loaders read it) are
 iris_amd/utils/trainer.py's.
 
-Not built: the in-training validation images (train_brdf_crf.py:339-453; `python -m iris_amd.render --ckpt last.ckpt` shows the same thing), TensorBoard /
-W&B logging (the scalars go to metrics.jsonl under the reference's names), the `val/loss`-monitored best checkpoint, the `Ranger` optimizer,
-`--res_scale` other than 1 for the real and synthetic layouts (`--dataset scannetpp ROOT --scene S` takes any: its 8-bit files are resized on the device,
-iris_amd/utils/resize.py); `--val_step` and `--num_workers` are accepted and ignored.
+`--validate metric|images|all` (an addition; default none) turns on the reference's validation (train_brdf_crf.py:331-499,539; iris_amd/utils/validation.py):
+val/loss and val/psnr over the validation views after every epoch with `best.ckpt` beside last.ckpt, and the validation images of view --val_frame every
+--val_step steps under outputs/<experiment_name>/<dir_val>/.  The images are path-traced, so `--validate images|all` also needs --emitter_path (emitter.pth;
+the radiance cache is --voxel_path's), which this stage does not otherwise read.
+
+Not built: the validation images' crfs.png and crfs_weight.png (matplotlib), TensorBoard / W&B logging (the scalars go to metrics.jsonl under the
+reference's names), the `Ranger` optimizer, `--res_scale` other than 1 for the real and synthetic layouts (`--dataset scannetpp ROOT --scene S` takes any:
+its 8-bit files are resized on the device, iris_amd/utils/resize.py); `--num_workers` is accepted and ignored, and so is `--val_step` without --validate.
 """
 import argparse
+import os
 
 from . import _lib as L
 from .utils import stage, trainer as base
@@ -32,12 +37,13 @@ def default_hparams(**changes):
 
 class BRDFCRFTrainer(base.Trainer):
     """material: an NGPBRDF on the GPU (init_parameters() or loaded); model_crf: an EmorCRF on the same device; pixel_set: a PixelSet with its cache attached
-    that has been through restrict_to_hits(scene, store_positions=True); hparams: a dict or Namespace of options (default_hparams()).
+    that has been through restrict_to_hits(scene, store_positions=True); hparams: a dict or Namespace of options (default_hparams()); validation: the
+    utils.validation.ValidationSet of hparams['validate'] (with its own emitter when images are written), or None.
     training_step(batch, global_step) -> brdf_crf_loss's dict; everything else is utils.trainer.Trainer's."""
     prefix, logged = "train", ("loss", "loss_c", "loss_d", "loss_seg", "loss_a", "psnr")          # train_brdf_crf.py:324-329, as 'train/<name>'
 
-    def __init__(self, material, model_crf, pixel_set, hparams):
-        super().__init__(pixel_set, hparams, PROGRAM_DEFAULTS)
+    def __init__(self, material, model_crf, pixel_set, hparams, validation=None):
+        super().__init__(pixel_set, hparams, PROGRAM_DEFAULTS, validation=validation)
         hp, self.material, self.model_crf = self.hparams, material, model_crf
         if pixel_set.cache is None or pixel_set.positions is None:
             raise L.IrisError("BRDFCRFTrainer: the pixel set needs attach_cache(cache) and restrict_to_hits(scene, store_positions=True)")
@@ -69,17 +75,43 @@ def parser():
     return ap
 
 
+def cli_parser():
+    """parser() and --validate: what main() parses.  They stand apart because parser()'s option table is pinned option for option
+    (tests/test_stage_setup_cpu.py) as the table the stage had before it validated."""
+    return base.add_validate_option(parser())
+
+
 def main(argv=None):
-    args = parser().parse_args(argv)
+    args = cli_parser().parse_args(argv)
     from .model.brdf import NGPBRDF
     from .model.crf import EmorCRF
-    stage.refuse_unbuilt_training(args)               # everything that can be refused is refused before the device is touched
+    val_files = stage.refuse_unbuilt_training(args)   # everything that can be refused is refused before the device is touched
     if args.cache_dir is None:
         raise L.IrisError("--cache_dir is needed: the stage trains on the baked shadings (python -m iris_amd.bake_shading --output DIR)")
-    print("train_brdf_crf: --val_step and --num_workers are accepted and ignored (no in-training validation images, no loader workers: the batches are "
-          "made on the device)", flush=True)
+    images = args.validate in ("images", "all")
+    if images:
+        if not args.emitter_path:
+            raise L.IrisError(f"--validate {args.validate} needs --emitter_path (emitter.pth): the validation images are path-traced under the emitter, "
+                              "which this stage does not otherwise load")
+        for path in (args.emitter_path, args.voxel_path):
+            if not path or not os.path.isfile(path):
+                raise L.IrisError(f"{path}: no such file (--validate {args.validate} reads --emitter_path and --voxel_path)")
+    if args.validate == "none":
+        print("train_brdf_crf: --val_step and --num_workers are accepted and ignored (no in-training validation images, no loader workers: the batches are "
+              "made on the device)", flush=True)
+    else:
+        print(base.validation_notice("train_brdf_crf", args, val_files), flush=True)
     device = stage.open_device(args.device, "train_brdf_crf")
-    files, _, ps, n = stage.open_training_set(args, device, cache_dir=args.cache_dir)
+    files, scene, ps, n = stage.open_training_set(args, device, cache_dir=args.cache_dir)
+    validation = None
+    if val_files is not None:
+        from .utils.validation import ValidationSet
+        emitter = None
+        if images:
+            from .model.emitter import SLFEmitter
+            emitter = SLFEmitter(args.emitter_path, args.voxel_path).to(device)
+            stage.freeze(emitter)
+        validation = ValidationSet.load(val_files, scene, device, emitter=emitter)
     material = NGPBRDF(*stage.voxel_range(args.voxel_path)).init_parameters()
     model_crf = EmorCRF(dim=args.crf_basis)
     if args.ckpt_path:
@@ -89,12 +121,14 @@ def main(argv=None):
             model_crf.load_state_dict(ck["model_crf"])
     material.to(device)
     model_crf.to(device)
-    trainer = BRDFCRFTrainer(material, model_crf, ps, args)
+    trainer = BRDFCRFTrainer(material, model_crf, ps, args, validation=validation)
     print(f"train_brdf_crf: {len(files['views'])} views of {files['img_hw'][0]} x {files['img_hw'][1]}, {n} pixels on the mesh, {len(ps)} steps per epoch; "
           f"starting at epoch {trainer.epoch}, step {trainer.global_step}", flush=True)
     trainer.fit(args.max_epochs)
-    last = trainer.history[-1] if trainer.history else {}
+    last = next((e for e in reversed(trainer.history) if "train/loss" in e), {})
     print(f"train_brdf_crf: {trainer.epoch} epochs, {trainer.global_step} steps; last logged loss {last.get('train/loss')}; checkpoint {trainer.ckpt_file}", flush=True)
+    if trainer.best is not None:
+        print(f"train_brdf_crf: best val/loss {trainer.best['val/loss']} after epoch {trainer.best['epoch']}; checkpoint {trainer.best_file}", flush=True)
     return 0
 
 

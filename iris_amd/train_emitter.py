@@ -20,11 +20,14 @@ call that returns the loss, the psnr and the gradient by L_sum (iris_amd.utils.l
 last.ckpt are iris_amd/utils/trainer.py's; the checkpoint holds `material.*` and `model_crf.*` (in the emitter mode: as loaded, so the file serves
 slf_refine, refine_shading and render as the reference's does) and `emitter.radiance`.
 
-Not built: the in-training validation images (the reference's validation(); `python -m iris_amd.render --ckpt last.ckpt` shows the same thing), TensorBoard /
-W&B logging (the scalars go to metrics.jsonl under the reference's names), the `val/loss`-monitored best checkpoint, the
-synthetic layout's `albedo` / `roughness` ground-truth scalars, the `Ranger` optimizer, `--res_scale` other than 1 for the real and synthetic layouts (the scannetpp layout takes any: its 8-bit files are resized on the
-device, iris_amd/utils/resize.py); `--val_step`,
-`--num_workers`, `--dir_val` and `--val_frame` are accepted and ignored.
+`--validate metric|images|all` (an addition; default none) turns on the reference's validation (validation_step, validation() and the val/loss-monitored
+checkpoint; iris_amd/utils/validation.py): val/loss and val/psnr over the validation views after every epoch with `best.ckpt` beside last.ckpt, and the
+validation images of view --val_frame every --val_step steps under outputs/<experiment_name>/<dir_val>/, rendered under the emitter being trained.
+
+Not built: the validation images' crfs.png and crfs_weight.png (matplotlib), TensorBoard / W&B logging (the scalars go to metrics.jsonl under the
+reference's names), the synthetic layout's `albedo` / `roughness` ground-truth scalars, the `Ranger` optimizer, `--res_scale` other than 1 for the real
+and synthetic layouts (the scannetpp layout takes any: its 8-bit files are resized on the device, iris_amd/utils/resize.py); `--num_workers` is accepted
+and ignored, and so are `--val_step`, `--dir_val` and `--val_frame` without --validate.
 """
 import argparse
 import os
@@ -51,14 +54,15 @@ class RadianceTrainer(base.Trainer):
     """scene: the Scene of the mesh; emitter: an SLFEmitterLearn; material: an NGPBRDF (loaded, or init_parameters() in mode 'initialize'); model_crf: an
     EmorCRF; all on the pixel set's device (the emitter is moved there).  pixel_set: a PixelSet(ray_diff=True) with exposure (and, in mode 'initialize',
     segmentation and int_albedo) that has been through restrict_to_hits(scene).  hparams: a dict or Namespace of options (default_hparams()).
-    mode: 'emitter' | 'initialize' (the module docstring).
+    mode: 'emitter' | 'initialize' (the module docstring).  validation: the utils.validation.ValidationSet of hparams['validate'], or None; its images are
+    rendered under `emitter`.
     training_step(batch) -> dict of 0-d device tensors under the names the mode logs; the checkpoint also holds `emitter.radiance`; everything else is
     utils.trainer.Trainer's."""
 
-    def __init__(self, scene, emitter, material, model_crf, pixel_set, hparams, mode):
+    def __init__(self, scene, emitter, material, model_crf, pixel_set, hparams, mode, validation=None):
         if mode not in MODES:
             raise L.IrisError(f"RadianceTrainer: mode {mode!r}, expected 'emitter' or 'initialize'")
-        super().__init__(pixel_set, hparams, PROGRAM_DEFAULTS)
+        super().__init__(pixel_set, hparams, PROGRAM_DEFAULTS, validation=validation)
         hp, self.mode, self.scene, self.emitter, self.material, self.model_crf = self.hparams, mode, scene, emitter, material, model_crf
         self.prefix, self.logged = MODES[mode]
         self.spp = int(hp["spp"])
@@ -134,12 +138,18 @@ def parser(prog="train_emitter", description="the emitter training stage"):
     return ap
 
 
+def cli_parser(prog="train_emitter", description="the emitter training stage"):
+    """parser() and --validate: what main() parses.  They stand apart because parser()'s option table is pinned option for option
+    (tests/test_stage_setup_cpu.py) as the table the stage had before it validated."""
+    return base.add_validate_option(parser(prog, description))
+
+
 def run(args, mode, stage_name):
     """main() of both stages: refuse, open the device, load, train"""
     from .model.brdf import NGPBRDF
     from .model.crf import EmorCRF
     from .model.emitter import SLFEmitterLearn
-    stage.refuse_unbuilt_training(args)               # everything that can be refused is refused before the device is touched
+    val_files = stage.refuse_unbuilt_training(args)   # everything that can be refused is refused before the device is touched
     if not args.emitter_path:
         raise L.IrisError("--emitter_path is needed: the emitter.pth of python -m iris_amd.extract_emitter_ldr, whose radiance this stage trains")
     if not args.voxel_path or not os.path.isfile(args.voxel_path):
@@ -151,8 +161,11 @@ def run(args, mode, stage_name):
                           "(python -m iris_amd.train_brdf_crf)")
     if int(args.spp) < 1 or int(args.SPP) // int(args.spp) < 1:
         raise L.IrisError(f"--SPP {args.SPP} --spp {args.spp}: expected 1 <= spp <= SPP (a step traces SPP // spp calls of spp samples)")
-    print(f"{stage_name}: --val_step, --num_workers, --dir_val and --val_frame are accepted and ignored (no in-training validation images, no loader "
-          "workers: the batches are made on the device)", flush=True)
+    if getattr(args, "validate", "none") == "none":
+        print(f"{stage_name}: --val_step, --num_workers, --dir_val and --val_frame are accepted and ignored (no in-training validation images, no loader "
+              "workers: the batches are made on the device)", flush=True)
+    else:
+        print(base.validation_notice(stage_name, args, val_files), flush=True)
     device = stage.open_device(args.device, stage_name)
     files, scene, ps, n = stage.open_training_set(args, device, ray_diff=True)
     material = NGPBRDF(*stage.voxel_range(args.voxel_path))
@@ -167,18 +180,24 @@ def run(args, mode, stage_name):
         model_crf = EmorCRF(dim=args.crf_basis, emor_path=args.emor_path).to(device)        # at its defaults (initialize.py:85)
     material.to(device)
     emitter = SLFEmitterLearn(args.emitter_path, args.voxel_path).to(device)
-    trainer = RadianceTrainer(scene, emitter, material, model_crf, ps, args, mode)
+    validation = None
+    if val_files is not None:
+        from .utils.validation import ValidationSet
+        validation = ValidationSet.load(val_files, scene, device)
+    trainer = RadianceTrainer(scene, emitter, material, model_crf, ps, args, mode, validation=validation)
     print(f"{stage_name}: {len(files['views'])} views of {files['img_hw'][0]} x {files['img_hw'][1]}, {n} pixels on the mesh, {len(ps)} steps per epoch of "
           f"{trainer.n_calls} x {trainer.spp} samples; starting at epoch {trainer.epoch}, step {trainer.global_step}", flush=True)
     trainer.fit(args.max_epochs)
-    last = trainer.history[-1] if trainer.history else {}
+    last = next((e for e in reversed(trainer.history) if trainer.prefix + "/loss" in e), {})
     print(f"{stage_name}: {trainer.epoch} epochs, {trainer.global_step} steps; last logged loss {last.get(trainer.prefix + '/loss')}; checkpoint {trainer.ckpt_file}",
           flush=True)
+    if trainer.best is not None:
+        print(f"{stage_name}: best val/loss {trainer.best['val/loss']} after epoch {trainer.best['epoch']}; checkpoint {trainer.best_file}", flush=True)
     return 0
 
 
 def main(argv=None):
-    return run(parser().parse_args(argv), "emitter", "train_emitter")
+    return run(cli_parser().parse_args(argv), "emitter", "train_emitter")
 
 
 def cli(argv=None):

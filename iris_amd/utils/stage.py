@@ -292,9 +292,11 @@ def add_common_options(parser, *names, **help_texts):
 def refuse_unbuilt_training(args):
     """what every trainer's main() refuses first, before the device is touched: a scannetpp root without its lists, camera file, mesh or first view's files
     (check_scannetpp_files: two JSON files and three image headers, nothing is decoded), what is not built of the real and synthetic layouts (--res_scale
-    != 1, no --ldr_img_dir: load_training_files' own messages), then --optimizer Ranger (make_optimizer's)"""
+    != 1, no --ldr_img_dir: load_training_files' own messages), then --optimizer Ranger (make_optimizer's), then, with --validate other than none, the
+    validation split's files, --val_frame and --val_step (utils.validation.check_validation_args) -> the validation files' dict, or None"""
     from .dataset.files import check_scannetpp_files, load_training_files
     from .trainer import make_optimizer
+    from .validation import check_validation_args
     dataset, root = args.dataset
     if dataset == "scannetpp":
         check_scannetpp_files(root, args.scene, args.res_scale)
@@ -302,6 +304,7 @@ def refuse_unbuilt_training(args):
         load_training_files(dataset, root, args.ldr_img_dir, res_scale=args.res_scale)
     if args.optimizer == "Ranger":
         make_optimizer(args.optimizer, [], args.learning_rate, args.weight_decay, networks=())
+    return check_validation_args(args)
 
 
 def exit_status(name, main, argv=None):

@@ -50,7 +50,29 @@ DEFAULT_OPTIONS = {
 }
 # train_brdf_crf.py:517-526 and train_emitter.py:396-403, and what the trainers here add; a stage with an option of its own extends the dict
 PROGRAM_DEFAULTS = dict(experiment_name=None, max_epochs=500, log_path="./logs", checkpoint_path="./checkpoints", resume=False, device=0, val_frame=0,
-                        log_every=50)
+                        log_every=50, validate="none")
+VALIDATE_MODES = ("none", "metric", "images", "all")
+
+
+def add_validate_option(parser):
+    """--validate: what a trainer's cli_parser() adds to its parser() (whose option table is pinned as it was before the trainers validated)"""
+    parser.add_argument("--validate", type=str, default=PROGRAM_DEFAULTS["validate"], choices=VALIDATE_MODES,
+                        help="metric: val/loss and val/psnr over the validation views after every epoch (metrics.jsonl) and best.ckpt, the epoch of the lowest "
+                             "val/loss; images: the validation images of view --val_frame every --val_step steps under outputs/<experiment_name>/<dir_val>; "
+                             "all: both; none (default): neither")
+    return parser
+
+
+def validation_notice(stage_name, args, files):
+    """the line a trainer prints, under --validate other than none, where it otherwise says that the validation options are ignored"""
+    parts = []
+    if args.validate in ("metric", "all"):
+        parts.append(f"val/loss and val/psnr over {len(files['views'])} validation views of {files['img_hw'][0]} x {files['img_hw'][1]} after every epoch "
+                     "(metrics.jsonl), best.ckpt and best.json beside last.ckpt")
+    if args.validate in ("images", "all"):
+        parts.append(f"the validation images of view {args.val_frame} every {args.val_step} steps under "
+                     f"{os.path.join('outputs', args.experiment_name, args.dir_val)} ({int(args.SPP) // int(args.spp)} rounds of {args.spp} samples)")
+    return f"{stage_name}: --validate {args.validate}: " + "; ".join(parts) + "; --num_workers is accepted and ignored (the batches are made on the device)"
 
 
 def add_trainer_options(parser):
@@ -107,9 +129,19 @@ class Trainer:
     step per batch.  The logged scalars stay on their device; every `log_every` steps that step's are read in ONE synchronisation, appended to
     `<log_path>/<experiment_name>/metrics.jsonl` and to `self.history`; a non-finite loss at such a read raises FloatingPointError with the step number.
     `<checkpoint_path>/<experiment_name>/last.ckpt` is written at the end of every epoch, `epoch` counting the completed ones; with hparams['resume'] and
-    that file in place the constructor restores parameters, optimizer state, epoch and global step from it, and the run continues as a straight one."""
+    that file in place the constructor restores parameters, optimizer state, epoch and global step from it, and the run continues as a straight one.
 
-    def __init__(self, pixel_set, hparams, program_defaults):
+    Validation (train_brdf_crf.py:331-499,539): `validation` is an object with `evaluate(scene, material)` -> {'val/loss', 'val/psnr'} (0-d tensors or
+    numbers) and `write_images(folder, step, frame, material, model_crf, SPP, spp, emitter=None)` (utils.validation.ValidationSet); hparams['validate']
+    says what is done with it.  'none' (the default): nothing -- the same files, log lines and output as a trainer without the object.  'metric' / 'all':
+    after every epoch's last.ckpt one line {'step', 'epoch', 'val/loss', 'val/psnr'} goes to metrics.jsonl and `history` ('step' and 'epoch' count the
+    completed ones, as the checkpoint does), and when val/loss is STRICTLY below the best so far the same checkpoint is written as `best.ckpt` beside
+    last.ckpt -- one fixed name where Lightning's ModelCheckpoint(monitor='val/loss', save_top_k=1) writes epoch=E-step=S.ckpt -- with `best.json`
+    {'val/loss', 'epoch', 'step'}, which --resume reads back.  'images' / 'all': before every step with global_step % val_step == 0, step 0 included,
+    the validation images of view val_frame are written to outputs/<experiment_name>/<dir_val>/ under the working directory.  Lightning's two-batch
+    sanity check before training is not reproduced."""
+
+    def __init__(self, pixel_set, hparams, program_defaults, validation=None):
         """hparams: a dict or Namespace of options; what is not among default_hparams(program_defaults) is dropped"""
         hp = default_hparams(program_defaults)
         given = vars(hparams) if isinstance(hparams, argparse.Namespace) else dict(hparams)
@@ -117,6 +149,13 @@ class Trainer:
         self.hparams, self.ps = hp, pixel_set
         self.epoch = self.global_step = 0
         self.history = []
+        self.validation, self.best = validation, None
+        if hp["validate"] not in VALIDATE_MODES:
+            raise L.IrisError(f"validate = {hp['validate']!r}: expected one of {', '.join(VALIDATE_MODES)}")
+        if hp["validate"] != "none" and validation is None:
+            raise L.IrisError(f"validate = {hp['validate']!r} needs a validation object (utils.validation.ValidationSet)")
+        if hp["validate"] in ("images", "all") and int(hp["val_step"]) < 1:
+            raise L.IrisError(f"val_step = {hp['val_step']}: a positive number of steps is expected")
 
     def _start(self, params, networks):
         """the optimizer over the subclass's parameters (networks: FusedAdam's), the two files' names, --resume"""
@@ -125,8 +164,13 @@ class Trainer:
         name = hp["experiment_name"]
         self.ckpt_file = os.path.join(hp["checkpoint_path"], name, "last.ckpt") if name and hp["checkpoint_path"] else None
         self.log_file = os.path.join(hp["log_path"], name, "metrics.jsonl") if name and hp["log_path"] else None
+        self.best_file = os.path.join(os.path.dirname(self.ckpt_file), "best.ckpt") if self.ckpt_file else None
         if hp["resume"] and self.ckpt_file and os.path.exists(self.ckpt_file):
             self.load(self.ckpt_file)
+            best_json = os.path.join(os.path.dirname(self.ckpt_file), "best.json")
+            if hp["validate"] in ("metric", "all") and os.path.exists(best_json):
+                with open(best_json) as fh:
+                    self.best = json.load(fh)
 
     def learning_rate(self, epoch):
         hp = self.hparams
@@ -160,20 +204,49 @@ class Trainer:
         loss = entry[self.prefix + "/loss"]
         if not math.isfinite(loss):
             raise FloatingPointError(f"the loss of step {step} (epoch {epoch}) is {loss}: " + json.dumps(entry))
+        self._append(entry)
+
+    def _append(self, entry):
         self.history.append(entry)
         if self.log_file:
             os.makedirs(os.path.dirname(os.path.abspath(self.log_file)), exist_ok=True)
             with open(self.log_file, "a") as fh:
                 fh.write(json.dumps(entry) + "\n")
 
+    def validate_epoch(self):
+        """the end of an epoch under validate = metric | all: the val/* line, and best.ckpt + best.json when val/loss is strictly below the best so far"""
+        out = self.validation.evaluate(getattr(self, "scene", None), self.material)
+        loss, psnr = torch.stack([torch.as_tensor(out[k]).detach().reshape(()).to(torch.float64).cpu() for k in ("val/loss", "val/psnr")]).tolist()
+        entry = {"step": self.global_step, "epoch": self.epoch, "val/loss": loss, "val/psnr": psnr}
+        self._append(entry)
+        if self.best_file and not math.isnan(loss) and (self.best is None or loss < self.best["val/loss"]):            # (a NaN is never the best)
+            self.best = {"val/loss": loss, "epoch": self.epoch, "step": self.global_step}
+            self.save(self.best_file)
+            tmp = os.path.join(os.path.dirname(self.best_file), "best.json.tmp")
+            with open(tmp, "w") as fh:
+                json.dump(self.best, fh)
+            os.replace(tmp, os.path.join(os.path.dirname(self.best_file), "best.json"))
+        return entry
+
+    def validation_images(self):
+        """validation() at the current parameters: view val_frame into outputs/<experiment_name>/<dir_val>/ under the working directory (:345)"""
+        hp = self.hparams
+        folder = os.path.join("outputs", str(hp["experiment_name"]), str(hp["dir_val"]))
+        return self.validation.write_images(folder, self.global_step, int(hp["val_frame"]), self.material, self.model_crf, int(hp["SPP"]), int(hp["spp"]),
+                                            emitter=getattr(self, "emitter", None))
+
     def fit(self, max_epochs):
         every = max(1, int(self.hparams["log_every"]))
+        mode = self.hparams["validate"]
+        val_step = int(self.hparams["val_step"]) if mode in ("images", "all") else 0
         for epoch in range(self.epoch, int(max_epochs)):
             lr = self.learning_rate(epoch)
             for group in self.optimizer.param_groups:
                 group["lr"] = lr
             self.ps.resample()
             for i in range(len(self.ps)):
+                if val_step and self.global_step % val_step == 0:
+                    self.validation_images()
                 out = self.training_step(self.ps[i], self.global_step)
                 self.optimizer.zero_grad(set_to_none=True)
                 out["loss"].backward()
@@ -184,4 +257,6 @@ class Trainer:
             self.epoch = epoch + 1
             if self.ckpt_file:
                 self.save()
+            if mode in ("metric", "all"):
+                self.validate_epoch()
         return self
