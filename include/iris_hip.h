@@ -729,6 +729,22 @@ IRIS_API int iris_texture_sample(const int64_t *tri, const float *bary, int64_t 
 IRIS_API int iris_texture_material(const iris_scene *, const float *xs, int64_t B, const int32_t *ft, int64_t F, const float *vt, int64_t n_vt,
                           const uint8_t *albedo_img, const uint8_t *rm_img, int32_t H, int32_t W, float *albedo, float *roughness, float *metallic, iris_stream_t);
 
+/* ---- 5c-20: the trainable texture (model/texture.py TextureBRDF, utils/texture.py fit_textures; the contract: DESIGN.md 5c-20) ----------------- */
+/* iris_texture_sample_f32: iris_texture_sample with ONE float32 image texels (H, W, 5) = albedo r, g, b, roughness, metallic per texel in place of the two 8-bit
+ * images: the same float32 UV, clamp, taps and lerp form, step for step; the taps are the texel values themselves (no / 255); roughness = max(lerp, 0.02); tri
+ * outside [0, F) gives zeros and roughness 0.02.  With texels = byte / 255 (a float32 division) the outputs equal iris_texture_sample's bit for bit.
+ * iris_texture_sample_f32_bwd: the same point inputs and texels, and the outputs' gradients g_albedo (B, 3), g_roughness (B), g_metallic (B); ADDS into g_texels
+ * (H, W, 5), which the caller zeroes (or keeps, to accumulate): per point and channel w00 g, w01 g, w10 g, w11 g to the four taps, w00 = (1 - fx)(1 - fy),
+ * w01 = fx (1 - fy), w10 = (1 - fx) fy, w11 = fx fy in float32; taps that the clamp merges (x1 == x0, y1 == y0) sum on one texel.  The roughness gradient passes
+ * only where the interpolated value is > 0.02; rows without a triangle add nothing; there is no gradient for bary, vt or positions.  The adds are float atomics on
+ * global memory, twenty per point: REPRODUCIBLE TO ROUNDING, NOT BIT FOR BIT (the arrival order is not fixed); per texel channel within (n + 4) 2^-24 sum |w g| of the
+ * exact sum over its n contributions.  Both: one launch, a grid-stride loop over B with 64-bit indices; B = 0 launches nothing; H and W in [1, 8192]. */
+IRIS_API int iris_texture_sample_f32(const int64_t *tri, const float *bary, int64_t B, const int32_t *ft, int64_t F, const float *vt, int64_t n_vt,
+                            const float *texels, int32_t H, int32_t W, float *albedo, float *roughness, float *metallic, iris_stream_t);
+IRIS_API int iris_texture_sample_f32_bwd(const int64_t *tri, const float *bary, int64_t B, const int32_t *ft, int64_t F, const float *vt, int64_t n_vt,
+                                const float *texels, int32_t H, int32_t W, const float *g_albedo, const float *g_roughness, const float *g_metallic,
+                                float *g_texels, iris_stream_t);
+
 /* ---- misc --------------------------------------------------------------------------------------------- */
 /* Philox uniforms exactly as the bake kernels draw them (for tests): u2[i] = U(seed, idx0+i, stream_id). */
 IRIS_API int iris_philox_u2(uint64_t seed, uint64_t idx0, uint32_t stream_id, int64_t n, float *u2, iris_stream_t);

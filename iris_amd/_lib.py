@@ -172,6 +172,8 @@ PROTOTYPES = {
     "iris_closest_point": [_P, _P, _I64, _P, _P, _P, _P, _P],
     "iris_texture_sample": [_P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P],
     "iris_texture_material": [_P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I32, _I32, _P, _P, _P, _P],
+    "iris_texture_sample_f32": [_P, _P, _I64, _P, _I64, _P, _I64, _P, _I32, _I32, _P, _P, _P, _P],
+    "iris_texture_sample_f32_bwd": [_P, _P, _I64, _P, _I64, _P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P],
     "iris_exr_zip_workspace_bytes": [_I32, _I64, _I64, _I64],
     "iris_exr_zip_encode": [_P, _P, _I32, _I64, _I64, _I64, _I32, _P, _P, _P, _U64, _P],
     "iris_png_row_bytes": [_I32, _I32, _I32, _I32],

@@ -1508,6 +1508,34 @@ extern "C" IRIS_API int iris_texture_material(const iris_scene* s, const float* 
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }
+// 5c-20: the trainable texture's float texels (iris_texmat.h)
+static int texels_args(const char* who, const int64_t* tri, const float* bary, int64_t B, const int32_t* ft, int64_t F, const float* vt, int64_t n_vt, const float* texels,
+                       int32_t H, int32_t W, const float* albedo, const float* rough, const float* metal, TexelsDev& t) {
+    if (H < 1 || W < 1 || H > kUvMaxRes || W > kUvMaxRes || F < 0 || n_vt < 0 || B < 0)
+        return fail(IRIS_ERR_ARG, std::string(who) + ": bad sizes (H " + std::to_string(H) + ", W " + std::to_string(W) + ", F " + std::to_string(F) + ", n_vt " +
+                                      std::to_string(n_vt) + ", B " + std::to_string(B) + "): H and W in [1, 8192]");
+    if (!texels || (F > 0 && (!ft || !vt)) || (B > 0 && (!tri || !bary || !albedo || !rough || !metal)) || (uintptr_t)ft % 4 || (uintptr_t)vt % 4 || (uintptr_t)texels % 4 ||
+        (uintptr_t)tri % 8 || (uintptr_t)bary % 4 || (uintptr_t)albedo % 4 || (uintptr_t)rough % 4 || (uintptr_t)metal % 4)
+        return fail(IRIS_ERR_ARG, std::string(who) + ": null or misaligned pointer");
+    t.ft = ft; t.vt = vt; t.texels = texels; t.F = F; t.n_vt = n_vt; t.H = (int)H; t.W = (int)W;
+    return IRIS_OK;
+}
+extern "C" IRIS_API int iris_texture_sample_f32(const int64_t* tri, const float* bary, int64_t B, const int32_t* ft, int64_t F, const float* vt, int64_t n_vt,
+                                                const float* texels, int32_t H, int32_t W, float* albedo, float* rough, float* metal, iris_stream_t stream) {
+    TexelsDev t;
+    if (int rc = texels_args("iris_texture_sample_f32", tri, bary, B, ft, F, vt, n_vt, texels, H, W, albedo, rough, metal, t)) return rc;
+    if (B == 0) return IRIS_OK;
+    return launch1d(texture_sample_f32_kernel, B, 4096, stream, t, tri, bary, B, albedo, rough, metal);
+}
+extern "C" IRIS_API int iris_texture_sample_f32_bwd(const int64_t* tri, const float* bary, int64_t B, const int32_t* ft, int64_t F, const float* vt, int64_t n_vt,
+                                                    const float* texels, int32_t H, int32_t W, const float* g_albedo, const float* g_rough, const float* g_metal,
+                                                    float* g_texels, iris_stream_t stream) {
+    TexelsDev t;
+    if (int rc = texels_args("iris_texture_sample_f32_bwd", tri, bary, B, ft, F, vt, n_vt, texels, H, W, g_albedo, g_rough, g_metal, t)) return rc;
+    if (!g_texels || (uintptr_t)g_texels % 4 || g_texels == texels) return fail(IRIS_ERR_ARG, "iris_texture_sample_f32_bwd: g_texels is null, misaligned or the texels themselves");
+    if (B == 0) return IRIS_OK;
+    return launch1d(texture_sample_f32_bwd_kernel, B, 4096, stream, t, tri, bary, B, g_albedo, g_rough, g_metal, g_texels);
+}
 
 __global__ void philox_kernel(uint64_t seed, uint64_t idx0, uint32_t stream_id, int64_t n, float* __restrict__ u2) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {

@@ -3,10 +3,12 @@
 they take NGPBRDF.
 
 The reference's TextureBRDF (model/brdf.py:262) is an unused, trainable uv -> sigmoid(texture) stub; BakedTextureBRDF is not that class: it reads the export's
-8-bit files, takes POSITIONS (closest triangle of the mesh -> its UVs -> a bilinear fetch) and has no parameters.
+8-bit files, takes POSITIONS (closest triangle of the mesh -> its UVs -> a bilinear fetch) and has no parameters.  TextureBRDF is the
+trainable one: the same fetch over float32 texels, with a backward pass to the texels, which `utils.export --fit_steps` fits to the network.
 
 Not built: mip levels or any filtering by the ray's footprint (every lookup is one bilinear fetch of the full-resolution image), sRGB textures (the export
-writes linear values and they are read as linear values), gradients (forward only)."""
+writes linear values and they are read as linear values), gradients of BakedTextureBRDF and sample_textures (forward only; TextureBRDF has the gradient to its
+texels), gradients to UVs, barycentrics or positions, a bitwise-reproducible backward."""
 import os
 
 import numpy as np
@@ -161,3 +163,99 @@ class BakedTextureBRDF(BaseBRDF):
     def sample(self, tri, bary):
         """sample_textures on this material's tables (nothing is uploaded again)"""
         return _sample(self.tex, tri, bary)
+
+
+class _TexelSample(torch.autograd.Function):
+    """texels (H, W, 5) -> (albedo, roughness, metallic) at fixed (tri, bary): iris_texture_sample_f32 and its backward, which recomputes the taps and the
+    roughness gate from the texels and adds into a zeroed gradient with float atomics (reproducible to rounding, not bit for bit)."""
+
+    @staticmethod
+    def forward(ctx, texels, owner, tri, bary):
+        ctx.owner, ctx.tri, ctx.bary = owner, tri, bary
+        ctx.save_for_backward(texels)
+        B = tri.shape[0]
+        out = _outputs(B, texels.device)
+        with torch.cuda.device(texels.device):
+            L.check(L.lib().iris_texture_sample_f32(L.ptr(tri), L.ptr(bary), B, *owner._args(texels), *(L.ptr(o) for o in out), L.stream()))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_albedo, g_rough, g_metal):
+        (texels,) = ctx.saved_tensors
+        B, dev = ctx.tri.shape[0], texels.device
+        grad = torch.zeros_like(texels)
+        if B > 0:
+            def cot(g, shape):
+                return torch.zeros(shape, device=dev) if g is None else g.to(torch.float32).contiguous()
+            g_albedo, g_rough, g_metal = cot(g_albedo, (B, 3)), cot(g_rough, (B,)), cot(g_metal, (B,))
+            with torch.cuda.device(dev):
+                L.check(L.lib().iris_texture_sample_f32_bwd(L.ptr(ctx.tri), L.ptr(ctx.bary), B, *ctx.owner._args(texels), L.ptr(g_albedo), L.ptr(g_rough),
+                                                            L.ptr(g_metal), L.ptr(grad), L.stream()))
+        return grad, None, None, None
+
+
+class TextureBRDF(BaseBRDF):
+    """The exported textures as a TRAINABLE material: one parameter `texels`, (H, W, 5) float32 on the device -- albedo r, g, b,
+    roughness, metallic per texel -- read by BakedTextureBRDF's fetch with the taps taken as they are (iris_texture_sample_f32), and differentiable with respect
+    to the texels (iris_texture_sample_f32_bwd).  It starts from the export's 8-bit images, texels = byte / 255 (a float32 division: sample() then equals
+    BakedTextureBRDF.sample() bit for bit), is fitted to the network by utils.texture.fit_textures, and goes back to 8 bits with to_images().
+    (The reference's unused TextureBRDF, model/brdf.py:262, is uv -> sigmoid(texture); this one takes positions or (tri, bary) and stores the values themselves.)
+
+    scene, ft, vt, the images: as BakedTextureBRDF.  position, bary and vt get no gradient, and a position or bary that requires grad raises.  FusedAdam steps
+    `texels` as any contiguous float32 device tensor.  The gradient is summed with float atomics: reproducible to rounding, not bit for bit."""
+
+    def __init__(self, scene, ft, vt, albedo_img, rm_img):
+        super().__init__()
+        self.scene = scene
+        tex = _Textures(ft, vt, albedo_img, rm_img, scene.device, n_faces=scene.n_triangles)
+        self.H, self.W, self.ft, self.vt = tex.H, tex.W, tex.ft, tex.vt
+        bytes5 = torch.cat([tex.albedo, tex.rm[..., :2]], dim=-1).to(torch.float32)
+        # (a tensor divisor: torch turns a division by a Python scalar into a multiplication by its reciprocal, which is not the fetch's byte / 255)
+        self.texels = torch.nn.Parameter((bytes5 / torch.tensor(255.0, device=tex.device)).contiguous())
+
+    from_export = classmethod(BakedTextureBRDF.from_export.__func__)
+
+    def _args(self, texels):
+        return (L.ptr(self.ft), self.ft.shape[0], L.ptr(self.vt), self.vt.shape[0], L.ptr(texels), self.H, self.W)
+
+    def sample(self, tri, bary):
+        """tri (B,) int64, bary (B, 2) float32 on the device -> {'albedo' (B, 3), 'roughness' (B, 1), 'metallic' (B, 1)}, differentiable w.r.t. texels"""
+        L.no_autograd("TextureBRDF.sample", bary)
+        texels = self.texels
+        if not texels.is_cuda or texels.dtype != torch.float32 or not texels.is_contiguous() or tuple(texels.shape) != (self.H, self.W, 5):
+            raise L.IrisError(f"TextureBRDF: texels must stay a contiguous ({self.H}, {self.W}, 5) float32 tensor on the device "
+                              f"(it is {tuple(texels.shape)} {texels.dtype} on {texels.device})")
+        tri = L.require_gpu(tri, torch.int64, "tri").reshape(-1)
+        bary = L.require_gpu(bary, torch.float32, "bary").detach().reshape(-1, 2)
+        B = tri.shape[0]
+        if bary.shape[0] != B:
+            raise L.IrisError(f"TextureBRDF.sample: {B} triangles and {bary.shape[0]} barycentric pairs")
+        if tri.device != texels.device or bary.device != texels.device:
+            raise L.IrisError(f"TextureBRDF.sample: tri on {tri.device}, bary on {bary.device}, the texels on {texels.device}")
+        albedo, rough, metal = _TexelSample.apply(texels, self, tri, bary)
+        return {"albedo": albedo, "roughness": rough.reshape(B, 1), "metallic": metal.reshape(B, 1)}
+
+    def forward(self, position):
+        """position (..., 3) float32 on the GPU -> NGPBRDF.forward's dict: closest_point, then sample at its (tri, bary) (two launches: the query dominates)"""
+        from ..utils.closest import closest_point
+        L.no_autograd("TextureBRDF.forward", position)
+        position = L.require_gpu(position, torch.float32, "position")
+        shape = position.shape[:-1]
+        tri, bary, _, _ = closest_point(self.scene, position.detach().reshape(-1, 3))
+        out = self.sample(tri, bary)
+        return {"albedo": out["albedo"].reshape(*shape, 3), "roughness": out["roughness"].reshape(*shape, 1), "metallic": out["metallic"].reshape(*shape, 1)}
+
+    @torch.no_grad()
+    def to_images(self):
+        """-> (albedo_img, rm_img), (H, W, 3) uint8 on the device: floor(clamp(x, 0, 1) * 255 + 0.5) in float32, a NaN as 0; rm = (roughness, metallic, 0).
+        Rounds to nearest where the bake truncates: a fitted value has no reason to be truncated."""
+        return quantize_texels(self.texels)
+
+
+def quantize_texels(texels):
+    """to_images' rule on an (H, W, 5) float32 tensor, wherever it lives -> (albedo (H, W, 3), rm (H, W, 3)) uint8"""
+    t = texels.detach().to(torch.float32)
+    t = torch.where(torch.isnan(t), torch.zeros_like(t), t).clamp(0.0, 1.0)
+    q = torch.floor(t * 255.0 + 0.5).to(torch.uint8)
+    return q[..., :3].contiguous(), torch.cat([q[..., 3:5], torch.zeros_like(q[..., :1])], dim=-1).contiguous()

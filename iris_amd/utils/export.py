@@ -8,7 +8,7 @@ with ft.npy / vt.npy, the atlas they were baked in.  The voxel bounds come from 
 its own: DESIGN.md section 5c-7), the network runs on every texel, the outputs are quantised on the device; the PNGs are written with zlib alone.
 
 Additions: --material pkg.module:factory (as the other command lines); --atlas auto|files|grid|area; --dilate N; --write_obj (mesh.obj + mesh.mtl next to the
-images); --verify N.
+images); --verify N; --fit_steps N with --fit_points, --fit_lr, --fit_seed.
     --atlas files  reads <dir_save>/ft.npy and vt.npy, exactly the reference's cache: an atlas unwrapped with xatlas elsewhere drops in that way.
     --atlas grid   builds texture.grid_atlas (two faces per grid cell, shape and area ignored: valid, not good) and saves the two files.
     --atlas area   builds texture.area_atlas on the device from the loaded mesh (one chart per face in a power-of-two cell sized by the face's area, placed in
@@ -20,9 +20,15 @@ images); --verify N.
     --verify N     (default 0: off) after the files are written, the network and the textures read back (BakedTextureBRDF on the arrays still on the device)
                    are evaluated at N surface points -- face i F // N, barycentrics from a CPU generator seeded with 0 -- and one line prints the PSNR of albedo,
                    roughness and metallic: whether --tex_res and --dilate were enough.
+    --fit_steps N  (default 0: off, every file as before) after the bake and the dilation, the images become a model.texture.TextureBRDF (float texels, the same
+                   bilinear fetch, differentiable) that texture.fit_textures fits to the network: N Adam steps of --fit_lr (default 5e-3, about one 8-bit code
+                   per step) on --fit_points (default 262144) area-proportional surface points per step, drawn from --fit_seed (default 0).  albedo.png and
+                   rm.png are then its to_images(), ROUNDED to 8 bits; the first and the last loss are printed, and --verify prints its line twice, before and
+                   after the fit, at the same points.  
 
 Not built: calling xatlas itself (not a dependency, no ROCm relevance: run it anywhere and drop the .npy files in); charts of several faces and charts that keep
-a face's shape (every chart of the two built-in atlases is a right isosceles triangle); a non-square texture for --atlas area; reading vt from an OBJ.
+a face's shape (every chart of the two built-in atlases is a right isosceles triangle); a non-square texture for --atlas area; reading vt from an OBJ; fitting
+the textures to the photographs (through train_brdf_crf) instead of to the network; mip levels and sRGB for the fitted textures.
 """
 import os
 import sys
@@ -34,11 +40,11 @@ from .. import _lib as L
 from . import stage, texture as T
 
 
-def build_parser(area_atlas=False, verify=False):
+def build_parser(area_atlas=False, verify=False, fit=False):
     """The stage's parser.  build_parser() is the stage as it was first built -- the reference's arguments, --material, --atlas auto|files|grid, --write_obj:
     the option table that tests/test_stage_setup_cpu.py pins, option for option.  build_parser(area_atlas=True) is that plus what the built-in area atlas
     brought, the choice --atlas area and the option --dilate (tests/test_atlas_cpu.py pins that table whole).  build_parser(area_atlas=True, verify=True) is
-    the command line that main() runs: one more option, --verify N."""
+    that plus --verify N, and build_parser(area_atlas=True, verify=True, fit=True) the command line that main() runs: the four options of the fit."""
     import argparse
     parser = argparse.ArgumentParser(description="python -m iris_amd.utils.export: the reference's utils/export.py on MI355X")
     parser.add_argument("--mesh")
@@ -59,6 +65,12 @@ def build_parser(area_atlas=False, verify=False):
     if verify:
         parser.add_argument("--verify", type=int, default=0, metavar="N", help="after the files are written: the PSNR of the textures, read back through "
                             "model.texture.BakedTextureBRDF, against the network at N surface points (0, the default: off)")
+    if fit:
+        parser.add_argument("--fit_steps", type=int, default=0, metavar="N", help="after the bake: N Adam steps that fit the textures, read back bilinearly, to the "
+                            "network at surface points; the images are then rounded to 8 bits (0, the default: off)")
+        parser.add_argument("--fit_points", type=int, default=262144, metavar="M", help="surface points per step of the fit")
+        parser.add_argument("--fit_lr", type=float, default=5e-3, help="the fit's learning rate (about one 8-bit code per step)")
+        parser.add_argument("--fit_seed", type=int, default=0, help="the seed of the fit's surface points")
     return parser
 
 
@@ -136,9 +148,10 @@ def load_atlas(mode, dir_save, n_faces, tex_res, v=None, f=None, device=None):
 
 def main(argv=None):
     from .path_tracing import load_mesh
-    args = build_parser(area_atlas=True, verify=True).parse_args(argv)
+    args = build_parser(area_atlas=True, verify=True, fit=True).parse_args(argv)
     if args.verify < 0:
         raise L.IrisError(f"export: --verify {args.verify}: a number of points, 0 for none")
+    T.check_fit_options(args.fit_steps, args.fit_points, args.fit_lr)
     for name in ("mesh", "emitter_path", "dir_save"):
         if not getattr(args, name):
             raise L.IrisError(f"export: --{name} is required")
@@ -159,6 +172,20 @@ def main(argv=None):
         material_net.to(device)
     print(f"[INFO] mesh v={v_np.shape} f={f_np.shape} vt={vt_np.shape} ft={ft_np.shape}, texture {args.tex_res} x {args.tex_res}")
     albedo, rm = T.bake_textures(material_net, vt, ft, v_np, f_np, args.tex_res, args.chunk_size, device=device, dilate=args.dilate)
+
+    def verify():
+        q = verify_textures(material_net, v_np, f_np, vt, ft, albedo, rm, args.verify, device)
+        print(f"[INFO] verify: textures against the network at {args.verify} surface points: PSNR albedo {q['albedo']:.2f} dB, roughness {q['roughness']:.2f} dB, "
+              f"metallic {q['metallic']:.2f} dB")
+    if args.fit_steps:
+        from ..model.texture import TextureBRDF
+        from .path_tracing import Scene
+        if args.verify:
+            verify()                                                       # the baked images, before the fit
+        fitted = TextureBRDF(Scene(v_np, f_np, device=device), ft, vt, albedo, rm)
+        report = T.fit_textures(material_net, fitted, v_np, f_np, args.fit_steps, args.fit_points, args.fit_lr, seed=args.fit_seed)
+        albedo, rm = fitted.to_images()
+        print(f"[INFO] fit: {args.fit_steps} steps of {args.fit_points} surface points at lr {args.fit_lr:g}: loss {report['first_loss']:.6g} -> {report['last_loss']:.6g}")
     path_albedo, path_rm = os.path.join(args.dir_save, "albedo.png"), os.path.join(args.dir_save, "rm.png")
     T.write_png(path_albedo, albedo)
     T.write_png(path_rm, rm)
@@ -166,9 +193,7 @@ def main(argv=None):
         T.write_textured_obj(args.dir_save, v_np, f_np, vt_np, ft_np)
     print(f"[INFO] saved albedo to {path_albedo}, saved roughness and metallic to {path_rm}")
     if args.verify:
-        q = verify_textures(material_net, v_np, f_np, vt, ft, albedo, rm, args.verify, device)
-        print(f"[INFO] verify: textures against the network at {args.verify} surface points: PSNR albedo {q['albedo']:.2f} dB, roughness {q['roughness']:.2f} dB, "
-              f"metallic {q['metallic']:.2f} dB")
+        verify()
 
 
 if __name__ == "__main__":

@@ -207,6 +207,81 @@ def bake_textures(material_net, vt, ft, v, f, tex_res, chunk_size=160000, device
     return albedo, rm
 
 
+def check_fit_options(steps, points, lr):
+    """The host checks of the fit, before a device is touched -> (steps, points, lr).  IrisError on steps < 0, points < 1, lr <= 0 (or not a number)."""
+    for name, n, lo in (("steps", steps, 0), ("points", points, 1)):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < lo:
+            raise L.IrisError(f"fit_textures: {name} = {n!r}: an integer >= {lo}")
+    if isinstance(lr, bool) or not isinstance(lr, (int, float, np.integer, np.floating)) or not float(lr) > 0.0 or not np.isfinite(float(lr)):
+        raise L.IrisError(f"fit_textures: lr = {lr!r}: a finite number > 0")
+    return int(steps), int(points), float(lr)
+
+
+def surface_draw(v, f, points, seed, device):
+    """The fit's default draw(step) -> (face (points,) int64, bary (points, 2) float32) on the device: 2 * points uniform pairs of iris_philox_u2 with the key
+    (seed, stream = step); the first component of pair i < points picks the face by searchsorted on the float64 cumulative face areas (area-proportional),
+    pair points + i is the barycentrics, folded into the triangle as export.verify_points folds them (b1 + b2 > 1 -> (1 - b1, 1 - b2))."""
+    v64 = torch.as_tensor(_host(v), dtype=torch.float64).reshape(-1, 3)
+    f64 = torch.as_tensor(_host(f).astype(np.int64)).reshape(-1, 3)
+    p0, p1, p2 = (v64[f64[:, k]] for k in range(3))
+    area = 0.5 * torch.linalg.cross(p1 - p0, p2 - p0).norm(dim=-1)
+    area = torch.where(torch.isfinite(area), area, torch.zeros_like(area))
+    cum = torch.cumsum(area, 0)
+    if not float(cum[-1]) > 0.0:
+        raise L.IrisError("fit_textures: the mesh has no face of finite positive area to draw points on")
+    cum_d, total, n_faces = cum.to(device), float(cum[-1]), f64.shape[0]
+
+    def draw(step):
+        u = torch.empty(2 * points, 2, device=device, dtype=torch.float32)
+        with torch.cuda.device(device):
+            L.check(L.lib().iris_philox_u2(int(seed) & (2 ** 64 - 1), 0, int(step) & 0xFFFFFFFF, 2 * points, L.ptr(u), L.stream()))
+        face = torch.searchsorted(cum_d, u[:points, 0].double() * total, right=True).clamp_(max=n_faces - 1)
+        b = u[points:]
+        return face, torch.where((b[:, :1] + b[:, 1:]) > 1.0, 1.0 - b, b).contiguous()
+    return draw
+
+
+def fit_step(material_net, texture_brdf, optimizer, v_d, f_d, face, bary):
+    """One step of fit_textures on the points (face, bary); v_d (V, 3) float32 and f_d (F, 3) int64 on the device -> the loss, a 0-d device tensor"""
+    b1, b2 = bary[:, :1], bary[:, 1:]
+    p0, p1, p2 = (v_d[f_d[face, k]] for k in range(3))
+    with torch.no_grad():
+        want = material_net(((1.0 - b1 - b2) * p0 + b1 * p1) + b2 * p2)
+        want = torch.cat([want["albedo"].reshape(-1, 3), want["roughness"].reshape(-1, 1), want["metallic"].reshape(-1, 1)], dim=1)
+    got = texture_brdf.sample(face, bary)
+    loss = ((torch.cat([got["albedo"], got["roughness"], got["metallic"]], dim=1) - want) ** 2).mean()
+    optimizer.zero_grad(set_to_none=True)
+    loss.backward()
+    optimizer.step()
+    return loss.detach()
+
+
+def fit_textures(material_net, texture_brdf, v, f, steps, points, lr, seed=0, draw=None):
+    """Least-squares fit of a model.texture.TextureBRDF to the network it was baked from: what the bake's point sampling at texel centres
+    and its truncation to 8 bits lose against the bilinear read-back is won back, the texels just outside a chart -- which dilation only copies -- included.
+    Per step: (face, bary) = draw(step); position = ((1 - b1 - b2) p0 + b1 p1) + b2 p2 in float32 (verify_points' order); target = material_net(position) under
+    no_grad; prediction = texture_brdf.sample(face, bary); loss = the mean over the points and the 5 channels of the squared difference; one FusedAdam step at lr.
+    draw: None = surface_draw(v, f, points, seed, device), area-proportional; or a callable step -> (face int64 (M,), bary float32 (M, 2)) on the device.
+    -> {'steps', 'first_loss', 'last_loss'} (the losses are None for steps = 0; they are read back once, after the last step)."""
+    from .optim import FusedAdam
+    steps, points, lr = check_fit_options(steps, points, lr)
+    dev = texture_brdf.texels.device
+    report = {"steps": steps, "first_loss": None, "last_loss": None}
+    if steps == 0:
+        return report
+    v_d, f_d = _upload(v, torch.float32, dev).reshape(-1, 3), _upload(f, torch.int64, dev).reshape(-1, 3)
+    if draw is None:
+        draw = surface_draw(v, f, points, seed, dev)
+    optimizer = FusedAdam([texture_brdf.texels], lr=lr)
+    first = last = None
+    for step in range(steps):
+        last = fit_step(material_net, texture_brdf, optimizer, v_d, f_d, *draw(step))
+        if step == 0:
+            first = last
+    report["first_loss"], report["last_loss"] = float(first), float(last)
+    return report
+
+
 def grid_atlas(n_faces, tex_res):
     """The stand-in for xatlas, which is not a dependency: (vt (3F, 2) float32, ft = arange(3F).reshape(F, 3) int32), host numpy.
     Every face gets its own three UV vertices.  Two faces share a cell of a G x G grid, G = ceil(sqrt(ceil(F / 2))), as the two halves on either side of the
